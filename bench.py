@@ -10,9 +10,16 @@ shapes in R/models/diff_model.py:105-111, seeded random-init weights of the refe
 
 One "step" = one denoising step of the sampler on one batch: one SalUNet evaluation + its solver update.
 Trajectories run back to back; exactly K steps are timed (a trailing partial trajectory is cut after its
-last needed evaluation).  value = n_gpus * batch * K / max-over-ranks(wall time), inputs resident in HBM.
+last needed evaluation).  value = n_gpus * batch * K / max-over-ranks(wall time), inputs resident in HBM;
+ms_per_step = that wall time / K.
 
-Extra objects on the JSON line:
+A plain run sets up, warms up (W steps), times the K steps once and prints the line.  --dump-outputs DIR also writes
+what the last timed step returned (the network's output, or the fused step's noise prediction and next solver state)
+as DIR/<name>.npy.  Everything else is measured only with --full: 5 timed regions (median), the extra objects below,
+the reduced-precision passes (`alt_precision`), the encoders' `end_to_end` leg, the `train` leg and, at N > 1, rank 0's
+solo timing (`scaling_efficiency`).
+
+Extra objects on the JSON line (--full):
   roofline     -- the dominant kernel (fp32-MFMA implicit GEMM): algorithmic FLOPs of the launches of one
                   timed step / their HIP-event durations, vs the 157.3 TFLOP/s dense fp32 matrix peak.
   cpu_baseline -- the CPU oracle (oracle/salunet_oracle.py, "port") timed on this box's host cores on a
@@ -263,7 +270,7 @@ def plumbing_only(args, rank, world):
         ranks = dist.get_world_size()
         dist.barrier()
     train = None
-    if args.workload == "train" or not args.no_train_leg:
+    if args.workload == "train" or (args.full and not args.no_train_leg):
         train = plumbing_train_leg(world)
     if rank == 0 and args.workload == "train":
         print(json.dumps({"metric": "training samples/sec (diffusion train step of the denoiser: fwd + MSE + bwd + all-reduce + clip + Adam)",
@@ -315,6 +322,25 @@ def emit(result) -> None:
         _REAL_STDOUT_FD = None
     print(json.dumps(result), flush=True)
     quiet_stdout()          # teardown chatter (communicator destruction) goes to the log as well
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs: all files together
+DUMP_SAMPLE = 1 << 22          # elements kept of an array too large for its share
+
+
+def dump_outputs(out_dir, arrays) -> None:
+    """--dump-outputs: `arrays` (name -> tensor) as float32 `out_dir/<name>.npy`.  An array larger than its share of DUMP_BYTES is
+    written as a sample: the elements at a fixed, seeded, sorted set of flat indices (the same set for the same shape)."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1) // 4
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy().astype(np.float32)
+        if a.size > share:
+            idx = np.unique(np.random.default_rng(20240607).integers(0, a.size, size=min(share, DUMP_SAMPLE)))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 class Config:
@@ -633,14 +659,17 @@ def bench_train(args, net, cfg, feats, audio, dev, rank, world):
     for _ in range(max(args.warmup, 1)):
         ts.step(sal, cond)
     regions, ev, host_issue = [], [], []
+    profile = args.full or bool(args.dump_launches)     # HIP events around every operator of the last step (roofline, launch table)
     for rep_i in range(args.repeats):      # each region: exactly K steps between barrier + synchronize; MAX over ranks
-        el, loss, e = timed_train_region(ts, sal, cond, args.steps, dev, profile_last=rep_i == args.repeats - 1)
+        el, loss, e = timed_train_region(ts, sal, cond, args.steps, dev, profile_last=profile and rep_i == args.repeats - 1)
         if rep_i == 0:
             ranks_tab = rank_table(timed_train_region.own_s, B * args.steps, dev, world, "samples/s")
         ev = e or ev
         regions.append(el)
         host_issue.append(timed_train_region.host_issue_s)
     elapsed = median(regions)
+    if args.dump_outputs and rank == 0:      # what the last step gave its caller: the loss, and the parameters it updated
+        dump_outputs(args.dump_outputs, {"loss": loss.detach().reshape(1), "params": ts.flat.flat_p})
     if args.dump_launches and rank == 0:     # per-launch table of the profiled step (shape -> TF/s, GB/s)
         rows = []
         for e0, e1, fl, cls, nb, *note in ev:
@@ -675,21 +704,22 @@ def bench_train(args, net, cfg, feats, audio, dev, rank, world):
                    "exchange": "RCCL all-reduce of the flat fp32 gradient, bucketed, overlapped with backward",
                    "final_loss": float(loss.item())},
         "ranks": ranks_tab,
-        "exchange": exchange_report(ts, sal, cond, args.steps, dev, world, elapsed / args.steps * 1e3),
+        **({"exchange": exchange_report(ts, sal, cond, args.steps, dev, world, elapsed / args.steps * 1e3)} if args.full else {}),
         "repeats": args.repeats, "ms_per_step_all_regions": [round(r / args.steps * 1e3, 4) for r in regions],
         # host time to QUEUE a step's launches (Python + autograd tape + ~1 800 launches): when it reaches ms_per_step the step is
         # issue-bound and kernel-side savings no longer show (the first, unprofiled regions are the ones to read)
         "host_issue_ms_per_step": [round(h / args.steps * 1e3, 4) for h in host_issue],
         "rccl_ranks": ranks_seen, "backend": "nccl (RCCL)" if world > 1 else "none (single rank)", "devices": devices,
-        "roofline": {"kernel": "diffsal::igemm_kernel + wgrad_kernel (fp32 MFMA: forward, data-gradient and "
-                               "weight-gradient convolutions/GEMMs of one step)",
-                     "bound": "mfma", "achieved": round(achieved, 2), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                     "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": None, "launches_per_step": len(gemm_ev),
-                     "step_ms_in_kernel": round(k_ms, 3), "classes": class_table(ev, FP32_MFMA_PEAK_TFLOPS),
-                     # how much of the step the class table brackets (HIP events of every library operator of one step; the rest
-                     # is torch-native elementwise / copy / fill kernels of the autograd tape and launch gaps)
-                     "classified_ms": round(sum(e[0].elapsed_time(e[1]) for e in ev), 3), "operators_bracketed": len(ev)},
     }
+    if args.full:
+        result["roofline"] = {"kernel": "diffsal::igemm_kernel + wgrad_kernel (fp32 MFMA: forward, data-gradient and "
+                                        "weight-gradient convolutions/GEMMs of one step)",
+                              "bound": "mfma", "achieved": round(achieved, 2), "peak": FP32_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                              "frac": round(achieved / FP32_MFMA_PEAK_TFLOPS, 4), "traffic": None, "launches_per_step": len(gemm_ev),
+                              "step_ms_in_kernel": round(k_ms, 3), "classes": class_table(ev, FP32_MFMA_PEAK_TFLOPS),
+                              # how much of the step the class table brackets (HIP events of every library operator of one step; the
+                              # rest is torch-native elementwise / copy / fill kernels of the autograd tape and launch gaps)
+                              "classified_ms": round(sum(e[0].elapsed_time(e[1]) for e in ev), 3), "operators_bracketed": len(ev)}
     if rank == 0:
         emit(result)
     if world > 1:
@@ -724,8 +754,17 @@ def main():
                          "(BASELINE configs[1] / configs[4]; own tolerance table, DESIGN.md 2b).  All but fp32 are opt-in "
                          "modes reported separately from the headline")
     ap.add_argument("--no-alt-precision", action="store_true", help="skip the extra reduced-precision passes reported beside the headline")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of exactly --steps steps each; the reported value is their median (SURVEY 8d)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: roofline / per-kernel tables (a profiled step), the reference-graph "
+                         "step, the reduced-precision passes, the encoders' end-to-end leg, the `train` leg, the CPU baseline, rank 0's "
+                         "solo leg at N > 1 and the gradient-exchange report of --workload train; 5 timed regions by default.  Without it "
+                         "a run sets up, warms up, times --steps steps once and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32; "
+                         "at most 64 MB in all, a seeded fixed sample of anything larger)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed regions of exactly --steps steps each; the reported value is their median (SURVEY 8d).  "
+                         "Default 1, or 5 with --full")
     ap.add_argument("--dump-launches", default=None,
                     help="write every operator launch of the profiled step (class, GFLOP, MB, us, TF/s, GB/s) to this JSON file")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -747,6 +786,8 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=32,
                     help="host threads for the CPU baseline (32 is the fastest setting measured on the 256-core box)")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 1
     global EXCHANGE_MODE
     EXCHANGE_MODE = args.exchange
 
@@ -807,6 +848,12 @@ def main():
     state = {"budget": 0, "profile_last": False}
     inner = net.forward
 
+    def keep(out, names):
+        """the last step of a run_steps call: keep what it returned to the sampler (--dump-outputs)"""
+        if state["budget"] == 0:
+            state["last"] = dict(zip(names, out if isinstance(out, tuple) else (out,)))
+        return out
+
     def counted(x, t, f, a=None):
         if state["budget"] <= 0:
             raise _Stop
@@ -814,10 +861,10 @@ def main():
         if state["budget"] == 0 and state["profile_last"]:
             ops.PROFILE = []
             try:
-                return inner(x, t, f, a)
+                return keep(inner(x, t, f, a), ("x0_pred",))
             finally:
                 state["events"], ops.PROFILE = ops.PROFILE, None
-        return inner(x, t, f, a)
+        return keep(inner(x, t, f, a), ("x0_pred",))
 
     net.forward = counted
     inner_fused = net.forward_fused_update
@@ -830,10 +877,10 @@ def main():
         if state["budget"] == 0 and state["profile_last"]:
             ops.PROFILE = []
             try:
-                return inner_fused(x, t, f, a, **kw)
+                return keep(inner_fused(x, t, f, a, **kw), ("noise_pred", "x_next"))
             finally:
                 state["events"], ops.PROFILE = ops.PROFILE, None
-        return inner_fused(x, t, f, a, **kw)
+        return keep(inner_fused(x, t, f, a, **kw), ("noise_pred", "x_next"))
 
     net.forward_fused_update = counted_fused
 
@@ -852,7 +899,7 @@ def main():
     def run_steps(n, profile_last=False):
         if special:
             for _ in range(max(1, n // NFE_PER_TRAJECTORY)):
-                sampler.sample_dpm_solver(x_T, feats, audio)
+                state["last"] = {"x_final": sampler.sample_dpm_solver(x_T, feats, audio)}
             return
         state["budget"], state["profile_last"] = n, profile_last
         while state["budget"] > 0:
@@ -892,7 +939,7 @@ def main():
     # run configuration, against which the line reports its own weak-scaling efficiency (the driver computes its own from the
     # per-N lines; this one needs no second invocation)
     solo = None
-    if world > 1 and not args.no_solo_leg:
+    if world > 1 and args.full and not args.no_solo_leg:
         torch.cuda.synchronize()
         barrier()
         if rank == 0:
@@ -902,19 +949,16 @@ def main():
             solo = time.perf_counter() - t0
         barrier()
     regions = []
+    profile = args.full or bool(args.dump_launches)     # HIP events around every operator of the last step (roofline, launch table)
     for i in range(args.repeats):
-        regions.append(timed_region(i == args.repeats - 1))
+        regions.append(timed_region(profile and i == args.repeats - 1))
         if i == 0:
             ranks_tab = rank_table(state["own_s"], B * args.steps, dev, world, "denoise-steps/s")
     elapsed = median(regions)
 
-    # ---- roofline of the dominant kernel, from the HIP events recorded inside the timed region ----
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, state["last"])
     all_ev = state.get("events") or []
-    ev = [e for e in all_ev if e[3] in GEMM_CLASSES]          # the implicit-GEMM family = the dominant kernel
-    k_ms = sum(e[0].elapsed_time(e[1]) for e in ev)
-    k_flops = sum(e[2] for e in ev)
-    n_launch = max(len(ev), 1)
-    achieved = k_flops / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
     if args.dump_launches and rank == 0:
         rows = []
         for e0, e1, fl, cls, nb, *note in all_ev:
@@ -922,16 +966,68 @@ def main():
             rows.append({"class": cls, "op": note[0] if note else "", "kernel": note[1] if len(note) > 1 else "", "gflop": round(fl / 1e9, 4), "mbytes": round(nb / 1e6, 3), "us": round(us, 2),
                          "tflops": round(fl / us / 1e6, 2) if us > 0 else 0.0, "gbs": round(nb / us / 1e3, 1) if us > 0 else 0.0})
         json.dump({"precision": args.precision, "mode": args.mode, "batch": B, "launches": rows}, open(args.dump_launches, "w"), indent=0)
-    peak_for_mode = FP32_MFMA_PEAK_TFLOPS if args.precision == "fp32" else BF16_MFMA_PEAK_TFLOPS
-    # roofline.traffic: HBM bytes of the GEMM family per launch from the PMC passes of THIS code (tools/profile_round.sh; separate
-    # --pmc runs as the guide prescribes).  A profile taken on other sources is refused: traffic = null, and the line says why.
-    traffic, traffic_src = None, None
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     try:
         from build_id import source_id
         bid = source_id()
     except Exception:  # noqa: BLE001
         bid = None
+    DT_LABEL = {"fp32": "f32", "bf16x3": "f32 in/out, bf16x3 split-precision MFMA (NOT the headline configuration)",
+                "bf16": "bf16 storage, f32 accumulate (NOT the headline configuration; BASELINE configs[1] as written)",
+                "fp16": "f16 storage, f32 accumulate (NOT the headline configuration; BASELINE configs[4] arithmetic)"}
+    devices = [torch.cuda.get_device_name(dev)]
+    ranks_seen = 1
+    if world > 1:
+        import torch.distributed as dist
+
+        ranks_seen = dist.get_world_size()
+        names = [None] * world
+        dist.all_gather_object(names, f"cuda:{local_rank} {torch.cuda.get_device_name(dev)}")
+        devices = names
+    result = {
+        "metric": "denoise-steps/sec (batch x NFE / wall time), 16x224x384 clip, 50-step DPM-Solver",
+        "value": round(world * B * args.steps / elapsed, 3),
+        "unit": "denoise-steps/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "repeats": args.repeats, "ms_per_step_all_regions": [round(r / args.steps * 1e3, 4) for r in regions],
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": DT_LABEL[args.precision],
+        "data": "synthetic",
+        "config": {
+            "workload": ("BASELINE configs[1]: DHF1k visual-only" if not av else "BASELINE configs[2]: AVAD audio-visual")
+            + f", batch={B}/GPU, 224x384, 50-NFE DPM-Solver (multistep-2, logSNR, denoise-to-zero), faithful full graph",
+            "batch_per_gpu": B, "nfe_per_trajectory": NFE_PER_TRAJECTORY, "sharding": "clips by rank, no collective",
+            "step": "one SalUNet evaluation + DPM-Solver update on one batch",
+            "sampler_mode": args.sampler_mode + ("" if not special else " (NOT the headline configuration)"),
+            "gflop_per_clip_step": 151.61 if not av else 152.73,
+            **({"switches (A/B run, NOT the shipped defaults)": list(args.set)} if args.set else {}),
+        },
+        "rccl_ranks": ranks_seen, "backend": "nccl (RCCL)" if world > 1 else "none (single rank)", "devices": devices,
+        "ranks": ranks_tab,
+        **({"solo_rank0": {"what": "rank 0 alone, same configuration and K steps, the other GPUs idle (N = 1 reference of this run)",
+                           "value": round(B * args.steps / solo, 3), "ms_per_step": round(solo / args.steps * 1e3, 4)},
+            "scaling_efficiency": round((world * B * args.steps / elapsed) / (world * B * args.steps / solo), 4)}
+           if solo is not None else {}),
+        "build": bid,
+    }
+    if not args.full:
+        return finish(result, rank, world)
+
+    # ---- roofline of the dominant kernel, from the HIP events recorded inside the timed region ----
+    ev = [e for e in all_ev if e[3] in GEMM_CLASSES]          # the implicit-GEMM family = the dominant kernel
+    k_ms = sum(e[0].elapsed_time(e[1]) for e in ev)
+    k_flops = sum(e[2] for e in ev)
+    n_launch = max(len(ev), 1)
+    achieved = k_flops / (k_ms * 1e-3) / 1e12 if k_ms > 0 else 0.0
+    peak_for_mode = FP32_MFMA_PEAK_TFLOPS if args.precision == "fp32" else BF16_MFMA_PEAK_TFLOPS
+    # roofline.traffic: HBM bytes of the GEMM family per launch from the PMC passes of THIS code (tools/profile_round.sh; separate
+    # --pmc runs as the guide prescribes).  A profile taken on other sources is refused: traffic = null, and the line says why.
+    traffic, traffic_src = None, None
     # artefact suffix as tools/profile_round.sh writes it: precision [_b<batch> when not the headline batch of 4] [_av]
     suf = args.precision + (f"_b{B}" if B != 4 else "") + ("_av" if av else "")
     cands = sorted(f for f in os.listdir(os.path.join(ROOT, "profiles")) if f.endswith(f"_hbm_traffic_{suf}.json")) \
@@ -1025,50 +1121,7 @@ def main():
             "bound": "mfma", "achieved": round(achieved, 2), "peak": BF16_MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
             "frac": round(achieved / BF16_MFMA_PEAK_TFLOPS, 4), "traffic": traffic, "dominant_kernel": dominant, **common}
 
-    DT_LABEL = {"fp32": "f32", "bf16x3": "f32 in/out, bf16x3 split-precision MFMA (NOT the headline configuration)",
-                "bf16": "bf16 storage, f32 accumulate (NOT the headline configuration; BASELINE configs[1] as written)",
-                "fp16": "f16 storage, f32 accumulate (NOT the headline configuration; BASELINE configs[4] arithmetic)"}
-    devices = [torch.cuda.get_device_name(dev)]
-    ranks_seen = 1
-    if world > 1:
-        import torch.distributed as dist
-
-        ranks_seen = dist.get_world_size()
-        names = [None] * world
-        dist.all_gather_object(names, f"cuda:{local_rank} {torch.cuda.get_device_name(dev)}")
-        devices = names
-    result = {
-        "metric": "denoise-steps/sec (batch x NFE / wall time), 16x224x384 clip, 50-step DPM-Solver",
-        "value": round(world * B * args.steps / elapsed, 3),
-        "unit": "denoise-steps/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-        "repeats": args.repeats, "ms_per_step_all_regions": [round(r / args.steps * 1e3, 4) for r in regions],
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": DT_LABEL[args.precision],
-        "data": "synthetic",
-        "config": {
-            "workload": ("BASELINE configs[1]: DHF1k visual-only" if not av else "BASELINE configs[2]: AVAD audio-visual")
-            + f", batch={B}/GPU, 224x384, 50-NFE DPM-Solver (multistep-2, logSNR, denoise-to-zero), faithful full graph",
-            "batch_per_gpu": B, "nfe_per_trajectory": NFE_PER_TRAJECTORY, "sharding": "clips by rank, no collective",
-            "step": "one SalUNet evaluation + DPM-Solver update on one batch",
-            "sampler_mode": args.sampler_mode + ("" if not special else " (NOT the headline configuration)"),
-            "gflop_per_clip_step": 151.61 if not av else 152.73,
-            **({"switches (A/B run, NOT the shipped defaults)": list(args.set)} if args.set else {}),
-        },
-        "rccl_ranks": ranks_seen, "backend": "nccl (RCCL)" if world > 1 else "none (single rank)", "devices": devices,
-        "ranks": ranks_tab,
-        **({"solo_rank0": {"what": "rank 0 alone, same configuration and K steps, the other GPUs idle (N = 1 reference of this run)",
-                           "value": round(B * args.steps / solo, 3), "ms_per_step": round(solo / args.steps * 1e3, 4)},
-            "scaling_efficiency": round((world * B * args.steps / elapsed) / (world * B * args.steps / solo), 4)}
-           if solo is not None else {}),
-        "build": bid,
-        "roofline": roofline,
-    }
+    result["roofline"] = roofline
 
     if world == 1 and args.precision == "fp32" and not special and not args.no_alt_precision:
         # The same K steps once more in each opt-in reduced-precision mode, reported next to the headline (not instead of
@@ -1223,6 +1276,10 @@ def main():
                 result["cpu_baseline"]["dpm50_batch1"] = {
                     "value": round(nfe[0] / c2, 4), "unit": "denoise-steps/s", "cores": n1, "nfe": nfe[0], "seconds": round(c2, 2),
                     "sample": "one 50-NFE DPM-Solver trajectory (multistep-2, logSNR, denoise-to-zero) of one clip, host loop included"}
+    finish(result, rank, world)
+
+
+def finish(result, rank, world) -> None:
     if rank == 0:
         emit(result)
     if world > 1:

@@ -135,13 +135,13 @@ def test_bench_spawns_its_own_ranks():
     if torch.cuda.is_available():
         pytest.skip("plumbing-only mode is for GPU-less hosts")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-cpu-baseline", "--steps", "2",
-                        "--warmup", "1"], capture_output=True, text=True, timeout=300, env=env)
+                        "--warmup", "1", "--full"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     j = json.loads(lines[0])
     assert j["n_gpus"] == 2 and j["rccl_ranks"] == 2 and j["value"] is None and len(j["devices"]) == 2
-    # the default line carries a `train` object at every N (BASELINE configs[3]); here its gradient-exchange plumbing ran over gloo
+    # the --full line carries a `train` object at every N (BASELINE configs[3]); here its gradient-exchange plumbing ran over gloo
     tr = j["train"]
     ex = tr["exchange"]
     assert tr["n_gpus"] == 2 and ex["world"] == 2 and ex["collective_executed"] and ex["replicas_identical"] is True

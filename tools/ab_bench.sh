@@ -8,7 +8,7 @@ while getopts "r:o:c:" o; do case $o in r) R=$OPTARG;; o) OUT=$OPTARG;; c) COMMO
 shift $((OPTIND - 1))
 cd ${GRAFT_REPO_ROOT:-$(dirname $0)/..}
 D=gpurun_out/$OUT; mkdir -p $D; : > $D/ab.txt
-BASE="python3 bench.py --steps 50 --warmup 10 --no-cpu-baseline --no-train-leg --no-encoders --no-alt-precision --no-reference-graph $COMMON"
+BASE="python3 bench.py --full --steps 50 --warmup 10 --no-cpu-baseline --no-train-leg --no-encoders --no-alt-precision --no-reference-graph $COMMON"
 for i in $(seq $R); do
   for v in "$@"; do
     label=${v%%=*}; spec=${v#*=}

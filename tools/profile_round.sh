@@ -10,7 +10,7 @@ mkdir -p $OUT
 BID=$(python3 $GRAFT_REPO_ROOT/tools/build_id.py)
 SUF=${PREC}$([ -n "${BATCH:-}" ] && echo _b${BATCH})$([ "$MODE" = av ] && echo _av)
 cd /tmp && export TMPDIR=/tmp
-ARGS="--no-cpu-baseline --no-alt-precision --no-encoders --no-reference-graph --no-train-leg --precision $PREC --mode $MODE --warmup 5 --repeats 1$([ -n "${BATCH:-}" ] && echo " --batch ${BATCH}")"
+ARGS="--full --no-cpu-baseline --no-alt-precision --no-encoders --no-reference-graph --no-train-leg --precision $PREC --mode $MODE --warmup 5 --repeats 1$([ -n "${BATCH:-}" ] && echo " --batch ${BATCH}")"
 STEPS=${STEPS:-50}; PSTEPS=${PSTEPS:-10}
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$SUF -- python3 $GRAFT_REPO_ROOT/bench.py $ARGS --steps $STEPS --dump-launches $OUT/${TAG}_launches_$SUF.json > $OUT/${TAG}_bench_profiled_$SUF.json 2> $OUT/stats_$SUF.err
 cp $(find $OUT/stats_$SUF -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_${SUF}_kernel_stats.csv

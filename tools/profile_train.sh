@@ -6,8 +6,8 @@ OUT=$GRAFT_REPO_ROOT/gpurun_out/$1; TAG=$2
 mkdir -p $OUT
 BID=$(python3 $GRAFT_REPO_ROOT/tools/build_id.py)
 cd $GRAFT_REPO_ROOT
-python3 bench.py --workload train --mode av --steps 10 --warmup 3 --repeats 3 --dump-launches $OUT/${TAG}_launches_train.json > $OUT/${TAG}_train_full.json 2> $OUT/train.err
-python3 bench.py --workload train --mode av --train-scope decoder --steps 20 --warmup 3 --repeats 3 > $OUT/${TAG}_train_decoder.json 2>> $OUT/train.err
+python3 bench.py --full --workload train --mode av --steps 10 --warmup 3 --repeats 3 --dump-launches $OUT/${TAG}_launches_train.json > $OUT/${TAG}_train_full.json 2> $OUT/train.err
+python3 bench.py --full --workload train --mode av --train-scope decoder --steps 20 --warmup 3 --repeats 3 > $OUT/${TAG}_train_decoder.json 2>> $OUT/train.err
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_train -- python3 $GRAFT_REPO_ROOT/bench.py --workload train --mode av --steps 10 --warmup 3 --repeats 1 > /dev/null 2> $OUT/stats_train.err
 cp $(find $OUT/stats_train -name "*kernel_stats.csv" | head -1) $OUT/${TAG}_train_kernel_stats.csv
