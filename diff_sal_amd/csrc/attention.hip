@@ -23,7 +23,6 @@
 
 namespace diffsal {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // Staging discipline of the three kernels below.  The next tile's pieces are fetched with UNCONDITIONAL 16-byte loads from
 // addresses clamped into valid memory and kept raw in registers; whether a piece is real (inside the tile, key / query inside

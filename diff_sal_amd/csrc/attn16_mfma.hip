@@ -15,21 +15,6 @@
 
 namespace diffsal {
 
-typedef float am_f32x16 __attribute__((ext_vector_type(16)));
-typedef float am_f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 am_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 am_f16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T> struct AmMma;
-template <> struct AmMma<__bf16> {
-  typedef am_bf16x8 vec;
-  static __device__ __forceinline__ am_f32x16 run(vec a, vec b, am_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct AmMma<_Float16> {
-  typedef am_f16x8 vec;
-  static __device__ __forceinline__ am_f32x16 run(vec a, vec b, am_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
 // key -> its column in V^T's LDS rows: position 16 j + 8 h + e holds key 16 j + 4 h + (e < 4 ? e : e + 4), the order in which the keys
 // sit in the C/D registers of S^T (register r of lane half h = key 4 h + (r & 3) + 8 (r >> 2))
 __device__ __forceinline__ int am_key_col(int key) {
@@ -41,7 +26,7 @@ __device__ __forceinline__ int am_key_col(int key) {
 template <typename T, int D>
 __global__ __launch_bounds__(256, 2) void attention16_mfma_kernel(const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
                                                                   T* __restrict__ o, int Lq, int Lk, int C, int heads, float scale) {
-  typedef typename AmMma<T>::vec vec;
+  typedef typename Mfma32x16<T>::vec vec;
   constexpr int PW = D + 8, PV = 40;             // row pitches in elements: (D + 8) * 2 and 80 bytes, odd multiples of 16 bytes
   constexpr int KS = D / 16, NU = D / 32;        // k-steps of S^T, row tiles of O^T
   extern __shared__ __attribute__((aligned(16))) unsigned char am_smem[];
@@ -73,12 +58,12 @@ __global__ __launch_bounds__(256, 2) void attention16_mfma_kernel(const T* __res
   __syncthreads();
   if ((blockIdx.y * 4 + wave) * 32 >= Lq) return;           // a wavefront past the last query (uniform)
   // ---- S^T = K Q^T: rows = keys, this lane's column = its query
-  am_f32x16 st;
+  f32x16 st;
 #pragma unroll
   for (int r = 0; r < 16; ++r) st[r] = 0.f;
   const T* kf = Ks + ml * PW + 8 * hf;
 #pragma unroll
-  for (int s = 0; s < KS; ++s) st = AmMma<T>::run(*reinterpret_cast<const vec*>(kf + 16 * s), qb[s], st);
+  for (int s = 0; s < KS; ++s) st = Mfma32x16<T>::run(*reinterpret_cast<const vec*>(kf + 16 * s), qb[s], st);
   // ---- softmax over the keys: register r of lane half hf = key 4 hf + (r & 3) + 8 (r >> 2)
   float mx = -3.0e38f;
 #pragma unroll
@@ -102,11 +87,11 @@ __global__ __launch_bounds__(256, 2) void attention16_mfma_kernel(const T* __res
   vec pb[2], pl[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
-    am_f32x8 t8, r8;
+    f32x8_t t8, r8;
 #pragma unroll
     for (int e = 0; e < 8; ++e) t8[e] = st[8 * j + e] * inv;
     pb[j] = __builtin_convertvector(t8, vec);
-    const am_f32x8 back = __builtin_convertvector(pb[j], am_f32x8);
+    const f32x8_t back = __builtin_convertvector(pb[j], f32x8_t);
 #pragma unroll
     for (int e = 0; e < 8; ++e) r8[e] = t8[e] - back[e];
     pl[j] = __builtin_convertvector(r8, vec);
@@ -116,16 +101,16 @@ __global__ __launch_bounds__(256, 2) void attention16_mfma_kernel(const T* __res
   T* orow = o + (static_cast<long>(n) * Lq + tok) * C + cb + 4 * hf;
 #pragma unroll
   for (int u = 0; u < NU; ++u) {
-    am_f32x16 ot;
+    f32x16 ot;
 #pragma unroll
     for (int r = 0; r < 16; ++r) ot[r] = 0.f;
     const vec v0 = *reinterpret_cast<const vec*>(vf + 32 * u * PV);
-    ot = AmMma<T>::run(v0, pl[0], ot);
-    ot = AmMma<T>::run(v0, pb[0], ot);
+    ot = Mfma32x16<T>::run(v0, pl[0], ot);
+    ot = Mfma32x16<T>::run(v0, pb[0], ot);
     if (Lk > 16) {
       const vec v1 = *reinterpret_cast<const vec*>(vf + 32 * u * PV + 16);
-      ot = AmMma<T>::run(v1, pl[1], ot);
-      ot = AmMma<T>::run(v1, pb[1], ot);
+      ot = Mfma32x16<T>::run(v1, pl[1], ot);
+      ot = Mfma32x16<T>::run(v1, pb[1], ot);
     }
     if (live) {
 #pragma unroll

@@ -20,21 +20,6 @@
 
 namespace diffsal {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T> struct Blk16;
-template <> struct Blk16<__bf16> {
-  typedef bf16x8 vec;
-  static __device__ __forceinline__ f32x16 mma(vec a, vec b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct Blk16<_Float16> {
-  typedef f16x8 vec;
-  static __device__ __forceinline__ f32x16 mma(vec a, vec b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
 template <typename T>
 struct Block16Args {
   const T* o; const T* x;
@@ -56,8 +41,7 @@ template <> __device__ __forceinline__ float4 unpack4<__bf16>(uint2 u) {
                      __builtin_bit_cast(float, u.y << 16), __builtin_bit_cast(float, u.y & 0xFFFF0000u));
 }
 template <> __device__ __forceinline__ float4 unpack4<_Float16>(uint2 u) {
-  typedef _Float16 h4 __attribute__((ext_vector_type(4)));
-  const h4 h = __builtin_bit_cast(h4, u);
+  const f16x4_t h = __builtin_bit_cast(f16x4_t, u);
   return make_float4(static_cast<float>(h.x), static_cast<float>(h.y), static_cast<float>(h.z), static_cast<float>(h.w));
 }
 
@@ -75,7 +59,7 @@ template <typename T, int NW>
 __global__ __launch_bounds__(NW * 64, 1) void block16_kernel(Block16Args<T> p) {
   constexpr int NT = NW * 64;
   constexpr bool PREFETCH = NW == 4;
-  typedef typename Blk16<T>::vec vec;
+  typedef typename Mfma32x16<T>::vec vec;
   constexpr int C = 96, HID = 192;
   constexpr int P1 = C + 8, P2 = HID + 8;          // LDS row pitches in elements: 208 B and 400 B = odd multiples of 16 B
   extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
@@ -121,7 +105,7 @@ __global__ __launch_bounds__(NW * 64, 1) void block16_kernel(Block16Args<T> p) {
   };
   // B operand of k-step (tile u, half j) from the fp32 C/D registers of a previous product
   auto b_from = [&](const f32x16& a, int j) -> vec {
-    f32x8 t;
+    f32x8_t t;
 #pragma unroll
     for (int e = 0; e < 8; ++e) t[e] = a[8 * j + e];
     return __builtin_convertvector(t, vec);
@@ -164,7 +148,7 @@ __global__ __launch_bounds__(NW * 64, 1) void block16_kernel(Block16Args<T> p) {
       const vec b = __builtin_bit_cast(vec, oa[s]);
 #pragma unroll
       for (int u = 0; u < 3; ++u)
-        x1[u] = Blk16<T>::mma(*reinterpret_cast<const vec*>(wpf + 32 * u * P1 + 16 * s), b, x1[u]);
+        x1[u] = Mfma32x16<T>::run(*reinterpret_cast<const vec*>(wpf + 32 * u * P1 + 16 * s), b, x1[u]);
       __builtin_amdgcn_sched_barrier(0);
     }
 #pragma unroll
@@ -203,7 +187,7 @@ __global__ __launch_bounds__(NW * 64, 1) void block16_kernel(Block16Args<T> p) {
         const vec b = xb[u][j];
 #pragma unroll
         for (int t = 0; t < 6; ++t)
-          hid[t] = Blk16<T>::mma(*reinterpret_cast<const vec*>(w1f + 32 * t * P1 + 32 * u + 16 * j), b, hid[t]);
+          hid[t] = Mfma32x16<T>::run(*reinterpret_cast<const vec*>(w1f + 32 * t * P1 + 32 * u + 16 * j), b, hid[t]);
         __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
@@ -223,7 +207,7 @@ __global__ __launch_bounds__(NW * 64, 1) void block16_kernel(Block16Args<T> p) {
         const vec b = b_from(hid[t], j);
 #pragma unroll
         for (int u = 0; u < 3; ++u)
-          y[u] = Blk16<T>::mma(*reinterpret_cast<const vec*>(w2f + 32 * u * P2 + 32 * t + 16 * j), b, y[u]);
+          y[u] = Mfma32x16<T>::run(*reinterpret_cast<const vec*>(w2f + 32 * u * P2 + 32 * t + 16 * j), b, y[u]);
         __builtin_amdgcn_sched_barrier(0);
       }
     // ---- stores: 4 consecutive channels (8 bytes) per (u, g)

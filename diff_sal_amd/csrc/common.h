@@ -260,4 +260,83 @@ __device__ __forceinline__ void bilin_coord(int dst, float scale, int in_size, i
   l1 = s - static_cast<float>(i0);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------------
+// Building blocks of the matrix-core and LDS-DMA kernels: one copy of each, for every kernel.
+// ---------------------------------------------------------------------------------------------------------------------------
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) void* lds_ptr_t;   // (lds_ptr_t)p: a __shared__ object's LDS pointer (its value: the byte address)
+
+// v_mfma_f32_32x32x16 on 16-bit storage type T: vec = one 8-element operand fragment, run(a, b, c) = c + a x b in fp32
+template <typename T> struct Mfma32x16;
+template <> struct Mfma32x16<__bf16> {
+  typedef bf16x8_t vec;
+  static __device__ __forceinline__ f32x16 run(vec a, vec b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+template <> struct Mfma32x16<_Float16> {
+  typedef f16x8_t vec;
+  static __device__ __forceinline__ f32x16 run(vec a, vec b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+};
+
+// Word 3 of every buffer descriptor: 32-bit data format, no swizzle, no stride -- raw byte offsets, range-checked against the
+// descriptor's byte count (an access past it reads zeros and touches no memory).
+constexpr int kRsrcWord3 = 0x00020000;
+// `records` bytes from byte address `base`, in the form the inline-assembly DMA below takes
+__device__ __forceinline__ i32x4 dma_rsrc(unsigned long base, int records) {
+  return i32x4{static_cast<int>(base), static_cast<int>(base >> 32) & 0xFFFF, records, kRsrcWord3};
+}
+// the same for __builtin_amdgcn_raw_buffer_load_*
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t buffer_rsrc(const void* base, int records) {
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, records, kRsrcWord3);
+}
+
+// One LDS-DMA piece: 64 lanes x 16 bytes from the buffer `rsrc` at voff + soff into LDS at lds_addr + 16 lane.  Inline assembly on
+// purpose: hipcc orders every later LDS read behind a DMA it knows about (s_waitcnt vmcnt(0) in front of the fragment reads at a
+// loop header, whatever object they read), which serialises the ring.  Here the compiler sees neither the LDS write nor the
+// vmcnt event; the kernel places its own counted waits.  (Its counted waits for ordinary loads stay safe: vmcnt retires in
+// order, so DMAs it does not know about only make such a wait stricter.)
+__device__ __forceinline__ void dma_piece(unsigned lds_addr, unsigned voff, i32x4 rsrc, unsigned soff) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
+               :
+               : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff)
+               : "memory", "m0");
+}
+// soff = 0 as an inline constant (no scalar register for it)
+__device__ __forceinline__ void dma_piece(unsigned lds_addr, unsigned voff, i32x4 rsrc) {
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" : : "s"(lds_addr), "v"(voff), "s"(rsrc) : "memory", "m0");
+}
+
+// Counted waits: at most VM vector-memory operations (DMA pieces included) and LGKM LDS / scalar-memory operations of this
+// wavefront still outstanding.  gfx950's s_waitcnt holds vmcnt in 6 bits and lgkmcnt in 4.
+template <int VM>
+__device__ __forceinline__ void wait_vmcnt() {
+  static_assert(VM >= 0 && VM < 64, "vmcnt: 6 bits");
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(VM) : "memory");
+}
+template <int VM, int LGKM>
+__device__ __forceinline__ void wait_vm_lgkm() {
+  static_assert(VM >= 0 && VM < 64, "vmcnt: 6 bits");
+  static_assert(LGKM >= 0 && LGKM < 16, "lgkmcnt: 4 bits");
+  asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(%1)" ::"n"(VM), "n"(LGKM) : "memory");
+}
+
+// Workgroups are dealt round-robin over the 8 XCDs, each with its own L2.  xcd_contiguous<I>(nwg): the virtual index of workgroup
+// b = blockIdx.x among the first nwg -- the (b / 8)-th item of the contiguous run of the virtual order that belongs to XCD b % 8 -- so
+// that neighbouring items (tiles that share operand rows, patches that share halo rows) are read through one L2.  A bijection of
+// [0, nwg) for any nwg.  I: the index arithmetic, int or unsigned, as the kernel had it (signed and unsigned shifts and compares
+// are different instructions).
+template <typename I>
+__device__ __forceinline__ I xcd_contiguous(unsigned nwg) {
+  const I n = nwg, b = blockIdx.x;
+  const I xcd = b & 7, slot = b >> 3;
+  const I q = n >> 3, r = n & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+}
+
+// a wave-uniform value -> a scalar register
+__device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+__device__ __forceinline__ float uniform_f(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
+}
+
 }  // namespace diffsal

@@ -27,22 +27,6 @@
 
 namespace diffsal {
 
-typedef float cd_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 cd_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 cd_f16x8 __attribute__((ext_vector_type(8)));
-typedef int cd_i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* cd_lds_ptr_t;
-
-template <typename T> struct CdMma;
-template <> struct CdMma<__bf16> {
-  typedef cd_bf16x8 vec;
-  static __device__ __forceinline__ cd_f32x16 run(vec a, vec b, cd_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct CdMma<_Float16> {
-  typedef cd_f16x8 vec;
-  static __device__ __forceinline__ cd_f32x16 run(vec a, vec b, cd_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
 template <typename T>
 struct CdArgs {
   const T* in;
@@ -57,18 +41,6 @@ struct CdArgs {
   int dil, pad, act, rowvec_ld;
   int tiles_x, tiles_y, tiles_n;
 };
-
-// inline assembly on purpose (see gemm_dma.hip): the compiler must know neither the LDS write nor the vmcnt event
-__device__ __forceinline__ void cd_dma(unsigned lds_addr, unsigned voff, cd_i32x4 rsrc, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff)
-               : "memory", "m0");
-}
-template <int N>
-__device__ __forceinline__ void cd_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 constexpr int kCdWaves = 4;
 constexpr int kCdRowB = 64;                     // bytes per staged pixel / weight row (one 32-channel chunk)
@@ -102,7 +74,7 @@ template <int WN> struct CdShape {
 // what is idle is the other CUs, so the tiles are halved and twice as many CUs work.
 template <int TW, int WN, typename T, bool HALF = false>
 __global__ __launch_bounds__(256, 2) void conv16_dma_kernel(CdArgs<T> p) {
-  typedef typename CdMma<T>::vec vec;
+  typedef typename Mfma32x16<T>::vec vec;
   typedef CdShape<WN> S;
   static_assert(!HALF || (WN == 1 && TW != 0), "half tiles: 128 pixels x 96 channels");
   constexpr int TM = HALF ? 1 : S::TM, TN = 3, BN = S::BN;
@@ -115,13 +87,8 @@ __global__ __launch_bounds__(256, 2) void conv16_dma_kernel(CdArgs<T> p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char cd_smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int b;
-  {  // XCD-aware order: an XCD takes a contiguous run of tiles (neighbouring patches share halo rows, N tiles share the patch)
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  // XCD-aware order: an XCD takes a contiguous run of tiles (neighbouring patches share halo rows, N tiles share the patch)
+  int b = xcd_contiguous<int>(gridDim.x);
   const int tn = b % p.tiles_n; b /= p.tiles_n;
   const int tx = b % p.tiles_x; b /= p.tiles_x;
   const int ty = b % p.tiles_y;
@@ -133,7 +100,7 @@ __global__ __launch_bounds__(256, 2) void conv16_dma_kernel(CdArgs<T> p) {
   const int PP = PH * PW, OP = p.Ho * p.Wo;        // MI: pixels of a padded image / of an output map
   const int patch_bytes = (MI ? 2 : 1) * PP * kCdRowB;       // <= 27648
   // LDS: [patch 0][patch 1][weight slot 0..2][scratch KiB]
-  const unsigned lds0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>((cd_lds_ptr_t)cd_smem));
+  const unsigned lds0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_ptr_t)cd_smem));
   constexpr int PATCH_CAP = S::PATCH_CAP;
   constexpr int SLOT_B = S::SLOT_B;
   // dead DMA instructions write zeros into the last KiB of patch buffer 0, which no patch reaches (host-checked)
@@ -147,9 +114,9 @@ __global__ __launch_bounds__(256, 2) void conv16_dma_kernel(CdArgs<T> p) {
   const T* in_img = p.in + static_cast<long>(img) * p.H * p.W * p.Cin;
   const unsigned long pa = reinterpret_cast<unsigned long>(in_img);
   const int a_records = __builtin_amdgcn_readfirstlane((MI && img + 1 < p.N ? 2 : 1) * p.H * p.W * p.Cin * 2);
-  const cd_i32x4 rs_a = cd_i32x4{static_cast<int>(pa), static_cast<int>(pa >> 32) & 0xFFFF, a_records, 0x00020000};
+  const i32x4 rs_a = dma_rsrc(pa, a_records);
   const unsigned long pw = reinterpret_cast<unsigned long>(p.w);
-  const cd_i32x4 rs_w = cd_i32x4{static_cast<int>(pw), static_cast<int>(pw >> 32) & 0xFFFF, p.Cout * p.K * 2, 0x00020000};
+  const i32x4 rs_w = dma_rsrc(pw, p.Cout * p.K * 2);
   unsigned a_voff[kCdPatchIss], w_voff[S::W_ISS];
 #pragma unroll
   for (int q = 0; q < kCdPatchIss; ++q) {
@@ -171,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void conv16_dma_kernel(CdArgs<T> p) {
   auto issue_patch = [&](int c, int q) __attribute__((always_inline)) {
     const unsigned dst = lds0 + (c & 1) * PATCH_CAP + (q * kCdWaves + wave) * 1024;
     const bool live = c < n_chunks && (q * kCdWaves + wave) * 1024 < patch_bytes + 1024 && (q * kCdWaves + wave) * 1024 < PATCH_CAP;
-    cd_dma(live ? dst : lds_scratch, live ? a_voff[q] : DEAD, rs_a, static_cast<unsigned>(c) * 64u);
+    dma_piece(live ? dst : lds_scratch, live ? a_voff[q] : DEAD, rs_a, static_cast<unsigned>(c) * 64u);
   };
   auto issue_weights = [&](int g) __attribute__((always_inline)) {       // the slice of step g (chunk g / 9, tap g % 9) -> slot g % SLOTS
     const bool live = g < G;
@@ -180,7 +147,7 @@ __global__ __launch_bounds__(256, 2) void conv16_dma_kernel(CdArgs<T> p) {
 #pragma unroll
     for (int q = 0; q < S::W_ISS; ++q) {
       const bool in_tile = (q * kCdWaves + wave) * 16 < BN;    // 96 rows: the second instruction of wavefronts 2, 3 has none (scratch)
-      cd_dma(live && in_tile ? dst + (q * kCdWaves + wave) * 1024 : lds_scratch, live && in_tile ? w_voff[q] : DEAD, rs_w, soff);
+      dma_piece(live && in_tile ? dst + (q * kCdWaves + wave) * 1024 : lds_scratch, live && in_tile ? w_voff[q] : DEAD, rs_w, soff);
     }
   };
 
@@ -211,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void conv16_dma_kernel(CdArgs<T> p) {
   issue_weights(0);
   issue_weights(1);
 
-  cd_f32x16 acc[TM][TN];
+  f32x16 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -224,27 +191,25 @@ __global__ __launch_bounds__(256, 2) void conv16_dma_kernel(CdArgs<T> p) {
     const unsigned char* Ab = cd_smem + (chunk & 1) * PATCH_CAP;
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap, ++g) {
-      // everything this wavefront issued up to step g - 2 has landed (first step: all but weight slice 1); after the barrier
-      // everybody's has.  What is issued now lands in buffers last read TWO steps ago -- weight slot (g + 2) % 4, and the other patch
+      // vmcnt: a wavefront issues VM = W_ISS + 1 DMA instructions per step (its weight rows and one patch piece, live or dead), so
+      // with VM left outstanding everything it issued up to step g - 2 has landed (first step: W_ISS, all but weight slice 1); after
+      // the barrier everybody's has.
+      // lgkmcnt, WN = 1: what is issued now lands in buffers last read TWO steps ago -- weight slot (g + 2) % 4, and the other patch
       // buffer from tap 1 on -- so that a fragment read of step g - 1 that is still queued in a busy LDS (hipcc sinks that step's
       // last MFMAs and their lgkmcnt waits below this barrier) cannot meet a DMA: with a three-slot ring and lookahead 2 that
-      // happened -- rare wrong tiles with every CU loaded -- and the cure there, lgkmcnt(0) in front of the barrier, cost 5 %
-      // lgkmcnt(10): at most the ten fragment reads of step g - 1 are still on their way -- those of step g - 2, whose buffers the DMAs
-      // below overwrite, have returned whatever the compiler did with that step's MFMAs (LDS operations return in order)
-      if constexpr (WN == 1) {
-        if (g == 0) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(3) lgkmcnt(10)" ::: "memory");
-      } else {
-        // three weight slots: what is issued below lands in the slot read in step g - 1, so every fragment read of that step has to
-        // have returned before the barrier (lgkmcnt(0)); four DMA instructions per wavefront and step (three weight rows, one patch)
-        if (g == 0) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
-      }
+      // happened -- rare wrong tiles with every CU loaded -- and the cure there, lgkmcnt(0) in front of the barrier, cost 5 %.  A step
+      // issues 2 (TM + TN) fragment reads; with that many left outstanding, those of step g - 2, whose buffers the DMAs below
+      // overwrite, have returned whatever the compiler did with that step's MFMAs (LDS operations return in order).
+      // lgkmcnt, WN = 2: three weight slots -- what is issued below lands in the slot read in step g - 1, so every fragment read of
+      // that step has to have returned before the barrier (0).
+      constexpr int VM = S::W_ISS + 1, LGKM = WN == 1 ? 2 * (TM + TN) : 0;
+      if (g == 0) wait_vmcnt<S::W_ISS>();
+      else wait_vm_lgkm<VM, LGKM>();
       __builtin_amdgcn_s_barrier();
       issue_weights(g + 2);
       constexpr int P0 = WN == 1 ? 1 : 0;          // first tap that refills the other patch buffer (WN = 1: reuse distance of two steps)
       if (tap >= P0 && tap < P0 + kCdPatchIss) issue_patch(chunk + 1, tap - P0);
-      else cd_dma(lds_scratch, DEAD, rs_a, 0u);
+      else dma_piece(lds_scratch, DEAD, rs_a, 0u);
       const unsigned char* Bb = cd_smem + 2 * PATCH_CAP + (g % S::SLOTS) * SLOT_B;
       const int ky = tap / 3, kx = tap - ky * 3;
       const int toff = ky * d * PW + kx * d;
@@ -270,7 +235,7 @@ __global__ __launch_bounds__(256, 2) void conv16_dma_kernel(CdArgs<T> p) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
-          for (int j = 0; j < TN; ++j) acc[i][j] = CdMma<T>::run(fb[kk][j], fa[kk][i], acc[i][j]);   // D^T: rows = channels, cols = pixels
+          for (int j = 0; j < TN; ++j) acc[i][j] = Mfma32x16<T>::run(fb[kk][j], fa[kk][i], acc[i][j]);   // D^T: rows = channels, cols = pixels
     }
   }
   // every DMA (the dead ones of the last steps included) has landed before the LDS is reused

@@ -23,20 +23,6 @@
 
 namespace diffsal {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 hbf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 hf16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T> struct HaloMma;
-template <> struct HaloMma<__bf16> {
-  typedef hbf16x8 vec;
-  static __device__ __forceinline__ f32x16 run(vec a, vec b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct HaloMma<_Float16> {
-  typedef hf16x8 vec;
-  static __device__ __forceinline__ f32x16 run(vec a, vec b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
 template <typename T>
 struct HaloArgs {
   const T* in;
@@ -69,7 +55,7 @@ constexpr int HP = 40;   // elements per staged pixel / weight row: 32 data + 8 
 // park, then runs the step's MFMAs; one barrier per step.  No phase without matrix work, 20 staging VGPRs.
 template <int TW, int NW, int TN, typename T>
 __global__ __launch_bounds__(NW * 64) void conv16_halo_kernel(HaloArgs<T> p) {
-  typedef typename HaloMma<T>::vec vec;
+  typedef typename Mfma32x16<T>::vec vec;
   constexpr int TH = 16;
   constexpr int NT = NW * 64;
   constexpr int RPM = 32 / TW;                     // image rows per 32-pixel MFMA tile
@@ -87,14 +73,8 @@ __global__ __launch_bounds__(NW * 64) void conv16_halo_kernel(HaloArgs<T> p) {
 #endif
   stamp(0);
   // block -> (image, tile_y, tile_x, n tile); consecutive blocks share the patch's neighbourhood and the same weights
-  int b;
-  {  // XCD-aware order (see igemm.hip): workgroups are dealt round-robin over the 8 XCDs, so give each XCD a contiguous run of
-     // tiles -- neighbouring patches share their halo rows and the N tiles of a patch share all of it, in ONE L2
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  // XCD-aware order: neighbouring patches share their halo rows and the N tiles of a patch share all of it, in ONE L2
+  int b = xcd_contiguous<int>(gridDim.x);
   const int tn = b % p.tiles_n; b /= p.tiles_n;
   const int tx = b % p.tiles_x; b /= p.tiles_x;
   const int ty = b % p.tiles_y;
@@ -115,10 +95,8 @@ __global__ __launch_bounds__(NW * 64) void conv16_halo_kernel(HaloArgs<T> p) {
   constexpr int B_PER = (3 * BN * 4 + NT - 1) / NT;
   constexpr unsigned DEAD = 0x80000000u;
   const T* in_img = p.in + static_cast<long>(img) * p.H * p.W * p.Cin;
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(in_img), 0, p.H * p.W * p.Cin * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(p.w), 0, p.Cout * p.K * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_a = buffer_rsrc(in_img, p.H * p.W * p.Cin * 2);
+  const __amdgpu_buffer_rsrc_t rsrc_b = buffer_rsrc(p.w, p.Cout * p.K * 2);
   unsigned a_voff[3 * A_STEP], b_voff[B_PER];
   int b_dst[B_PER];
   const int a_pieces = PH * PW * 4;
@@ -233,7 +211,7 @@ __global__ __launch_bounds__(NW * 64) void conv16_halo_kernel(HaloArgs<T> p) {
 #pragma unroll
           for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int j = 0; j < TN; ++j) acc[i][j] = HaloMma<T>::run(fb[j], fa[i], acc[i][j]);   // D^T: rows = channels, cols = pixels
+            for (int j = 0; j < TN; ++j) acc[i][j] = Mfma32x16<T>::run(fb[j], fa[i], acc[i][j]);   // D^T: rows = channels, cols = pixels
         }
       }
       __syncthreads();

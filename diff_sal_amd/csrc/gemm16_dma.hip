@@ -19,22 +19,6 @@
 
 namespace diffsal {
 
-typedef float gd_f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 gd_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 gd_f16x8 __attribute__((ext_vector_type(8)));
-typedef int gd_i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* gd_lds_ptr_t;
-
-template <typename T> struct GdMma;
-template <> struct GdMma<__bf16> {
-  typedef gd_bf16x8 vec;
-  static __device__ __forceinline__ gd_f32x16 run(vec a, vec b, gd_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct GdMma<_Float16> {
-  typedef gd_f16x8 vec;
-  static __device__ __forceinline__ gd_f32x16 run(vec a, vec b, gd_f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-
 template <typename T>
 struct GdArgs {
   const T* a;
@@ -54,48 +38,31 @@ struct GdArgs {
   int taps, Wrow, Hrow, Cin;
 };
 
-// inline assembly on purpose (see gemm_dma.hip): the compiler must know neither the LDS write nor the vmcnt event
-__device__ __forceinline__ void gd_dma(unsigned lds_addr, unsigned voff, gd_i32x4 rsrc, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff)
-               : "memory", "m0");
-}
-template <int N>
-__device__ __forceinline__ void gd_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-
 // Two tile shapes, four wavefronts each, a wavefront = TM x 3 accumulators of 32 x 32:
 //   <2, 1>  256 x 96: the wavefronts stacked along M (64 rows x 96 columns each);
 //   <3, 2>  192 x 192: the wavefronts 2 x 2 (96 x 96 each).  Per MFMA a wavefront reads (1 / TM + 1 / 3) KiB of fragments from LDS:
 //           0.83 against 0.67 -- at one MFMA per 8 cycles and CU that is 81 % of the LDS's 128 bytes per cycle against 65 %, before the
 //           DMA's own LDS writes -- and a tile's L2 -> LDS bytes per flop are 1 / 256 + 1 / 96 against 2 / 192 (-27 %).
-// A ring slot holds BM rows of A and BN rows of W, one 32-element K chunk (64 bytes) each; (BM + BN) / 16 <= 24 DMA instructions per step,
-// six per wavefront in both shapes.
+// A ring slot holds BM rows of A and BN rows of W, one 32-element K chunk (64 bytes) each; (BM + BN) / 16 DMA instructions per step, shared
+// out over the four wavefronts: six per wavefront in both shapes.
 template <typename T, int TM, int WN>
 __global__ __launch_bounds__(256, 2) void gemm16_dma2_kernel(GdArgs<T> p) {
-  typedef typename GdMma<T>::vec vec;
+  typedef typename Mfma32x16<T>::vec vec;
   constexpr int TN = 3, WM = 4 / WN, BM = WM * TM * 32, BN = WN * 96;
   constexpr int kGdSlot = (BM + BN) * 64;
+  constexpr int ISS = ((BM + BN) / 16 + 3) / 4;   // DMA instructions per wavefront and step (256 x 96: the last one of waves 2, 3 is dead)
   constexpr int NA = BM / 64;                     // DMA instruction q of a wavefront: q < NA rows of A, else rows of W
-  static_assert(BM % 64 == 0 && (BM + BN) / 16 <= 24, "six DMA instructions per wavefront and step");
+  static_assert(BM % 64 == 0 && ISS <= 6, "at most six DMA instructions per wavefront and step");
   constexpr unsigned DEAD = 0x80000000u;
   extern __shared__ __attribute__((aligned(16))) unsigned char gd_smem[];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  int b;
-  {  // XCD-aware order: an XCD takes a contiguous run of tiles; N tiles of one row block are neighbours (they share the A rows)
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int xcd = bid & 7, slot = bid >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    b = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
+  // XCD-aware order: an XCD takes a contiguous run of tiles; N tiles of one row block are neighbours (they share the A rows)
+  const int b = xcd_contiguous<int>(gridDim.x);
   const int tn = b % p.tiles_n, tm = b / p.tiles_n;
   const int m0 = tm * BM, n0 = tn * BN;
   const int wm = wave / WN, wn = wave - wm * WN;
-  const unsigned lds0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>((gd_lds_ptr_t)gd_smem));
+  const unsigned lds0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_ptr_t)gd_smem));
   const unsigned lds_scratch = lds0 + 3 * kGdSlot;
   const int G = p.K >> 5;
 
@@ -111,17 +78,17 @@ __global__ __launch_bounds__(256, 2) void gemm16_dma2_kernel(GdArgs<T> p) {
   const unsigned long pa = reinterpret_cast<unsigned long>(p.a) + static_cast<unsigned long>(base_off);
   const int rows_a = min(BM, p.M - m0), rows_w = min(BN, p.N - n0);
   const long rec_a = total_b - base_off;
-  const gd_i32x4 rs_a = gd_i32x4{static_cast<int>(pa), static_cast<int>(pa >> 32) & 0xFFFF, static_cast<int>(rec_a < 0x7FFFFFFFL ? rec_a : 0x7FFFFFFFL), 0x00020000};
+  const i32x4 rs_a = dma_rsrc(pa, static_cast<int>(rec_a < 0x7FFFFFFFL ? rec_a : 0x7FFFFFFFL));
   const unsigned long pw = reinterpret_cast<unsigned long>(p.w + static_cast<long>(n0) * p.K);
-  const gd_i32x4 rs_w = gd_i32x4{static_cast<int>(pw), static_cast<int>(pw >> 32) & 0xFFFF, rows_w * p.K * 2, 0x00020000};
-  unsigned a_voff[NA], w_voff[6 - NA];
+  const i32x4 rs_w = dma_rsrc(pw, rows_w * p.K * 2);
+  unsigned a_voff[NA], w_voff[ISS - NA];
 #pragma unroll
   for (int q = 0; q < NA; ++q) {
     const int row = (q * 4 + wave) * 16 + (lane >> 2), ls = (lane & 3) ^ ((row >> 2) & 3);
     a_voff[q] = row < rows_a ? static_cast<unsigned>(row_off(m0 + row) - base_off + ls * 16) : DEAD;
   }
 #pragma unroll
-  for (int q = 0; q < 6 - NA; ++q) {
+  for (int q = 0; q < ISS - NA; ++q) {
     const int row = (q * 4 + wave) * 16 + (lane >> 2), ls = (lane & 3) ^ ((row >> 2) & 3);
     w_voff[q] = row < rows_w ? static_cast<unsigned>((row * p.K + ls * 8) * 2) : DEAD;     // rows past BN (256 x 96: q = 1, waves 2, 3): past rows_w
   }
@@ -132,11 +99,11 @@ __global__ __launch_bounds__(256, 2) void gemm16_dma2_kernel(GdArgs<T> p) {
     const int ch = g / p.taps, tap = g - ch * p.taps;
     const unsigned soff_a = static_cast<unsigned>(tap) * tap_stride + static_cast<unsigned>(ch) * 64u;
 #pragma unroll
-    for (int q = 0; q < NA; ++q) gd_dma(live ? dst + (q * 4 + wave) * 1024 : lds_scratch, live ? a_voff[q] : DEAD, rs_a, soff_a);
+    for (int q = 0; q < NA; ++q) dma_piece(live ? dst + (q * 4 + wave) * 1024 : lds_scratch, live ? a_voff[q] : DEAD, rs_a, soff_a);
 #pragma unroll
-    for (int q = 0; q < 6 - NA; ++q) {
+    for (int q = 0; q < ISS - NA; ++q) {
       const bool in_tile = (q * 4 + wave) * 16 < BN;      // 256 x 96: the second W instruction of wavefronts 2, 3 has no rows
-      gd_dma(live && in_tile ? dst + BM * 64 + (q * 4 + wave) * 1024 : lds_scratch, live && in_tile ? w_voff[q] : DEAD, rs_w, soff);
+      dma_piece(live && in_tile ? dst + BM * 64 + (q * 4 + wave) * 1024 : lds_scratch, live && in_tile ? w_voff[q] : DEAD, rs_w, soff);
     }
   };
 
@@ -158,7 +125,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_dma2_kernel(GdArgs<T> p) {
 
   issue(0);
   issue(1);
-  gd_f32x16 acc[TM][TN];
+  f32x16 acc[TM][TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -167,9 +134,9 @@ __global__ __launch_bounds__(256, 2) void gemm16_dma2_kernel(GdArgs<T> p) {
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
   for (int g = 0; g < G; ++g) {
-    // this wavefront's pieces of chunk g have landed (the six of chunk g + 1 may be in flight) and its LDS reads of step g - 1 have
+    // this wavefront's pieces of chunk g have landed (the ISS of chunk g + 1 may be in flight) and its LDS reads of step g - 1 have
     // returned (see conv16_dma.hip); after the barrier everybody's have, and slot (g + 2) % 3 is free
-    asm volatile("s_waitcnt vmcnt(6) lgkmcnt(0)" ::: "memory");
+    wait_vm_lgkm<ISS, 0>();
     __builtin_amdgcn_s_barrier();
     issue(g + 2);
     const unsigned char* S = gd_smem + (g % 3) * kGdSlot;
@@ -186,7 +153,7 @@ __global__ __launch_bounds__(256, 2) void gemm16_dma2_kernel(GdArgs<T> p) {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int j = 0; j < TN; ++j) acc[i][j] = GdMma<T>::run(fb[kk][j], fa[kk][i], acc[i][j]);   // D^T: rows = columns of out, cols = rows of out
+        for (int j = 0; j < TN; ++j) acc[i][j] = Mfma32x16<T>::run(fb[kk][j], fa[kk][i], acc[i][j]);   // D^T: rows = columns of out, cols = rows of out
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();

@@ -34,9 +34,6 @@
 
 namespace diffsal {
 
-typedef float f32x4v __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
 struct DmaGemmArgs {
   const void* a;          // storage type T of the launch (float, bf16, f16): activations, weights, residual, output
   const void* w;
@@ -79,34 +76,14 @@ static unsigned long long* g_dma_stamps = nullptr;
 static size_t g_dma_stamp_bytes = 0;
 #endif
 
-// One LDS-DMA piece: 64 lanes x 16 bytes from the buffer `rsrc` at voff + soff into LDS at lds_addr + 16 lane.  Inline assembly on
-// purpose: hipcc orders every later LDS read behind a DMA it knows about (s_waitcnt vmcnt(0) in front of the fragment reads at a
-// loop header, whatever object they read), which serialises the ring.  Here the compiler sees neither the LDS write nor the
-// vmcnt event; the kernel places its own counted waits.  (Its counted waits for ordinary loads stay safe: vmcnt retires in
-// order, so DMAs it does not know about only make such a wait stricter.)
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void dma_piece(unsigned lds_addr, unsigned voff, i32x4 rsrc, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff)
-               : "memory", "m0");
-}
-
-typedef __bf16 dma_bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 dma_f16x8 __attribute__((ext_vector_type(8)));
 // one 16 x 16 x 32 product of two 16-byte fragments (8 elements of k per lane), fp32 accumulation
-__device__ __forceinline__ f32x4v mma16(const float4& a, const float4& b, f32x4v c, const bf16_t*) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(dma_bf16x8, a), __builtin_bit_cast(dma_bf16x8, b), c, 0, 0, 0);
+__device__ __forceinline__ f32x4_t mma16(const float4& a, const float4& b, f32x4_t c, const bf16_t*) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, a), __builtin_bit_cast(bf16x8_t, b), c, 0, 0, 0);
 }
-__device__ __forceinline__ f32x4v mma16(const float4& a, const float4& b, f32x4v c, const f16_t*) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(dma_f16x8, a), __builtin_bit_cast(dma_f16x8, b), c, 0, 0, 0);
+__device__ __forceinline__ f32x4_t mma16(const float4& a, const float4& b, f32x4_t c, const f16_t*) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
 }
-__device__ __forceinline__ f32x4v mma16(const float4&, const float4&, f32x4v c, const float*) { return c; }   // never called
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
+__device__ __forceinline__ f32x4_t mma16(const float4&, const float4&, f32x4_t c, const float*) { return c; }   // never called
 
 // Grouped launch: up to four independent problems (own operands, shapes, K splits) share ONE persistent grid; unit v of the
 // launch belongs to problem idx = #(unit_end[j] <= v).  The host orders the problems by decreasing K slices per unit, so the
@@ -260,16 +237,16 @@ __global__ __launch_bounds__(256, OCC) void gemm_dma_kernel(std::conditional_t<G
     const int m0 = tmi * BM, n0 = tni * BN;
     const int rows_b = live ? min(BN, pi.N - n0) : 0;
     const unsigned long pb = reinterpret_cast<unsigned long>(static_cast<const T*>(base_w) + ib_w + static_cast<long>(n0) * K);
-    rs_b = i32x4{static_cast<int>(pb), static_cast<int>(pb >> 32) & 0xFFFF, rows_b * K * ESZ, 0x00020000};
+    rs_b = dma_rsrc(pb, rows_b * K * ESZ);
     const int kt0 = split_of(pi, iss_lv) * pi.kt_per_unit;
     iss_kofs = static_cast<unsigned>(kt0) * 128u;
     if constexpr (!CONV) {
       const int rows_a = live ? min(BM, pi.M - m0) : 0;
       const unsigned long pa = reinterpret_cast<unsigned long>(static_cast<const T*>(base_a) + ib_a + static_cast<long>(m0) * K);
-      rs_a = i32x4{static_cast<int>(pa), static_cast<int>(pa >> 32) & 0xFFFF, rows_a * K * ESZ, 0x00020000};
+      rs_a = dma_rsrc(pa, rows_a * K * ESZ);
     } else {
       const unsigned long pa = reinterpret_cast<unsigned long>(pi.a);
-      rs_a = i32x4{static_cast<int>(pa), static_cast<int>(pa >> 32) & 0xFFFF, static_cast<int>(live ? pi.in_bytes : 0u), 0x00020000};
+      rs_a = dma_rsrc(pa, static_cast<int>(live ? pi.in_bytes : 0u));
       iss_chunk = kt0 / pi.taps;
       iss_tap = kt0 - iss_chunk * pi.taps;
       iss_ky = iss_tap / pi.KW;
@@ -351,11 +328,11 @@ __global__ __launch_bounds__(256, OCC) void gemm_dma_kernel(std::conditional_t<G
 #pragma unroll
     for (int h = 0; h < 2; ++h) b_off[j][h] = BM * 32 + row * 32 + (((q4 + 4 * h) ^ ((row >> 1) & 7)) << 2);
   }
-  f32x4v acc[TMB][TNB];
+  f32x4_t acc[TMB][TNB];
 #pragma unroll
   for (int i = 0; i < TMB; ++i)
 #pragma unroll
-    for (int j = 0; j < TNB; ++j) acc[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < TNB; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   float4 fa[2][TMB], fb[2][TNB];
   auto load_frag = [&](const float* st, int h, int set, int f) __attribute__((always_inline)) {   // f < TMB: A block f, else W block
@@ -442,7 +419,7 @@ __global__ __launch_bounds__(256, OCC) void gemm_dma_kernel(std::conditional_t<G
       for (int i = 0; i < TMB; ++i) {
         const int m = mb + i * 16;
         float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-        acc[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
+        acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         if (pc.bias) { v[0] += qb.x; v[1] += qb.y; v[2] += qb.z; v[3] += qb.w; }
         if (pc.scale) {
           v[0] = v[0] * qs.x + qh.x; v[1] = v[1] * qs.y + qh.y;
@@ -495,7 +472,7 @@ __global__ __launch_bounds__(256, OCC) void gemm_dma_kernel(std::conditional_t<G
 #pragma unroll
       for (int i = 0; i < TMB; ++i) {
         const float4 v = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-        acc[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
+        acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         if (mb + i * 16 < pc.M && nb + j * 16 < pc.N) st4(ob + (static_cast<long>(i) * 16 * pc.N + j * 16), v);
       }
   };
@@ -526,7 +503,7 @@ __global__ __launch_bounds__(256, OCC) void gemm_dma_kernel(std::conditional_t<G
 #pragma unroll
       for (int i = 0; i < TMB; ++i) {
         const float4 v = make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
-        acc[i][j] = f32x4v{0.f, 0.f, 0.f, 0.f};
+        acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
         if (mb + i * 16 < pc.M && nb + j * 16 < pc.N) st4(ob + (static_cast<long>(i) * 16 * pc.N + j * 16), v);
       }
   };

@@ -48,8 +48,6 @@ int try_gemm16_dma2(const diffsal_conv_desc* d, const void* a, const void* w, co
                     const float* rowvec, int rowvec_ld, const void* residual, void* out, hipStream_t s, bool out_f32);
 double gemm_dma_estimate(int cfg, long M, int K, int N);
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 struct IgemmArgs {
   const float* in;
   const float* w;
@@ -88,8 +86,6 @@ __device__ __forceinline__ void select_pair(IgemmArgs& p, int which) {
 
 typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BK = 32;
 constexpr int PITCH = BK + 4;  // dwords; 36*r mod 64 hits 16 distinct 4-bank slots for 16 rows
@@ -126,17 +122,9 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs p) {
   const int wm = wave / WN;
   const int wn = wave % WN;
 
-  // XCD-aware tile order: workgroups are dealt round-robin over the 8 XCDs, so give each XCD a
-  // contiguous run of tiles (same-M tiles share their A rows in one L2).  Bijective for any count.
-  int tile;
+  // XCD-aware tile order: same-M tiles share their A rows in one L2
+  const int tile = xcd_contiguous<int>(p.n_tiles);
   const int split = blockIdx.y;
-  {
-    const int nwg = p.n_tiles;
-    const int b = blockIdx.x;
-    const int xcd = b & 7, slot = b >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
   const int tile_m = tile / p.n_tiles_n;
   const int tile_n = tile - tile_m * p.n_tiles_n;
   const int m0 = tile_m * BM;
@@ -151,10 +139,8 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs p) {
   const int lcol = (tid & 7) * 4;
   const int lrow_a = PREC == 1 ? tid >> 2 : lrow;
   const int lcol_a = PREC == 1 ? (tid & 3) * 8 : lcol;
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(p.in), 0, static_cast<int>(p.in_bytes), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(p.w), 0, static_cast<int>(p.w_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_a = buffer_rsrc(p.in, static_cast<int>(p.in_bytes));
+  const __amdgpu_buffer_rsrc_t rsrc_b = buffer_rsrc(p.w, static_cast<int>(p.w_bytes));
 
   unsigned a_voff[A_PASSES];   // byte offset of (n, iy0, ix0, lcol); wraps for negative iy0/ix0, only used when valid
   unsigned a_valid[A_PASSES];  // bit t: tap t of this row lies inside the image
@@ -360,19 +346,19 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs p) {
   } else {
     // bf16x3: a K slice is two 16-wide MFMA steps; lane half h owns k = g*16 + h*8 .. +7 of step g (A and B agree, so
     // the k order inside a step is free): one ds_read_b128 of hi halves and one of lo halves per 32-row tile and step.
-    bf16x8 ah[2][TM], al[2][TM], bh[2][TN], bl[2][TN];
+    bf16x8_t ah[2][TM], al[2][TM], bh[2][TN], bl[2][TN];
     const int a_frag3 = (wm * TM * 32 + frow) * PITCH + (lane >> 5) * 4;
     const int b_frag3 = (BM + wn * TN * 32 + frow) * PITCH + (lane >> 5) * 4;
     auto load_frags3 = [&](const float* stage, int g, int set) {
 #pragma unroll
       for (int i = 0; i < TM; ++i) {
-        ah[set][i] = __builtin_bit_cast(bf16x8, ld4(stage + a_frag3 + i * 32 * PITCH + g * 8));
-        al[set][i] = __builtin_bit_cast(bf16x8, ld4(stage + a_frag3 + i * 32 * PITCH + 16 + g * 8));
+        ah[set][i] = __builtin_bit_cast(bf16x8_t, ld4(stage + a_frag3 + i * 32 * PITCH + g * 8));
+        al[set][i] = __builtin_bit_cast(bf16x8_t, ld4(stage + a_frag3 + i * 32 * PITCH + 16 + g * 8));
       }
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
-        bh[set][j] = __builtin_bit_cast(bf16x8, ld4(stage + b_frag3 + j * 32 * PITCH + g * 8));
-        bl[set][j] = __builtin_bit_cast(bf16x8, ld4(stage + b_frag3 + j * 32 * PITCH + 16 + g * 8));
+        bh[set][j] = __builtin_bit_cast(bf16x8_t, ld4(stage + b_frag3 + j * 32 * PITCH + g * 8));
+        bl[set][j] = __builtin_bit_cast(bf16x8_t, ld4(stage + b_frag3 + j * 32 * PITCH + 16 + g * 8));
       }
     };
     auto do_mfmas3 = [&](int set) {
@@ -380,9 +366,9 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs p) {
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) {   // small terms first
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bl[set][j], ah[set][i], acc[i][j], 0, 0, 0);   // D^T, as above
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[set][j], al[set][i], acc[i][j], 0, 0, 0);
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bh[set][j], ah[set][i], acc[i][j], 0, 0, 0);
+          acc[i][j] = Mfma32x16<__bf16>::run(bl[set][j], ah[set][i], acc[i][j]);   // D^T, as above
+          acc[i][j] = Mfma32x16<__bf16>::run(bh[set][j], al[set][i], acc[i][j]);
+          acc[i][j] = Mfma32x16<__bf16>::run(bh[set][j], ah[set][i], acc[i][j]);
         }
     };
     // The MFMA phase of a K slice is ~5x shorter than in fp32, so global loads are issued THREE slices ahead (two
@@ -574,8 +560,8 @@ __global__ __launch_bounds__(256, (TM * TN <= 4 ? 2 : 1)) void igemm_linear_kern
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   const int lrow = tid >> 3, lcol = (tid & 7) * 4;
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.in), 0, static_cast<int>(p.in_bytes), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.w), 0, static_cast<int>(p.w_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_a = buffer_rsrc(p.in, static_cast<int>(p.in_bytes));
+  const __amdgpu_buffer_rsrc_t rsrc_b = buffer_rsrc(p.w, static_cast<int>(p.w_bytes));
   unsigned a_rel[A_PASSES], b_rel[B_PASSES];
 #pragma unroll
   for (int j = 0; j < A_PASSES; ++j) a_rel[j] = static_cast<unsigned>((lrow + 32 * j) * p.K + lcol) * 4u;

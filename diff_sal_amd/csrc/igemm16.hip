@@ -19,24 +19,6 @@
 
 namespace diffsal {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T> struct Mma16;
-template <> struct Mma16<__bf16> {
-  typedef bf16x8 vec;
-  static __device__ __forceinline__ f32x16 run(vec a, vec b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-  }
-};
-template <> struct Mma16<_Float16> {
-  typedef f16x8 vec;
-  static __device__ __forceinline__ f32x16 run(vec a, vec b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0);
-  }
-};
-
 template <typename T>
 struct Igemm16Args {
   const T* in;
@@ -80,7 +62,7 @@ constexpr int PITCH16 = 36;         // dwords per LDS row (32 data + 4 pad)
 template <int WM, int WN, int TM, int TN, typename T>
 __global__ __launch_bounds__(256) void igemm16_kernel(Igemm16Args<T> p) {
   select_pair16(p, blockIdx.z);
-  typedef typename Mma16<T>::vec frag_t;
+  typedef typename Mfma32x16<T>::vec frag_t;
   constexpr int BM = WM * TM * 32;
   constexpr int BN = WN * TN * 32;
   constexpr int A_PASSES = BM / 32;
@@ -95,15 +77,8 @@ __global__ __launch_bounds__(256) void igemm16_kernel(Igemm16Args<T> p) {
   const int wm = wave / WN;
   const int wn = wave % WN;
 
-  int tile;
+  const int tile = xcd_contiguous<int>(p.n_tiles);   // XCD-aware order (see igemm.hip)
   const int split = blockIdx.y;
-  {  // XCD-aware order: each XCD owns a contiguous run of tiles (see igemm.hip)
-    const int nwg = p.n_tiles;
-    const int b = blockIdx.x;
-    const int xcd = b & 7, slot = b >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-  }
   const int tile_m = tile / p.n_tiles_n;
   const int tile_n = tile - tile_m * p.n_tiles_n;
   const int m0 = tile_m * BM;
@@ -114,10 +89,8 @@ __global__ __launch_bounds__(256) void igemm16_kernel(Igemm16Args<T> p) {
   const int l8 = tid & 7;
   const int lsub = l8 >> 2;
   const int lcol_dw = l8 * 4;  // dword column inside the LDS row
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(p.in), 0, static_cast<int>(p.in_bytes), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<T*>(p.w), 0, static_cast<int>(p.w_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_a = buffer_rsrc(p.in, static_cast<int>(p.in_bytes));
+  const __amdgpu_buffer_rsrc_t rsrc_b = buffer_rsrc(p.w, static_cast<int>(p.w_bytes));
 
   unsigned a_voff[A_PASSES];
   unsigned a_valid[A_PASSES];
@@ -221,7 +194,7 @@ __global__ __launch_bounds__(256) void igemm16_kernel(Igemm16Args<T> p) {
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j)
-        acc[i][j] = Mma16<T>::run(__builtin_bit_cast(frag_t, fb[set][j]), __builtin_bit_cast(frag_t, fa[set][i]), acc[i][j]);  // D^T
+        acc[i][j] = Mfma32x16<T>::run(__builtin_bit_cast(frag_t, fb[set][j]), __builtin_bit_cast(frag_t, fa[set][i]), acc[i][j]);  // D^T
   };
 
   // prologue: stages 0, 1, 2 in flight together; stage 0 is parked, 1 and 2 stay in the two register sets
@@ -356,7 +329,7 @@ __global__ __launch_bounds__(256) void igemm16_kernel(Igemm16Args<T> p) {
 // =================================================================================================================
 template <int WM, int WN, int TM, int TN, typename T>
 __global__ __launch_bounds__(256, (TM * TN <= 4 ? 2 : 1)) void igemm16_linear_kernel(Igemm16Args<T> p) {
-  typedef typename Mma16<T>::vec frag_t;
+  typedef typename Mfma32x16<T>::vec frag_t;
   constexpr int BM = WM * TM * 32;
   constexpr int BN = WN * TN * 32;
   constexpr int A_PASSES = BM / 32;
@@ -368,8 +341,8 @@ __global__ __launch_bounds__(256, (TM * TN <= 4 ? 2 : 1)) void igemm16_linear_ke
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WN, wn = wave % WN;
   const int lrow = tid >> 3, l8 = tid & 7, lsub = l8 >> 2, lcol_dw = l8 * 4;
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(p.in), 0, static_cast<int>(p.in_bytes), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_b = __builtin_amdgcn_make_buffer_rsrc(const_cast<T*>(p.w), 0, static_cast<int>(p.w_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_a = buffer_rsrc(p.in, static_cast<int>(p.in_bytes));
+  const __amdgpu_buffer_rsrc_t rsrc_b = buffer_rsrc(p.w, static_cast<int>(p.w_bytes));
   unsigned a_rel[A_PASSES], b_rel[B_PASSES];   // byte offsets of this thread's 16-byte piece relative to the tile origin
 #pragma unroll
   for (int j = 0; j < A_PASSES; ++j) a_rel[j] = static_cast<unsigned>((lrow + 32 * j) * p.K + l8 * 8) * 2u;
@@ -456,7 +429,7 @@ __global__ __launch_bounds__(256, (TM * TN <= 4 ? 2 : 1)) void igemm16_linear_ke
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j)
-        acc[i][j] = Mma16<T>::run(__builtin_bit_cast(frag_t, fb[set][j]), __builtin_bit_cast(frag_t, fa[set][i]), acc[i][j]);  // D^T
+        acc[i][j] = Mfma32x16<T>::run(__builtin_bit_cast(frag_t, fb[set][j]), __builtin_bit_cast(frag_t, fa[set][i]), acc[i][j]);  // D^T
   };
 
   // compute side: which tile the stages being multiplied belong to

@@ -11,7 +11,6 @@
 
 namespace diffsal {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct LinStreamArgs {
   const float* x;

@@ -304,9 +304,6 @@ struct ResizeSumArgs {
 // 4 (factor 2) source rows/columns, so the NR x NR source window is loaded ONCE and reused for all 16 outputs:
 // 2 loads per output instead of 16 -- the naive form is bound by L1/L2 request rate, not by HBM.
 // All coordinates / weights are wave-uniform scalars.
-__device__ __forceinline__ float uniform_f(float v) {   // wave-uniform value -> SGPR
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
 
 // nr = source rows / columns a 4-aligned run of 4 outputs touches: 2 (factor >= 8), 3 (factor 4) or 4 (factor 2);
 // wave-uniform, so ONE code path serves every scale (three specialised copies tripled the live accumulators).

@@ -26,13 +26,6 @@ __device__ __forceinline__ int div_fast_(int a, int b, float inv_b) {   // exact
   return q;
 }
 
-// workgroups are dealt round-robin over the 8 XCDs: give each XCD a contiguous run of the virtual order, so that the taps
-// of neighbouring tokens hit the same L2
-__device__ __forceinline__ int xcd_contiguous(int b, int nwg) {
-  const int xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-  return xcd * q + (xcd < r ? xcd : r) + (b >> 3);
-}
-
 __device__ __forceinline__ float4 fma4(float4 a, float4 w, float4 c) {
   c.x = fmaf(a.x, w.x, c.x); c.y = fmaf(a.y, w.y, c.y); c.z = fmaf(a.z, w.z, c.z); c.w = fmaf(a.w, w.w, c.w);
   return c;
@@ -84,7 +77,7 @@ __device__ __forceinline__ void stage_filter(float4* w_s, const float* __restric
 template <bool LN, typename TS>
 __global__ __launch_bounds__(256) void qkv_pool_kernel(QkvPoolArgs p) {
   __shared__ float4 w_s[28 * PQ];
-  int blk = xcd_contiguous(blockIdx.x, gridDim.x), which = 0;
+  int blk = xcd_contiguous<int>(gridDim.x), which = 0;
   if (blk >= p.blocks[0]) {
     blk -= p.blocks[0]; which = 1;
     if (blk >= p.blocks[1]) { blk -= p.blocks[1]; which = 2; }
@@ -217,7 +210,7 @@ __device__ __forceinline__ void pool_bwd_token(float4 (&acc)[3], const float4* w
 
 __global__ __launch_bounds__(256) void qkv_pool_bwd_data_kernel(QkvPoolArgs p) {
   __shared__ float4 w_s[28 * PQ];
-  int blk = xcd_contiguous(blockIdx.x, gridDim.x), which = 0;
+  int blk = xcd_contiguous<int>(gridDim.x), which = 0;
   if (blk >= p.blocks[0]) {
     blk -= p.blocks[0]; which = 1;
     if (blk >= p.blocks[1]) { blk -= p.blocks[1]; which = 2; }
@@ -411,7 +404,7 @@ __device__ __forceinline__ int run_which(const QkvPoolArgs& p, int& blk) {
 
 __global__ __launch_bounds__(256) void qkv_pool_bwd_data_runs_kernel(QkvPoolArgs p) {
   __shared__ float4 w_s[28 * PQ];
-  int blk = xcd_contiguous(blockIdx.x, gridDim.x);
+  int blk = xcd_contiguous<int>(gridDim.x);
   const int which = run_which(p, blk), g = which ? 1 : 0;
   stage_filter(w_s, p.w27[which], p.w_channel_major);
   __syncthreads();

@@ -153,8 +153,6 @@ __global__ __launch_bounds__(256) void col2im_gather_kernel(const float* __restr
   }
 }
 
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-
 // fp32 [..][32-k slices] -> per slice: 16 dwords of bf16 hi halves (k order) + 16 dwords of lo halves
 __global__ __launch_bounds__(256) void split_weight_kernel(const float* __restrict__ src, float* __restrict__ dst, long n4) {
   for (long i = static_cast<long>(blockIdx.x) * 256 + threadIdx.x; i < n4; i += static_cast<long>(gridDim.x) * 256) {

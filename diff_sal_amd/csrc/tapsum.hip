@@ -40,11 +40,6 @@ struct TapSumArgs {
   float* head_out;
 };
 
-__device__ __forceinline__ float uni_f(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ int uni_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
 // acc[d][e] += bilinear sample of `src` (row pitch P channels, this lane's channel offset already applied) at the target
 // positions (Ys + d, Xs + e), d, e = 0..3; positions outside [0,H) x [0,W) contribute nothing.
 template <typename T>
@@ -61,13 +56,13 @@ __device__ __forceinline__ void tap_accumulate(const T* __restrict__ img, int nr
     float ly, lx;
     bilin_coord(vy ? Yp : 0, sy, h, y0, y1, ly);
     bilin_coord(vx ? Xp : 0, sx, w, x0, x1, lx);
-    y0d[d] = uni_i(vy ? y0 : -(1 << 20)); y1d[d] = uni_i(vy ? y1 : -(1 << 20)); lyd[d] = uni_f(ly);
-    x0d[d] = uni_i(vx ? x0 : -(1 << 20)); x1d[d] = uni_i(vx ? x1 : -(1 << 20)); lxd[d] = uni_f(lx);
+    y0d[d] = uniform_i(vy ? y0 : -(1 << 20)); y1d[d] = uniform_i(vy ? y1 : -(1 << 20)); lyd[d] = uniform_f(ly);
+    x0d[d] = uniform_i(vx ? x0 : -(1 << 20)); x1d[d] = uniform_i(vx ? x1 : -(1 << 20)); lxd[d] = uniform_f(lx);
     if (vy && y0 < ry0) ry0 = y0;
     if (vx && x0 < rx0) rx0 = x0;
   }
-  ry0 = uni_i(ry0);
-  rx0 = uni_i(rx0);
+  ry0 = uniform_i(ry0);
+  rx0 = uniform_i(rx0);
   if (ry0 == (1 << 30) || rx0 == (1 << 30)) return;   // the whole 4x4 block of positions lies outside the image
   float wx[4][4];
 #pragma unroll
@@ -106,12 +101,10 @@ __device__ __forceinline__ void tap_accumulate(const T* __restrict__ img, int nr
 template <typename T, bool HEAD = false>
 __global__ __launch_bounds__(256) void tapsum_kernel(TapSumArgs a, T* __restrict__ out, int w_patches, int slabs, long n_items) {
   const int lane = threadIdx.x & 63, half = lane >> 5, l32 = lane & 31;
-  // XCD-aware order: workgroups are dealt round-robin over the 8 XCDs (each with its own L2), and neighbouring patches read
-  // the same source rows for every tap.  Workgroup b therefore takes the b/8-th item block of the contiguous run that belongs to
-  // XCD b % 8 (bijective for any grid size): an XCD's L2 sees whole bands of one image instead of every eighth patch of all of
-  // them.  PMC before: 2.6x the once-through bytes fetched from HBM, at which point the gather was HBM-bound.
-  const unsigned nb = gridDim.x, xq = nb >> 3, xr = nb & 7u, xcd = blockIdx.x & 7u;
-  const unsigned vb = xcd * xq + (xcd < xr ? xcd : xr) + (blockIdx.x >> 3);
+  // XCD-aware order: neighbouring patches read the same source rows for every tap, and an XCD's L2 sees whole bands of one image
+  // instead of every eighth patch of all of them.  PMC before: 2.6x the once-through bytes fetched from HBM, at which point the
+  // gather was HBM-bound.
+  const unsigned vb = xcd_contiguous<unsigned>(gridDim.x);
   const long item = static_cast<long>(vb) * 4 + (threadIdx.x >> 6);
   if (item >= n_items) return;
   const int slab = static_cast<int>(item % slabs);
@@ -120,7 +113,7 @@ __global__ __launch_bounds__(256) void tapsum_kernel(TapSumArgs a, T* __restrict
   const int px = static_cast<int>(t % w_patches); t /= w_patches;
   const int py = static_cast<int>(t % h_patches);
   const int pair = static_cast<int>(t / h_patches);
-  const int Y0 = uni_i(py * 4), X0 = uni_i(px * 4);
+  const int Y0 = uniform_i(py * 4), X0 = uniform_i(px * 4);
   const int n = pair * 2 + half, c = slab * 128 + l32 * 4;
   const bool live = n < a.N && c < a.C;
   const int nc = n < a.N ? n : a.N - 1, cc = c < a.C ? c : a.C - 4;   // dead lanes walk valid memory and store nothing
@@ -250,24 +243,24 @@ __device__ __forceinline__ void tap_source_rows(const char* __restrict__ src, un
     int lower;
     float a, b;
     tap_pos(X0 - 1 + i, W, w, sx, lower, a, b);
-    wxa[i] = SX ? a : uni_f(a);                     // !SX: wave-uniform, scalar registers
-    wxb[i] = SX ? b : uni_f(b);
+    wxa[i] = SX ? a : uniform_f(a);                     // !SX: wave-uniform, scalar registers
+    wxb[i] = SX ? b : uniform_f(b);
     if (i == 0) first_x = lower;
-    xr[i] = SX ? lower - first_x : uni_i(lower - first_x);     // F = 2, 4: (2 i - 1 + F) / (2 F) by construction; F = 0: 0 or 1
+    xr[i] = SX ? lower - first_x : uniform_i(lower - first_x);     // F = 2, 4: (2 i - 1 + F) / (2 F) by construction; F = 0: 0 or 1
   }
-  if constexpr (!SX) first_x = uni_i(first_x);
+  if constexpr (!SX) first_x = uniform_i(first_x);
   unsigned coff[NL];               // !SX: uniform column offset (added to the scalar base); SX: this lane's byte offset, column included
 #pragma unroll
   for (int c = 0; c < NL; ++c) {
     const int col = min(max(first_x + c, 0), w - 1);
-    coff[c] = SX ? lane_byte + static_cast<unsigned>(col * P * 4) : static_cast<unsigned>(uni_i(col) * P * 4);
+    coff[c] = SX ? lane_byte + static_cast<unsigned>(col * P * 4) : static_cast<unsigned>(uniform_i(col) * P * 4);
   }
   // ---- y axis: dense weights wtab[j * 4 + r] of line r (0 .. NL-1) for position j, one entry per lane
   int first_y;
   {
     float a0, b0;
     tap_pos(Y0 - 1, H, h, sy, first_y, a0, b0);
-    first_y = uni_i(first_y);
+    first_y = uniform_i(first_y);
     if (lane < NPY * NLP) {
       const int j = lane / NLP, r = lane - j * NLP;
       int lower;
@@ -289,8 +282,8 @@ __device__ __forceinline__ void tap_source_rows(const char* __restrict__ src, un
     for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
       for (int c = 0; c < NL; ++c) {    // the offset IS uniform; inside the runtime loop hipcc no longer proves it: say so
-        if constexpr (SX) V[kx][c] = tap_ld<CPL>(src + static_cast<unsigned>(uni_i(roff + kx * C * 4)), coff[c]);
-        else V[kx][c] = tap_ld<CPL>(src + static_cast<unsigned>(uni_i(roff + static_cast<int>(coff[c]) + kx * C * 4)), lane_byte);
+        if constexpr (SX) V[kx][c] = tap_ld<CPL>(src + static_cast<unsigned>(uniform_i(roff + kx * C * 4)), coff[c]);
+        else V[kx][c] = tap_ld<CPL>(src + static_cast<unsigned>(uniform_i(roff + static_cast<int>(coff[c]) + kx * C * 4)), lane_byte);
       }
   };
   auto sum = [&](const TapVec<CPL> (&V)[3][NL], int it) __attribute__((always_inline)) {
@@ -378,8 +371,7 @@ __global__ __launch_bounds__(256, IMGS == 1 ? 2 : 1) void tapsum_head_rows_kerne
   constexpr int LPI = 64 / IMGS;
   __shared__ float wtab_all[4][64];
   const int lane = threadIdx.x & 63, sub = lane / LPI, li = lane % LPI;
-  const unsigned nb = gridDim.x, xq = nb >> 3, xr = nb & 7u, xcd = blockIdx.x & 7u;       // XCD-aware order, as tapsum_kernel
-  const unsigned vb = xcd * xq + (xcd < xr ? xcd : xr) + (blockIdx.x >> 3);
+  const unsigned vb = xcd_contiguous<unsigned>(gridDim.x);       // XCD-aware order, as tapsum_kernel
   const long item = static_cast<long>(vb) * 4 + (threadIdx.x >> 6);
   if (item >= n_items) return;
   float* wtab = wtab_all[threadIdx.x >> 6];
@@ -399,7 +391,7 @@ __global__ __launch_bounds__(256, IMGS == 1 ? 2 : 1) void tapsum_head_rows_kerne
     py = static_cast<int>(t % h_patches);
     grp = static_cast<int>(t / h_patches);
   }
-  const int Y0 = uni_i(py * PS), X0 = SX ? (px * 2 + sub) * 4 : uni_i(px * 4);     // SX: w_patches counts 8-pixel patch pairs
+  const int Y0 = uniform_i(py * PS), X0 = SX ? (px * 2 + sub) * 4 : uniform_i(px * 4);     // SX: w_patches counts 8-pixel patch pairs
   const int n = SX ? grp : grp * IMGS + sub, c = li * CPL;
   const int nc = n < a.N ? n : a.N - 1, cc = c < a.C ? c : a.C - CPL;   // dead lanes walk valid memory and contribute nothing
   const int P = 9 * a.C;
@@ -461,16 +453,6 @@ __global__ __launch_bounds__(256, IMGS == 1 ? 2 : 1) void tapsum_head_rows_kerne
 // weight 0 in the row-streamed kernel: same sums, same order, same bits.
 // ------------------------------------------------------------------------------------------------
 constexpr int kTlSlot = 12288, kTlDepth = 6;
-typedef int tl_i32x4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) void* tl_lds_ptr_t;
-
-__device__ __forceinline__ void tl_dma(unsigned lds_addr, unsigned voff, tl_i32x4 rsrc, unsigned soff) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :
-               : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff)
-               : "memory", "m0");
-}
-
 // one (ky, line) item of this wavefront: slot = the staged line (pixel-major: [column][3 kx][C] fp32), rl = the line's index among the
 // wavefront's own lines, col0 = this lane half's first column in the block's window, ncb = the window's columns
 template <int CPL, int F>
@@ -538,7 +520,7 @@ __device__ __forceinline__ void tap_pos2(int p, int L, int n, float scale, int l
 // are multiplied, the first items of the next one are already on their way)
 struct TlIssue {
   unsigned voff[3];     // this lane's three pieces of a line: byte offset of (window column, piece)
-  tl_i32x4 rsrc;        // the source's image n
+  i32x4 rsrc;        // the source's image n
   int s, bfy, hs, ws, nlb, iky, ir, slot;
   bool done;            // the source's last item has gone out
 };
@@ -552,9 +534,9 @@ __device__ __forceinline__ void tl_issue_setup(const TapSumArgs& a, TlIssue& st,
   st.nlb = max(16 >> a.lf[s], 1) + 2;                          // lines and columns of the block's window
   int lo; float aa, bb;
   tap_pos2(BY - 1, a.H, st.hs, a.sy[s], a.lf[s], lo, aa, bb);
-  st.bfy = uni_i(lo);
+  st.bfy = uniform_i(lo);
   tap_pos2(BX - 1, a.W, st.ws, a.sx[s], a.lf[s], lo, aa, bb);
-  const int bfx = uni_i(lo);
+  const int bfx = uniform_i(lo);
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
     const int pc = q * 256 + tid;
@@ -563,7 +545,7 @@ __device__ __forceinline__ void tl_issue_setup(const TapSumArgs& a, TlIssue& st,
     st.voff[q] = static_cast<unsigned>(col * P * 4 + j * 16);
   }
   const unsigned long base = reinterpret_cast<unsigned long>(a.in[s]) + static_cast<unsigned long>(n) * st.hs * st.ws * P * 4ul;
-  st.rsrc = tl_i32x4{static_cast<int>(base), static_cast<int>(base >> 32) & 0xFFFF, st.hs * st.ws * P * 4, 0x00020000};
+  st.rsrc = dma_rsrc(base, st.hs * st.ws * P * 4);
   st.iky = 0; st.ir = 0; st.done = false;
 }
 
@@ -574,7 +556,7 @@ __device__ __forceinline__ void tl_issue_one(TlIssue& st, unsigned lds0, int wav
   const int line = min(max(st.bfy + st.ir, 0), st.hs - 1);
   const unsigned soff = static_cast<unsigned>(line * st.ws * P * 4 + st.iky * 3 * C * 4);
 #pragma unroll
-  for (int q = 0; q < 3; ++q) tl_dma(lds0 + st.slot * kTlSlot + (q * 4 + wave) * 1024, st.voff[q], st.rsrc, soff);
+  for (int q = 0; q < 3; ++q) dma_piece(lds0 + st.slot * kTlSlot + (q * 4 + wave) * 1024, st.voff[q], st.rsrc, soff);
   st.slot = st.slot + 1 == kTlDepth ? 0 : st.slot + 1;
   const bool wrap = st.ir + 1 == st.nlb, last = wrap && st.iky == 2;
   st.done = st.done || last;
@@ -588,7 +570,7 @@ __device__ __forceinline__ void tl_source(const TapSumArgs& a, int s, int n, int
                                           const unsigned char* __restrict__ smem, float* __restrict__ wtab, TlIssue& is, int& sl,
                                           float (&acc)[8][4][CPL]) {
   constexpr int NLYW = F == 2 ? 6 : (F == 4 ? 4 : 3);
-  const int lane = threadIdx.x & 63, wave = uni_i(threadIdx.x >> 6), li = lane & 31;
+  const int lane = threadIdx.x & 63, wave = uniform_i(threadIdx.x >> 6), li = lane & 31;
   const int hs = a.h[s], ws = a.w[s], lf = a.lf[s];
   const int nlb = max(16 >> lf, 1) + 2;
   const int n_it = 3 * nlb;
@@ -605,11 +587,11 @@ __device__ __forceinline__ void tl_source(const TapSumArgs& a, int s, int n, int
   }
   int lo, first_yw; float aa, bb;
   tap_pos2(BX - 1, a.W, ws, a.sx[s], lf, lo, aa, bb);
-  const int col0 = first_x - uni_i(lo);
+  const int col0 = first_x - uniform_i(lo);
   tap_pos2(Y0 - 1, a.H, hs, a.sy[s], lf, first_yw, aa, bb);
-  first_yw = uni_i(first_yw);
+  first_yw = uniform_i(first_yw);
   tap_pos2(BY - 1, a.H, hs, a.sy[s], lf, lo, aa, bb);
-  const int lw = first_yw - uni_i(lo);
+  const int lw = first_yw - uniform_i(lo);
   if (lane < 60) {                                 // (the table is this wavefront's own: its reads of the previous source's are behind it)
     const int j = lane / 6, r = lane - j * 6;
     int lower;
@@ -637,15 +619,14 @@ template <int CPL, int C>
 __global__ __launch_bounds__(256, 2) void tapsum_head_lds_kernel(TapSumArgs a, int bw, int bh) {
   extern __shared__ __attribute__((aligned(16))) unsigned char tl_smem[];
   float* wtab = reinterpret_cast<float*>(tl_smem + kTlDepth * kTlSlot) + (threadIdx.x >> 6) * 64;
-  const int tid = threadIdx.x, lane = tid & 63, wave = uni_i(tid >> 6), sub = lane >> 5, li = lane & 31;
-  const unsigned nb = gridDim.x, xq = nb >> 3, xrm = nb & 7u, xcd = blockIdx.x & 7u;       // XCD-aware order: an image's blocks on one XCD
-  const unsigned vb = xcd * xq + (xcd < xrm ? xcd : xrm) + (blockIdx.x >> 3);
+  const int tid = threadIdx.x, lane = tid & 63, wave = uniform_i(tid >> 6), sub = lane >> 5, li = lane & 31;
+  const unsigned vb = xcd_contiguous<unsigned>(gridDim.x);       // XCD-aware order: an image's blocks on one XCD
   const int bx = static_cast<int>(vb % bw), by = static_cast<int>((vb / bw) % bh), n = static_cast<int>(vb / (static_cast<unsigned>(bw) * bh));
   const int BY = by * 16, BX = bx * 16;
   const int Y0 = BY + (wave >> 1) * 8;                         // wave-uniform
   const int X0 = BX + ((wave & 1) * 2 + sub) * 4;              // per lane half
   const int c0 = li * CPL;
-  const unsigned lds0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>((tl_lds_ptr_t)tl_smem));
+  const unsigned lds0 = static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_ptr_t)tl_smem));
   float acc[8][4][CPL];
 #pragma unroll
   for (int d = 0; d < 8; ++d)

@@ -24,21 +24,7 @@
 
 namespace diffsal {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-template <typename T> struct Mma16;
-template <> struct Mma16<__bf16> {
-  typedef bf16x8 vec;
-  static __device__ __forceinline__ f32x16 mma(vec a, vec b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mma16<_Float16> {
-  typedef f16x8 vec;
-  static __device__ __forceinline__ f32x16 mma(vec a, vec b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
-};
-template <> struct Mma16<float> { typedef f32x8 vec; };   // placeholder: the fp32 instantiation never touches the 16-bit branch
+template <> struct Mfma32x16<float> { typedef f32x8_t vec; };   // placeholder: the fp32 instantiation never touches the 16-bit branch
 
 template <typename T>
 struct FrontArgs {
@@ -116,7 +102,7 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 4 || C > 96) ? 1 : 2)) void blo
   // ahead.  16-bit storage fits two workgroups per CU, which cover each other's load phases; no look-ahead (256 registers)
   // C = 192 on 16-bit storage: Wq + the halo tile fill the LDS: one workgroup per CU as well, same look-ahead
   constexpr bool AHEAD = F32 || C > 96;
-  typedef typename Mma16<T>::vec vec;
+  typedef typename Mfma32x16<T>::vec vec;
   typedef typename RawPiece<T>::type raw_t;
   auto raw_to_f4 = [](raw_t r) { return raw_to_f4_impl(r, static_cast<const T*>(nullptr)); };
   constexpr int NU = C / 32;                 // 32-channel row tiles
@@ -341,7 +327,7 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 4 || C > 96) ? 1 : 2)) void blo
     if constexpr (!F32) {
 #pragma unroll
       for (int s = 0; s < C / 16; ++s) {                               // k-step s = 2 u + j consumes channel groups 2 s, 2 s + 1
-        f32x8 t8 = {qin[2 * s].x, qin[2 * s].y, qin[2 * s].z, qin[2 * s].w,
+        f32x8_t t8 = {qin[2 * s].x, qin[2 * s].y, qin[2 * s].z, qin[2 * s].w,
                     qin[2 * s + 1].x, qin[2 * s + 1].y, qin[2 * s + 1].z, qin[2 * s + 1].w};
         qb[s] = __builtin_convertvector(t8, vec);
       }
@@ -402,7 +388,7 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 4 || C > 96) ? 1 : 2)) void blo
           const vec b = qb[s];
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int t = 0; t < NU; ++t) qt[t] = Mma16<T>::mma(af[s & 1][t], b, qt[t]);
+          for (int t = 0; t < NU; ++t) qt[t] = Mfma32x16<T>::run(af[s & 1][t], b, qt[t]);
           __builtin_amdgcn_sched_barrier(0);
         }
       } else {
@@ -423,7 +409,7 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 4 || C > 96) ? 1 : 2)) void blo
           const vec b = qb[s];
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int t = 0; t < HT; ++t) qt[h0 + t] = Mma16<T>::mma(af[i & 1][t], b, qt[h0 + t]);
+          for (int t = 0; t < HT; ++t) qt[h0 + t] = Mfma32x16<T>::run(af[i & 1][t], b, qt[h0 + t]);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -464,10 +450,10 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 4 || C > 96) ? 1 : 2)) void blo
 #pragma unroll
         for (int s = hd * (D / 16); s < (hd + 1) * (D / 16); ++s) {     // k-steps (16 channels) of this head
           const int u = s >> 1, j = s & 1;
-          f32x8 t8;
+          f32x8_t t8;
 #pragma unroll
           for (int e = 0; e < 8; ++e) t8[e] = qt[u][8 * j + e];
-          st = Mma16<T>::mma(*reinterpret_cast<const vec*>(kf + 16 * s), __builtin_convertvector(t8, vec), st);
+          st = Mfma32x16<T>::run(*reinterpret_cast<const vec*>(kf + 16 * s), __builtin_convertvector(t8, vec), st);
         }
       }
       // key of register r in this lane half: (r & 3) + 8 (r >> 2) + 4 hf
@@ -517,12 +503,12 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 4 || C > 96) ? 1 : 2)) void blo
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
             if (16 * j < p.Lk) {
-              f32x8 t8;
+              f32x8_t t8;
 #pragma unroll
               for (int e = 0; e < 8; ++e) t8[e] = pt[hd][8 * j + e];
               uint4 araw = *reinterpret_cast<const uint4*>(vtf + 32 * u * PV + 16 * j);
               if (!mine) araw = make_uint4(0u, 0u, 0u, 0u);
-              ot[u] = Mma16<T>::mma(__builtin_bit_cast(vec, araw), __builtin_convertvector(t8, vec), ot[u]);
+              ot[u] = Mfma32x16<T>::run(__builtin_bit_cast(vec, araw), __builtin_convertvector(t8, vec), ot[u]);
             }
           }
         }

@@ -15,7 +15,6 @@
 
 namespace diffsal {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct WgradArgs {
   const float* in;   // layer input, NHWC
@@ -59,10 +58,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs p) {
   const int m_end = min(p.M, (seg + 1) * p.seg_rows);
   const int m_stride = p.splits * BM;
   const int HoWo = p.Ho * p.Wo;
-  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(p.in), 0, static_cast<int>(p.in_bytes), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_dy = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(p.dy), 0, static_cast<int>(p.dy_bytes), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc = buffer_rsrc(p.in, static_cast<int>(p.in_bytes));
+  const __amdgpu_buffer_rsrc_t rsrc_dy = buffer_rsrc(p.dy, static_cast<int>(p.dy_bytes));
 
   f32x16 acc[CT][ST];
 #pragma unroll
@@ -188,15 +185,6 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradArgs p) {
 // lane's (row, column) fixed for the kernel.  Rows past the split's end, columns past Cout / K: offset 0xFFFFFFFF, the DMA
 // writes zeros.  Same accumulation order per output element as wgrad_kernel (rows in ascending order inside a split).
 // ---------------------------------------------------------------------------------------------------------------------------
-typedef int wg_i32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void wgrad_dma_piece(unsigned lds_addr, unsigned voff, wg_i32x4 rsrc) {
-  asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" : : "s"(lds_addr), "v"(voff), "s"(rsrc) : "memory", "m0");
-}
-template <int N>
-__device__ __forceinline__ void wgrad_wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 template <int CT, int WCO, int WK, int ST>
 __global__ __launch_bounds__(256, 1) void wgrad_dma_kernel(WgradArgs p) {
   static_assert(WCO * WK == 4, "four waves");
@@ -220,8 +208,8 @@ __global__ __launch_bounds__(256, 1) void wgrad_dma_kernel(WgradArgs p) {
   const int n_steps = m_begin < m_end ? (m_end - m_begin + m_stride - 1) / m_stride : 0;
 
   const unsigned long pdy = reinterpret_cast<unsigned long>(p.dy), pin = reinterpret_cast<unsigned long>(p.in);
-  const wg_i32x4 rs_dy = {static_cast<int>(pdy), static_cast<int>(pdy >> 32) & 0xFFFF, static_cast<int>(p.dy_bytes), 0x00020000};
-  const wg_i32x4 rs_x = {static_cast<int>(pin), static_cast<int>(pin >> 32) & 0xFFFF, static_cast<int>(p.in_bytes), 0x00020000};
+  const i32x4 rs_dy = dma_rsrc(pdy, static_cast<int>(p.dy_bytes));
+  const i32x4 rs_x = dma_rsrc(pin, static_cast<int>(p.in_bytes));
   // this lane's slot in every piece it issues: (row of the step, byte offset inside the operand's row), ~0 when the column is
   // outside the matrix
   int a_row[APW], b_row[BPW];
@@ -240,7 +228,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_dma_kernel(WgradArgs p) {
     const int k = sl0 * 32 + (idx - b_row[q] * (BKI / 4)) * 4;
     b_col[q] = k < p.K ? static_cast<unsigned>(k) * 4u : 0xFFFFFFFFu;
   }
-  const unsigned lds_base = static_cast<unsigned>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) void*)smem)) + wave * 1024u;
+  const unsigned lds_base = static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_ptr_t)smem)) + wave * 1024u;
   int iss_step = 0;
   auto issue_piece = [&](int stage, int q) __attribute__((always_inline)) {      // q < APW: dY, else X
     const int mb = m_begin + iss_step * m_stride;
@@ -248,12 +236,12 @@ __global__ __launch_bounds__(256, 1) void wgrad_dma_kernel(WgradArgs p) {
     if (q < APW) {
       const int m = mb + a_row[q];
       const unsigned off = (m < m_end && iss_step < n_steps) ? static_cast<unsigned>(m) * static_cast<unsigned>(p.Cout * 4) + a_col[q] : 0xFFFFFFFFu;
-      wgrad_dma_piece(st + q * 4096u, off | (a_col[q] == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u), rs_dy);
+      dma_piece(st + q * 4096u, off | (a_col[q] == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u), rs_dy);
     } else {
       const int qb = q - APW;
       const int m = mb + b_row[qb];
       const unsigned off = (m < m_end && iss_step < n_steps) ? static_cast<unsigned>(m) * static_cast<unsigned>(p.K * 4) + b_col[qb] : 0xFFFFFFFFu;
-      wgrad_dma_piece(st + (A_F + qb * 1024) * 4u, off | (b_col[qb] == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u), rs_x);
+      dma_piece(st + (A_F + qb * 1024) * 4u, off | (b_col[qb] == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u), rs_x);
     }
   };
 
@@ -273,7 +261,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_dma_kernel(WgradArgs p) {
     for (int q = 0; q < PPW; ++q) issue_piece(s, q);
     ++iss_step;
   }
-  wgrad_wait_vmcnt<(P - 1) * PPW>();
+  wait_vmcnt<(P - 1) * PPW>();
   __builtin_amdgcn_s_barrier();
 
   int stage = 0;
@@ -311,7 +299,7 @@ __global__ __launch_bounds__(256, 1) void wgrad_dma_kernel(WgradArgs p) {
       __builtin_amdgcn_sched_barrier(0);
     }
     // step t + 1 (this wave's pieces) has landed; after the barrier every wave's have, and nobody reads stage `ist` any more
-    wgrad_wait_vmcnt<WAIT_N>();
+    wait_vmcnt<WAIT_N>();
     __builtin_amdgcn_s_barrier();
 #pragma unroll
     for (int ks = BM / 4; ks < BM / 2; ++ks) {
@@ -370,8 +358,8 @@ __global__ __launch_bounds__(256, 2) void wgrad_dma2_kernel(WgradArgs p) {
   const int n_steps = m_begin < m_end ? (m_end - m_begin + m_stride - 1) / m_stride : 0;
 
   const unsigned long pdy = reinterpret_cast<unsigned long>(p.dy), pin = reinterpret_cast<unsigned long>(p.in);
-  const wg_i32x4 rs_dy = {static_cast<int>(pdy), static_cast<int>(pdy >> 32) & 0xFFFF, static_cast<int>(p.dy_bytes), 0x00020000};
-  const wg_i32x4 rs_x = {static_cast<int>(pin), static_cast<int>(pin >> 32) & 0xFFFF, static_cast<int>(p.in_bytes), 0x00020000};
+  const i32x4 rs_dy = dma_rsrc(pdy, static_cast<int>(p.dy_bytes));
+  const i32x4 rs_x = dma_rsrc(pin, static_cast<int>(p.in_bytes));
   // this lane's slot in every piece it issues: (row of the step, byte offset inside the operand's row), ~0 when the column is
   // outside the matrix
   int a_row[APW], b_row[BPW];
@@ -390,7 +378,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_dma2_kernel(WgradArgs p) {
     const int k = sl0 * 32 + (idx - b_row[q] * (BKI / 4)) * 4;
     b_col[q] = k < p.K ? static_cast<unsigned>(k) * 4u : 0xFFFFFFFFu;
   }
-  const unsigned lds_base = static_cast<unsigned>(reinterpret_cast<uintptr_t>((__attribute__((address_space(3))) void*)smem)) + wave * 1024u;
+  const unsigned lds_base = static_cast<unsigned>(reinterpret_cast<uintptr_t>((lds_ptr_t)smem)) + wave * 1024u;
   int iss_step = 0;
   auto issue_piece = [&](int stage, int q) __attribute__((always_inline)) {      // q < APW: dY, else X
     const int mb = m_begin + iss_step * m_stride;
@@ -398,12 +386,12 @@ __global__ __launch_bounds__(256, 2) void wgrad_dma2_kernel(WgradArgs p) {
     if (q < APW) {
       const int m = mb + a_row[q];
       const unsigned off = (m < m_end && iss_step < n_steps) ? static_cast<unsigned>(m) * static_cast<unsigned>(p.Cout * 4) + a_col[q] : 0xFFFFFFFFu;
-      wgrad_dma_piece(st + q * 4096u, off | (a_col[q] == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u), rs_dy);
+      dma_piece(st + q * 4096u, off | (a_col[q] == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u), rs_dy);
     } else {
       const int qb = q - APW;
       const int m = mb + b_row[qb];
       const unsigned off = (m < m_end && iss_step < n_steps) ? static_cast<unsigned>(m) * static_cast<unsigned>(p.K * 4) + b_col[qb] : 0xFFFFFFFFu;
-      wgrad_dma_piece(st + (A_F + qb * 1024) * 4u, off | (b_col[qb] == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u), rs_x);
+      dma_piece(st + (A_F + qb * 1024) * 4u, off | (b_col[qb] == 0xFFFFFFFFu ? 0xFFFFFFFFu : 0u), rs_x);
     }
   };
 
@@ -420,7 +408,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_dma2_kernel(WgradArgs p) {
 #pragma unroll
   for (int q = 0; q < PPW; ++q) issue_piece(0, q);
   ++iss_step;
-  wgrad_wait_vmcnt<0>();
+  wait_vmcnt<0>();
   __builtin_amdgcn_s_barrier();
 
   for (int t = 0; t < n_steps; ++t) {

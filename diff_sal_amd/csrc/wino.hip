@@ -25,7 +25,6 @@
 
 namespace diffsal {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct WinoGeom {
   int N, H, W, Cin, Cout, d;
@@ -154,8 +153,7 @@ __global__ __launch_bounds__(256) void wino_gemm_kernel(WinoArgs p) {
   // contiguous run of it -- the channel blocks of a tile block then read their shared V block from ONE L2
   int vb, tail_piece = -1;
   if (static_cast<int>(blockIdx.x) < p.n_full) {
-    const int nwg = p.n_full, b = blockIdx.x, xcd = b & 7, q = nwg >> 3, r = nwg & 7;
-    vb = xcd * q + (xcd < r ? xcd : r) + (b >> 3);
+    vb = xcd_contiguous<int>(p.n_full);
   } else {                                   // a piece of a tail block: dispatched after every whole block
     const int t = static_cast<int>(blockIdx.x) - p.n_full;
     vb = p.n_full + t / p.tail_split;
@@ -176,7 +174,6 @@ __global__ __launch_bounds__(256) void wino_gemm_kernel(WinoArgs p) {
   // SOURCE address: the lane that fills slot s loads float4 wino_slot(s) of the block, and the fragment reads apply the same
   // involution.  The pieces of chunk c + 1 are issued between the MFMAs of the first half of chunk c (four per pair of positions)
   // into the other stage; the __syncthreads() at the end of the chunk retires them (vmcnt(0)) before anyone reads that stage.
-  typedef __attribute__((address_space(3))) void* lds_ptr_t;
   typedef const __attribute__((address_space(1))) void* glb_ptr_t;
   const unsigned src_off = 16u * static_cast<unsigned>(tid ^ ((lane >> 4) & 1));   // bytes; the only per-lane address part
   auto block_v = [&](int c) { return reinterpret_cast<const char*>(p.V + (static_cast<long>(c) * g.tile_blocks + tb) * 8192); };
