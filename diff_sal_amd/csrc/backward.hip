@@ -213,6 +213,7 @@ __global__ __launch_bounds__(256) void norm_finalize_bwd_kernel(const double* __
 }
 
 // y = act(x * s[seg, c] + t[seg, c])   (BatchNorm / GroupNorm forward once the statistics are folded into s, t)
+constexpr int kActSwish = 4;   // diffsal_affine_act's own act code (part of its ABI), beside DIFFSAL_ACT_NONE / RELU / GELU_ERF
 __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict__ x, const float* __restrict__ sc,
                                                          const float* __restrict__ sh_, float* __restrict__ out, long M,
                                                          int C, int seg_rows, int act) {
@@ -226,9 +227,10 @@ __global__ __launch_bounds__(256) void affine_act_kernel(const float* __restrict
     float o[4] = {v.x * s4.x + t4.x, v.y * s4.y + t4.y, v.z * s4.z + t4.z, v.w * s4.w + t4.w};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      if (act == DIFFSAL_ACT_RELU) o[k] = fmaxf(o[k], 0.f);
-      else if (act == DIFFSAL_ACT_GELU_ERF) o[k] = gelu_erf(o[k]);
-      else if (act == 4) o[k] = swishf(o[k]);
+      float w[1] = {o[k]};
+      if (act == kActSwish) w[0] = swishf(w[0]);
+      else if (act != DIFFSAL_ACT_SIGMOID) epi_act(w, act);   // none, ReLU or GELU: this entry point has no sigmoid
+      o[k] = w[0];
     }
     st4(out + m * C + c, make_float4(o[0], o[1], o[2], o[3]));
   }

@@ -339,4 +339,72 @@ __device__ __forceinline__ float uniform_f(float v) {
   return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
 }
 
+// The epilogue of the matrix kernels, on N (1, 4 or 8) consecutive output channels n .. n + N - 1 of one output row, in fp32:
+//   v += bias[n];  v = v * scale[n] + shift[n];  v += rowvec[image of the row][n];  v = act(v);
+//   v += residual   (act == DIFFSAL_ACT_GELU_GRAD:  v *= gelu_erf'(residual));   one rounding at the store.
+// A term whose operand is absent is skipped (skipped, not "added as zero": -0.0 + 0.0 is +0.0).  scale and shift come together:
+// every entry point refuses one without the other, so `scale` alone decides and `shift` is read untested.  Only fp32
+// diffsal_conv_igemm accepts DIFFSAL_ACT_GELU_GRAD (and then requires `residual`): its kernels choose between epi_gelu_grad and
+// epi_add, every other kernel has epi_add alone.  Loads of the residual, bounds tests, LDS staging and stores stay with the kernels.
+template <int N>
+__device__ __forceinline__ void epi_act(float (&v)[N], int act) {
+  if (act == DIFFSAL_ACT_RELU) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] = fmaxf(v[e], 0.f);
+  } else if (act == DIFFSAL_ACT_GELU_ERF) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] = gelu_erf(v[e]);
+  } else if (act == DIFFSAL_ACT_SIGMOID) {
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] = sigmoidf_(v[e]);
+  }
+}
+
+// t = p[0 .. N - 1], as 16-byte loads when N is 4 or 8
+template <int N>
+__device__ __forceinline__ void epi_ld(float (&t)[N], const float* p) {
+  static_assert(N == 1 || N % 4 == 0, "one channel or whole quads");
+  if constexpr (N == 1) {
+    t[0] = *p;
+  } else {
+#pragma unroll
+    for (int q = 0; q < N; q += 4) {
+      const float4 x = ld4(p + q);
+      t[q] = x.x; t[q + 1] = x.y; t[q + 2] = x.z; t[q + 3] = x.w;
+    }
+  }
+}
+template <int N>
+__device__ __forceinline__ void epi_add(float (&v)[N], const float (&t)[N]) {
+#pragma unroll
+  for (int e = 0; e < N; ++e) v[e] += t[e];
+}
+__device__ __forceinline__ void epi_add(float (&v)[4], float4 t) { v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
+// bias, scale / shift and rowvec from memory: the vectors' base pointers (null: absent) and n.  rowvec's row starts at
+// rowvec + row_off(), which is evaluated only when rowvec is set (an image index usually costs a division).
+template <int N, typename RowOff>
+__device__ __forceinline__ void epi_channels(float (&v)[N], const float* bias, const float* scale, const float* shift, const float* rowvec,
+                                             RowOff row_off, int n) {
+  float t[N], h[N];
+  if (bias) { epi_ld(t, bias + n); epi_add(v, t); }
+  if (scale) {
+    epi_ld(t, scale + n);
+    epi_ld(h, shift + n);
+#pragma unroll
+    for (int e = 0; e < N; ++e) v[e] = v[e] * t[e] + h[e];
+  }
+  if (rowvec) { epi_ld(t, rowvec + row_off() + n); epi_add(v, t); }
+}
+// the same with the row's address in hand: rowvec_row = rowvec + the row's offset, or null
+template <int N>
+__device__ __forceinline__ void epi_channels(float (&v)[N], const float* bias, const float* scale, const float* shift, const float* rowvec_row,
+                                             int n) {
+  epi_channels(v, bias, scale, shift, rowvec_row, [] { return 0; }, n);
+}
+
+// DIFFSAL_ACT_GELU_GRAD's residual term, v *= gelu_erf'(r), on a residual the caller has loaded (the plain term is epi_add)
+__device__ __forceinline__ void epi_gelu_grad(float (&v)[4], float4 r) {
+  v[0] *= gelu_erf_grad(r.x); v[1] *= gelu_erf_grad(r.y); v[2] *= gelu_erf_grad(r.z); v[3] *= gelu_erf_grad(r.w);
+}
+
 }  // namespace diffsal

@@ -283,37 +283,10 @@ __global__ __launch_bounds__(256, 2) void conv16_dma_kernel(CdArgs<T> p) {
       const float4 s0 = ld4(stage + px * 100 + oc * 8), s1 = ld4(stage + px * 100 + oc * 8 + 4);
       if (gy >= p.Ho || gx >= p.Wo || n >= p.Cout || ti >= p.N) continue;
       float v[8] = {s0.x, s0.y, s0.z, s0.w, s1.x, s1.y, s1.z, s1.w};
-      if (p.bias) {
-        const float4 t0 = ld4(p.bias + n), t1 = ld4(p.bias + n + 4);
-        v[0] += t0.x; v[1] += t0.y; v[2] += t0.z; v[3] += t0.w; v[4] += t1.x; v[5] += t1.y; v[6] += t1.z; v[7] += t1.w;
-      }
-      if (p.scale) {
-        const float4 c0 = ld4(p.scale + n), c1 = ld4(p.scale + n + 4);
-        const float4 h0 = p.shift ? ld4(p.shift + n) : make_float4(0.f, 0.f, 0.f, 0.f), h1 = p.shift ? ld4(p.shift + n + 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        v[0] = v[0] * c0.x + h0.x; v[1] = v[1] * c0.y + h0.y; v[2] = v[2] * c0.z + h0.z; v[3] = v[3] * c0.w + h0.w;
-        v[4] = v[4] * c1.x + h1.x; v[5] = v[5] * c1.y + h1.y; v[6] = v[6] * c1.z + h1.z; v[7] = v[7] * c1.w + h1.w;
-      }
-      if (rv_row) {
-        const float* rv = MI ? rv_row + static_cast<long>(ti - img) * p.rowvec_ld : rv_row;
-        const float4 t0 = ld4(rv + n), t1 = ld4(rv + n + 4);
-        v[0] += t0.x; v[1] += t0.y; v[2] += t0.z; v[3] += t0.w; v[4] += t1.x; v[5] += t1.y; v[6] += t1.z; v[7] += t1.w;
-      }
-      if (p.act == DIFFSAL_ACT_RELU) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = fmaxf(v[e], 0.f);
-      } else if (p.act == DIFFSAL_ACT_GELU_ERF) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = gelu_erf(v[e]);
-      } else if (p.act == DIFFSAL_ACT_SIGMOID) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = sigmoidf_(v[e]);
-      }
+      epi_channels(v, p.bias, p.scale, p.shift, rv_row, [&] { return MI ? static_cast<long>(ti - img) * p.rowvec_ld : 0; }, n);
+      epi_act(v, p.act);
       const long o = ((static_cast<long>(ti) * p.Ho + gy) * p.Wo + gx) * p.Cout + n;
-      if (resid) {
-        const f8v t = ld8(reinterpret_cast<const T*>(&rraw[it]));
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] += t.v[e];
-      }
+      if (resid) epi_add(v, ld8(reinterpret_cast<const T*>(&rraw[it])).v);
       f8v ov;
 #pragma unroll
       for (int e = 0; e < 8; ++e) ov.v[e] = v[e];

@@ -241,24 +241,9 @@ __global__ __launch_bounds__(NW * 64) void conv16_halo_kernel(HaloArgs<T> p) {
         if (n >= p.Cout) continue;
         const long o = obase + n;
         float v[4] = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
-        if (p.bias) { const float4 t = ld4(p.bias + n); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
-        if (p.scale) {
-          const float4 sc = ld4(p.scale + n);
-          const float4 sh = p.shift ? ld4(p.shift + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-          v[0] = v[0] * sc.x + sh.x; v[1] = v[1] * sc.y + sh.y; v[2] = v[2] * sc.z + sh.z; v[3] = v[3] * sc.w + sh.w;
-        }
-        if (rv_row) { const float4 t = ld4(rv_row + n); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
-        if (p.act == DIFFSAL_ACT_RELU) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-        } else if (p.act == DIFFSAL_ACT_GELU_ERF) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-        } else if (p.act == DIFFSAL_ACT_SIGMOID) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = sigmoidf_(v[e]);
-        }
-        if (resid) { const float4 t = ld4(resid + o); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
+        epi_channels(v, p.bias, p.scale, p.shift, rv_row, n);
+        epi_act(v, p.act);
+        if (resid) epi_add(v, ld4(resid + o));
         st4(outp + o, make_float4(v[0], v[1], v[2], v[3]));
       }
     }

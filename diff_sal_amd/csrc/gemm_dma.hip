@@ -395,7 +395,9 @@ __global__ __launch_bounds__(256, OCC) void gemm_dma_kernel(std::conditional_t<G
     }
   };
   // act_c: the activation as a compile-time constant (one straight-line copy of the loop per activation, chosen by ONE scalar
-  // branch per tile: with the choice inside the loop every 16 x 16 block re-tested it)
+  // branch per tile: with the choice inside the loop every 16 x 16 block re-tested it).  The terms are spelled out here, not taken
+  // from common.h's epi_* pieces: any call in this lambda moves the register allocation, and the 192 x 192 tile of 16-bit storage
+  // then spills 52 bytes instead of 16.
   auto epilogue = [&](auto act_c) __attribute__((always_inline)) {
     constexpr int ACT = decltype(act_c)::value;
     int tmi, tni;
@@ -635,22 +637,13 @@ __global__ __launch_bounds__(256) void gemm_dma_reduce_kernel(DmaGemmArgs p) {
     float v[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float x = v[e];
-      if (p.bias) x += p.bias[n + e];
-      if (p.scale) x = x * p.scale[n + e] + p.shift[n + e];
-      if (p.rowvec) x += p.rowvec[(m / p.rows_per_img) * p.rowvec_ld + n + e];
-      if (p.act == DIFFSAL_ACT_RELU) x = fmaxf(x, 0.f);
-      else if (p.act == DIFFSAL_ACT_GELU_ERF) x = gelu_erf(x);
-      else if (p.act == DIFFSAL_ACT_SIGMOID) x = sigmoidf_(x);
-      v[e] = x;
+      float x[1] = {v[e]};
+      epi_channels(x, p.bias, p.scale, p.shift, p.rowvec, [&] { return (m / p.rows_per_img) * p.rowvec_ld; }, n + e);
+      epi_act(x, p.act);
+      v[e] = x[0];
     }
-    if (p.act == DIFFSAL_ACT_GELU_GRAD) {
-      const float4 t = ld4(resid + o);
-      v[0] *= gelu_erf_grad(t.x); v[1] *= gelu_erf_grad(t.y); v[2] *= gelu_erf_grad(t.z); v[3] *= gelu_erf_grad(t.w);
-    } else if (resid) {
-      const float4 t = ld4(resid + o);
-      v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w;
-    }
+    if (p.act == DIFFSAL_ACT_GELU_GRAD) epi_gelu_grad(v, ld4(resid + o));
+    else if (resid) epi_add(v, ld4(resid + o));
     st4(outp + o, make_float4(v[0], v[1], v[2], v[3]));
   }
 }

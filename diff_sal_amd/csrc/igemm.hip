@@ -463,17 +463,13 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs p) {
           const int n = n0 + (wn * TN + j) * 32 + (r & 3) + 8 * (r >> 2) + hq;
           if (n >= p.Cout) continue;
           const long o = static_cast<long>(m) * p.Cout + n;
-          float v = acc[i][j][r];
-          if (part) { part[o] = v; continue; }
-          if (p.bias) v += p.bias[n];
-          if (p.scale) v = v * p.scale[n] + (p.shift ? p.shift[n] : 0.f);
-          if (rowv) v += rowv[static_cast<long>(img) * p.rowvec_ld + n];
-          if (p.act == DIFFSAL_ACT_RELU) v = fmaxf(v, 0.f);
-          else if (p.act == DIFFSAL_ACT_GELU_ERF) v = gelu_erf(v);
-          else if (p.act == DIFFSAL_ACT_SIGMOID) v = sigmoidf_(v);
-          if (p.act == DIFFSAL_ACT_GELU_GRAD) v *= gelu_erf_grad(resid[o]);
-          else if (resid) v += resid[o];
-          outp[o] = v;
+          float v[1] = {acc[i][j][r]};
+          if (part) { part[o] = v[0]; continue; }
+          epi_channels(v, p.bias, p.scale, p.shift, rowv, [&] { return static_cast<long>(img) * p.rowvec_ld; }, n);
+          epi_act(v, p.act);
+          if (p.act == DIFFSAL_ACT_GELU_GRAD) v[0] *= gelu_erf_grad(resid[o]);
+          else if (resid) v[0] += resid[o];
+          outp[o] = v[0];
         }
       }
     }
@@ -510,30 +506,10 @@ __global__ __launch_bounds__(256) void igemm_kernel(IgemmArgs p) {
       const long o = static_cast<long>(m) * p.Cout + n;
       if (part) { st4(part + o, a4); continue; }
       float v[4] = {a4.x, a4.y, a4.z, a4.w};
-      if (p.bias) { const float4 t = ld4(p.bias + n); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
-      if (p.scale) {
-        const float4 sc = ld4(p.scale + n);
-        const float4 sh = p.shift ? ld4(p.shift + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-        v[0] = v[0] * sc.x + sh.x; v[1] = v[1] * sc.y + sh.y; v[2] = v[2] * sc.z + sh.z; v[3] = v[3] * sc.w + sh.w;
-      }
-      if (rowv) {
-        const float4 t = ld4(rowv + static_cast<long>(m / HoWo) * p.rowvec_ld + n);
-        v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w;
-      }
-      if (p.act == DIFFSAL_ACT_RELU) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-      } else if (p.act == DIFFSAL_ACT_GELU_ERF) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-      } else if (p.act == DIFFSAL_ACT_SIGMOID) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = sigmoidf_(v[e]);
-      }
-      if (p.act == DIFFSAL_ACT_GELU_GRAD) {
-        const float4 t = ld4(resid + o);
-        v[0] *= gelu_erf_grad(t.x); v[1] *= gelu_erf_grad(t.y); v[2] *= gelu_erf_grad(t.z); v[3] *= gelu_erf_grad(t.w);
-      } else if (resid) { const float4 t = ld4(resid + o); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
+      epi_channels(v, p.bias, p.scale, p.shift, rowv, [&] { return static_cast<long>(m / HoWo) * p.rowvec_ld; }, n);
+      epi_act(v, p.act);
+      if (p.act == DIFFSAL_ACT_GELU_GRAD) epi_gelu_grad(v, ld4(resid + o));
+      else if (resid) epi_add(v, ld4(resid + o));
       st4(outp + o, make_float4(v[0], v[1], v[2], v[3]));
     }
     if (ps + 1 < NPASS) __syncthreads();
@@ -694,30 +670,10 @@ __global__ __launch_bounds__(256, (TM * TN <= 4 ? 2 : 1)) void igemm_linear_kern
           acc[i][j][4 * g] = 0.f; acc[i][j][4 * g + 1] = 0.f; acc[i][j][4 * g + 2] = 0.f; acc[i][j][4 * g + 3] = 0.f;
           if (m >= p.M || n >= p.Cout) continue;
           const long o = static_cast<long>(m) * p.Cout + n;
-          if (p.bias) { const float4 t = ld4(p.bias + n); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
-          if (p.scale) {
-            const float4 sc = ld4(p.scale + n);
-            const float4 sh = p.shift ? ld4(p.shift + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-            v[0] = v[0] * sc.x + sh.x; v[1] = v[1] * sc.y + sh.y; v[2] = v[2] * sc.z + sh.z; v[3] = v[3] * sc.w + sh.w;
-          }
-          if (p.rowvec) {
-            const float4 t = ld4(p.rowvec + static_cast<long>(m / (p.Ho * p.Wo)) * p.rowvec_ld + n);
-            v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w;
-          }
-          if (p.act == DIFFSAL_ACT_RELU) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-          } else if (p.act == DIFFSAL_ACT_GELU_ERF) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-          } else if (p.act == DIFFSAL_ACT_SIGMOID) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = sigmoidf_(v[e]);
-          }
-          if (p.act == DIFFSAL_ACT_GELU_GRAD) {
-            const float4 t = rres[i][j][g];
-            v[0] *= gelu_erf_grad(t.x); v[1] *= gelu_erf_grad(t.y); v[2] *= gelu_erf_grad(t.z); v[3] *= gelu_erf_grad(t.w);
-          } else if (resid) { const float4 t = rres[i][j][g]; v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
+          epi_channels(v, p.bias, p.scale, p.shift, p.rowvec, [&] { return static_cast<long>(m / (p.Ho * p.Wo)) * p.rowvec_ld; }, n);
+          epi_act(v, p.act);
+          if (p.act == DIFFSAL_ACT_GELU_GRAD) epi_gelu_grad(v, rres[i][j][g]);
+          else if (resid) epi_add(v, rres[i][j][g]);
           st4(outp + o, make_float4(v[0], v[1], v[2], v[3]));
         }
       }
@@ -803,16 +759,12 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(IgemmArgs p) {
     float v[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float x = v[j];
-      if (p.bias) x += p.bias[n + j];
-      if (p.scale) x = x * p.scale[n + j] + p.shift[n + j];
-      if (p.rowvec) x += p.rowvec[(m / HoWo) * p.rowvec_ld + n + j];
-      if (p.act == DIFFSAL_ACT_RELU) x = fmaxf(x, 0.f);
-      else if (p.act == DIFFSAL_ACT_GELU_ERF) x = gelu_erf(x);
-      else if (p.act == DIFFSAL_ACT_SIGMOID) x = sigmoidf_(x);
-      if (p.act == DIFFSAL_ACT_GELU_GRAD) x *= gelu_erf_grad(p.residual[o + j]);
-      else if (p.residual) x += p.residual[o + j];
-      v[j] = x;
+      float x[1] = {v[j]};
+      epi_channels(x, p.bias, p.scale, p.shift, p.rowvec, [&] { return (m / HoWo) * p.rowvec_ld; }, n + j);
+      epi_act(x, p.act);
+      if (p.act == DIFFSAL_ACT_GELU_GRAD) x[0] *= gelu_erf_grad(p.residual[o + j]);
+      else if (p.residual) x[0] += p.residual[o + j];
+      v[j] = x[0];
     }
     st4(p.out + o, make_float4(v[0], v[1], v[2], v[3]));
   }

@@ -263,16 +263,12 @@ __global__ __launch_bounds__(256) void igemm16_kernel(Igemm16Args<T> p) {
           const int n = n0 + (wn * TN + j) * 32 + (r & 3) + 8 * (r >> 2) + hq;
           if (n >= p.Cout) continue;
           const long o = static_cast<long>(m) * p.Cout + n;
-          float v = acc[i][j][r];
-          if (part) { part[o] = v; continue; }
-          if (p.bias) v += p.bias[n];
-          if (p.scale) v = v * p.scale[n] + (p.shift ? p.shift[n] : 0.f);
-          if (rowv) v += rowv[static_cast<long>(img) * p.rowvec_ld + n];
-          if (p.act == DIFFSAL_ACT_RELU) v = fmaxf(v, 0.f);
-          else if (p.act == DIFFSAL_ACT_GELU_ERF) v = gelu_erf(v);
-          else if (p.act == DIFFSAL_ACT_SIGMOID) v = sigmoidf_(v);
-          if (resid) v += static_cast<float>(resid[o]);
-          outp[o] = static_cast<T>(v);
+          float v[1] = {acc[i][j][r]};
+          if (part) { part[o] = v[0]; continue; }
+          epi_channels(v, p.bias, p.scale, p.shift, rowv, [&] { return static_cast<long>(img) * p.rowvec_ld; }, n);
+          epi_act(v, p.act);
+          if (resid) v[0] += static_cast<float>(resid[o]);
+          outp[o] = static_cast<T>(v[0]);
         }
       }
     }
@@ -295,24 +291,9 @@ __global__ __launch_bounds__(256) void igemm16_kernel(Igemm16Args<T> p) {
         const long o = static_cast<long>(m) * p.Cout + n;
         float v[4] = {acc[i][j][4 * g], acc[i][j][4 * g + 1], acc[i][j][4 * g + 2], acc[i][j][4 * g + 3]};
         if (part) { st4(part + o, make_float4(v[0], v[1], v[2], v[3])); continue; }
-        if (p.bias) { const float4 t = ld4(p.bias + n); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
-        if (p.scale) {
-          const float4 sc = ld4(p.scale + n);
-          const float4 sh = p.shift ? ld4(p.shift + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-          v[0] = v[0] * sc.x + sh.x; v[1] = v[1] * sc.y + sh.y; v[2] = v[2] * sc.z + sh.z; v[3] = v[3] * sc.w + sh.w;
-        }
-        if (rv_row) { const float4 t = ld4(rv_row + n); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
-        if (p.act == DIFFSAL_ACT_RELU) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-        } else if (p.act == DIFFSAL_ACT_GELU_ERF) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-        } else if (p.act == DIFFSAL_ACT_SIGMOID) {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = sigmoidf_(v[e]);
-        }
-        if (resid) { const float4 t = ld4(resid + o); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
+        epi_channels(v, p.bias, p.scale, p.shift, rv_row, n);
+        epi_act(v, p.act);
+        if (resid) epi_add(v, ld4(resid + o));
         st4(outp + o, make_float4(v[0], v[1], v[2], v[3]));
       }
     }
@@ -474,26 +455,8 @@ __global__ __launch_bounds__(256, (TM * TN <= 4 ? 2 : 1)) void igemm16_linear_ke
           acc[i][j][4 * g] = 0.f; acc[i][j][4 * g + 1] = 0.f; acc[i][j][4 * g + 2] = 0.f; acc[i][j][4 * g + 3] = 0.f;
           if (m >= p.M || n >= p.Cout) continue;
           const long o = static_cast<long>(m) * p.Cout + n;
-          if (p.bias) { const float4 t = ld4(p.bias + n); v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w; }
-          if (p.scale) {
-            const float4 sc = ld4(p.scale + n);
-            const float4 sh = p.shift ? ld4(p.shift + n) : make_float4(0.f, 0.f, 0.f, 0.f);
-            v[0] = v[0] * sc.x + sh.x; v[1] = v[1] * sc.y + sh.y; v[2] = v[2] * sc.z + sh.z; v[3] = v[3] * sc.w + sh.w;
-          }
-          if (p.rowvec) {
-            const float4 t = ld4(p.rowvec + static_cast<long>(m / (p.Ho * p.Wo)) * p.rowvec_ld + n);
-            v[0] += t.x; v[1] += t.y; v[2] += t.z; v[3] += t.w;
-          }
-          if (p.act == DIFFSAL_ACT_RELU) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = fmaxf(v[e], 0.f);
-          } else if (p.act == DIFFSAL_ACT_GELU_ERF) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = gelu_erf(v[e]);
-          } else if (p.act == DIFFSAL_ACT_SIGMOID) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = sigmoidf_(v[e]);
-          }
+          epi_channels(v, p.bias, p.scale, p.shift, p.rowvec, [&] { return static_cast<long>(m / (p.Ho * p.Wo)) * p.rowvec_ld; }, n);
+          epi_act(v, p.act);
           if (resid) {
             T rt[4];
             __builtin_memcpy(rt, &rres[i][j][g], 8);
@@ -574,14 +537,10 @@ __global__ __launch_bounds__(256) void splitk16_reduce_kernel(Igemm16Args<T> p) 
     const float rr[4] = {rs.x, rs.y, rs.z, rs.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float x = v[j];
-      if (p.bias) x += p.bias[n + j];
-      if (p.scale) x = x * p.scale[n + j] + p.shift[n + j];
-      if (p.rowvec) x += p.rowvec[(m / HoWo) * p.rowvec_ld + n + j];
-      if (p.act == DIFFSAL_ACT_RELU) x = fmaxf(x, 0.f);
-      else if (p.act == DIFFSAL_ACT_GELU_ERF) x = gelu_erf(x);
-      else if (p.act == DIFFSAL_ACT_SIGMOID) x = sigmoidf_(x);
-      v[j] = x + rr[j];
+      float x[1] = {v[j]};
+      epi_channels(x, p.bias, p.scale, p.shift, p.rowvec, [&] { return (m / HoWo) * p.rowvec_ld; }, n + j);
+      epi_act(x, p.act);
+      v[j] = x[0] + rr[j];   // a zero residual is ADDED when there is none (-0.0 becomes +0.0)
     }
     st4(p.out + o, make_float4(v[0], v[1], v[2], v[3]));
   }

@@ -122,12 +122,10 @@ __global__ __launch_bounds__(256, (TN <= 3 ? 2 : 1)) void lin_stream_kernel(LinS
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int m = tile * 32 + (r & 3) + 8 * (r >> 2) + row_h;
-        float v = acc[j][r] + bi[j];
-        if (p.act == DIFFSAL_ACT_RELU) v = fmaxf(v, 0.f);
-        else if (p.act == DIFFSAL_ACT_GELU_ERF) v = gelu_erf(v);
-        else if (p.act == DIFFSAL_ACT_SIGMOID) v = sigmoidf_(v);
-        if (HAS_RES) v += res[j][r];
-        if (m < p.M) outp[static_cast<long>(m) * N + j * 32 + col_l] = v;
+        float v[1] = {acc[j][r] + bi[j]};
+        epi_act(v, p.act);
+        if (HAS_RES) v[0] += res[j][r];
+        if (m < p.M) outp[static_cast<long>(m) * N + j * 32 + col_l] = v[0];
       }
     }
     static_assert(KH == 1 || KH == 2, "the register double buffer alternates per K half");

@@ -133,13 +133,6 @@ struct WinoArgs {
 // the 16 lanes of one ds_read_b128 pass (16 consecutive rows, same q) cover all 64 banks
 __device__ __forceinline__ int wino_slot(int f) { return f ^ ((f >> 4) & 1); }
 
-__device__ __forceinline__ float wino_act(float x, int act) {
-  if (act == DIFFSAL_ACT_RELU) return fmaxf(x, 0.f);
-  if (act == DIFFSAL_ACT_GELU_ERF) return gelu_erf(x);
-  if (act == DIFFSAL_ACT_SIGMOID) return sigmoidf_(x);
-  return x;
-}
-
 __global__ __launch_bounds__(256) void wino_gemm_kernel(WinoArgs p) {
   // two stages of [V 2048 | U 2048] float4 as TWO objects: hipcc orders an LDS read behind every LDS-DMA in flight (s_waitcnt
   // vmcnt(0) before each fragment read) unless it can see that they touch different variables
@@ -299,10 +292,11 @@ __global__ __launch_bounds__(256) void wino_gemm_kernel(WinoArgs p) {
                       rr[4] = {rw.x, rw.y, rw.z, rw.w};
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
-            float xv = v[e] + bb[e];
-            if (p.scale) xv = xv * ss[e] + hh[e];
-            xv += rr[e];
-            v[e] = wino_act(xv, p.act);
+            float xv[1] = {v[e] + bb[e]};
+            if (p.scale) xv[0] = xv[0] * ss[e] + hh[e];
+            xv[0] += rr[e];
+            epi_act(xv, p.act);
+            v[e] = xv[0];
           }
           if (p.residual) {
             const float4 rs = ld4(p.residual + o);
@@ -333,13 +327,11 @@ __global__ __launch_bounds__(256) void wino_reduce_kernel(WinoArgs p, const floa
     float v[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float xv = v[e];
-      if (p.bias) xv += p.bias[co + e];
-      if (p.scale) xv = xv * p.scale[co + e] + p.shift[co + e];
-      if (p.rowvec) xv += p.rowvec[(m / HW) * p.rowvec_ld + co + e];
-      xv = wino_act(xv, p.act);
-      if (p.residual) xv += p.residual[o + e];
-      v[e] = xv;
+      float xv[1] = {v[e]};
+      epi_channels(xv, p.bias, p.scale, p.shift, p.rowvec, [&] { return (m / HW) * p.rowvec_ld; }, co + e);
+      epi_act(xv, p.act);
+      if (p.residual) xv[0] += p.residual[o + e];
+      v[e] = xv[0];
     }
     st4(out + o, make_float4(v[0], v[1], v[2], v[3]));
   }
@@ -368,13 +360,11 @@ __global__ __launch_bounds__(256) void wino_tail_reduce_kernel(WinoArgs p, float
     float v[4] = {a.x, a.y, a.z, a.w};
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float xv = v[e];
-      if (p.bias) xv += p.bias[co + e];
-      if (p.scale) xv = xv * p.scale[co + e] + p.shift[co + e];
-      if (p.rowvec) xv += p.rowvec[static_cast<long>(n) * p.rowvec_ld + co + e];
-      xv = wino_act(xv, p.act);
-      if (p.residual) xv += p.residual[o + e];
-      v[e] = xv;
+      float xv[1] = {v[e]};
+      epi_channels(xv, p.bias, p.scale, p.shift, p.rowvec, [&] { return static_cast<long>(n) * p.rowvec_ld; }, co + e);
+      epi_act(xv, p.act);
+      if (p.residual) xv[0] += p.residual[o + e];
+      v[e] = xv[0];
     }
     st4(out + o, make_float4(v[0], v[1], v[2], v[3]));
   }

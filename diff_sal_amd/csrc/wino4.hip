@@ -277,13 +277,6 @@ struct Wino4Out {
   int groups, tiles_per_img;
 };
 
-__device__ __forceinline__ float w4_act(float x, int act) {
-  if (act == DIFFSAL_ACT_RELU) return fmaxf(x, 0.f);
-  if (act == DIFFSAL_ACT_GELU_ERF) return gelu_erf(x);
-  if (act == DIFFSAL_ACT_SIGMOID) return sigmoidf_(x);
-  return x;
-}
-
 // A^T applied to six values (rows of A^T: [1 1 1 1 1 0], [0 1 -1 2 -2 0], [0 1 1 4 4 0], [0 1 -1 8 -8 1])
 template <typename VT>
 __device__ __forceinline__ void w4_at(const VT (&m)[6], VT (&y)[4]) {
@@ -354,10 +347,11 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(Wino4Out p) {
         float v[VW];
 #pragma unroll
         for (int e = 0; e < VW; ++e) {
-          float xv = w4_get<VT>(y[b], e) + bb[e];
-          if (p.scale) xv = xv * ss[e] + hh[e];
-          xv += rr[e];
-          v[e] = w4_act(xv, p.act);
+          float xv[1] = {w4_get<VT>(y[b], e) + bb[e]};
+          if (p.scale) xv[0] = xv[0] * ss[e] + hh[e];
+          xv[0] += rr[e];
+          epi_act(xv, p.act);
+          v[e] = xv[0];
         }
         if (p.residual) {
           const VT rs = w4_ld<VT>(p.residual + o);

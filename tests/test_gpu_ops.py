@@ -566,3 +566,28 @@ def test_groupnorm_single_launch_slab_path_equals_the_two_launch_path(ops, tunin
     ref = F.silu(F.group_norm(x.permute(0, 3, 1, 2).double(), 32, g.double(), b.double(), 1e-6)).permute(0, 2, 3, 1)
     assert rel_err(one, ref) < 2e-5 and rel_err(two, ref) < 2e-5
     assert rel_err(one, two) < 3e-6
+
+
+@pytest.mark.parametrize("given", ["scale", "shift"])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16, torch.float16])
+def test_conv_igemm_refuses_scale_without_shift(dtype, given):
+    """The kernels' epilogue reads `shift` whenever `scale` is set, without a test of its own: diffsal_conv_igemm has to refuse
+    one without the other (DIFFSAL_E_ARG) on fp32 and on 16-bit storage, before anything is launched -- the output buffer
+    keeps its contents."""
+    import ctypes
+
+    from diff_sal_amd import _lib
+    N, H, W, Cin, Cout = 1, 4, 8, 64, 32
+    x = torch.ones(N, H, W, Cin, device=DEV, dtype=dtype)
+    w = torch.ones(Cout, Cin, device=DEV, dtype=dtype)
+    vec = torch.ones(Cout, device=DEV)
+    out = torch.full((N, H, W, Cout), 7.0, device=DEV, dtype=dtype)
+    dt = {torch.float32: _lib.F32, torch.bfloat16: _lib.BF16, torch.float16: _lib.F16}[dtype]
+    d = _lib.ConvDesc(N, H, W, Cin, H, W, Cout, 1, 1, 1, 1, 0, 0, 1, 1, _lib.ACT_NONE, 0, 0, _lib.PREC_FP32, dt)
+    scale, shift = (vec.data_ptr(), None) if given == "scale" else (None, vec.data_ptr())
+    lib = _lib.load()
+    rc = lib.diffsal_conv_igemm(ctypes.byref(d), x.data_ptr(), w.data_ptr(), None, scale, shift, None, None, out.data_ptr(),
+                                None, 0, torch.cuda.current_stream().cuda_stream)
+    assert rc == -4 and b"scale and shift" in lib.diffsal_last_error()
+    torch.cuda.synchronize()
+    assert torch.equal(out, torch.full_like(out, 7.0))
