@@ -1179,6 +1179,32 @@ def attention(q: Tensor, k: Tensor, v: Tensor, heads: int, scale: float) -> Tens
     return o
 
 
+def attn_fold_supported(C: int, heads: int, Lk: int, dtype: torch.dtype = torch.float32) -> bool:
+    """csrc/attn_fold.hip: fp32 storage, 2 heads, up to 32 keys per frame, C = 192 / 384 / 768."""
+    return dtype == torch.float32 and heads == 2 and 0 < Lk <= 32 and C in (192, 384, 768)
+
+
+def attn_fold(q_in: Tensor, G: Tensor, U: Tensor, kp: Tensor, ukq: Tensor, x: Tensor, bias: Tensor, heads: int,
+              scale: float) -> Tensor:
+    """Attention + proj + residual of a TransformerBlock with proj_q / proj folded onto the key side (csrc/attn_fold.hip):
+    x1 = x + bias + sum_h softmax_t(scale (q_in . G[:, t, h] + kp[:, t] . ukq[h])) U[:, t, h].  q_in, x [N, L, C]; G, U [N, Lk, 2 C]
+    (the paired product of the pooled rows kp, vp [N, Lk, C] with the folded weights of SalUNet.packed()); ukq [2, C]; bias [C]."""
+    lib = _lib.load()
+    N, L, Cc = q_in.shape
+    Lk = kp.shape[1]
+    if G.shape != (N, Lk, heads * Cc) or U.shape != G.shape or x.shape != q_in.shape or ukq.shape != (heads, Cc):
+        raise RuntimeError(f"attn_fold: inconsistent shapes q_in {tuple(q_in.shape)} G {tuple(G.shape)} U {tuple(U.shape)} "
+                           f"kp {tuple(kp.shape)} ukq {tuple(ukq.shape)} x {tuple(x.shape)}")
+    out = torch.empty_like(q_in)
+    M, R = N * L, heads * Lk
+    Rp = -(-R // 16) * 16      # score rows as issued (16-row blocks); the output product runs ceil(R / 4) K steps of 4
+    fl = 2.0 * M * Cc * Rp + 2.0 * M * Cc * (-(-R // 4) * 4) + 2.0 * N * R * Cc
+    with _prof("K10f", fl, _nb(q_in, x, out, G, U, kp, ukq, bias), f"attn_fold M={M} C={Cc}", kernel=f"attn_fold_kernel<{Cc}>"):
+        _lib.check(lib.diffsal_attn_fold(_p(q_in), _p(G), _p(U), _p(kp), _p(ukq), _p(x), _p(bias), _p(out), N, L, Lk, Cc, heads,
+                                         float(scale), _stream()), "attn_fold")
+    return out
+
+
 def head_sigmoid(x: Tensor, w: Tensor, bias: Tensor) -> Tensor:
     """x NHWC [N,H,W,C] (any storage type) -> fp32 [N,H,W,1]."""
     lib = _lib.load()

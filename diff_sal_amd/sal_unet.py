@@ -233,7 +233,7 @@ class SalUNet(nn.Module):
         return self.gemm_precision or ops.get_gemm_precision()
 
     def _cache_key(self):
-        return (self._pack_epoch, self._precision(), self.compute_dtype, self.winograd) + tuple(
+        return (self._pack_epoch, self._precision(), self.compute_dtype, self.winograd, self.fold_attn_proj) + tuple(
             (p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
 
     def pack_epoch(self):
@@ -281,6 +281,33 @@ class SalUNet(nn.Module):
     def _gemm_w(self, w: Tensor) -> Tensor:
         """Linear / 1x1 weight [N, K] as the GEMM reads it (K % 32 == 0: the packed k order is the identity)."""
         return w.detach() if self.compute_dtype == torch.float32 else ops.cast(w.detach().contiguous(), self.compute_dtype)
+
+    def _fold_attn(self, i: int, Lk: int) -> bool:
+        """Stage i takes the key-side form of its attention (ops.attn_fold): switch on, fp32 storage, exact fp32 arithmetic and a
+        shape csrc/attn_fold.hip is built for."""
+        return (self.fold_attn_proj and self.compute_dtype == torch.float32 and self._precision() == "fp32"
+                and ops.attn_fold_supported(self.up_channels[i], self.heads[i], Lk, torch.float32))
+
+    @staticmethod
+    def fold_attn_weights(a: nn.Module):
+        """(kq.w [2C, C], vp.w [2C, C], ukq [2, C], proj.bf [C]) of an attention module (proj_q, proj_k, proj_v, proj): proj_q and
+        proj re-associated onto the key side (weight-only, formed in fp64 on the device, rounded once).  Per head h
+        with channel slice s_h:  kq.w rows h C .. = (Wk[s_h]^T Wq[s_h])^T,  vp.w rows h C .. = (Wv[s_h]^T Wp[:, s_h]^T)^T, so that
+        ops.linear_pair (x @ w^T) gives G = kp Wkq_h and U = vp Wvp_h as [N Lk, 2 C];  ukq[h] = Wk[s_h]^T bq[s_h];
+        proj.bf = bp + Wp bv (the softmax rows sum to 1).  The score terms that do not depend on the key are dropped."""
+        c = a.proj_q.weight.shape[0]
+        d = c // 2
+        wq, wk, wv, wp = (l.weight.detach().double() for l in (a.proj_q, a.proj_k, a.proj_v, a.proj))
+        zero = wq.new_zeros(c)
+        bq, bv, bp = ((l.bias.detach().double() if l.bias is not None else zero) for l in (a.proj_q, a.proj_v, a.proj))
+        kq, vp, ukq = [], [], []
+        for h in range(2):
+            s = slice(h * d, (h + 1) * d)
+            kq.append(wq[s].t() @ wk[s])
+            vp.append(wp[:, s] @ wv[s])
+            ukq.append(wk[s].t() @ bq[s])
+        return (torch.cat(kq, 0).float().contiguous(), torch.cat(vp, 0).float().contiguous(),
+                torch.stack(ukq, 0).float().contiguous(), (bp + wp @ bv).float().contiguous())
 
     @staticmethod
     def _bn_affine(bn: nn.BatchNorm2d):
@@ -344,6 +371,8 @@ class SalUNet(nn.Module):
                             ("fc2", blk.mlp.fc2)):
                 pk[f"s{i}.{nm}.w"] = self._gemm_w(lin.weight)
             pk[f"s{i}.redu.w"] = self._pack_conv(dec.redu_chan_up[i].proj[0].weight)  # [Co, C, kt, 1, 1]
+            if self._fold_attn(i, 1):
+                pk[f"s{i}.kq.w"], pk[f"s{i}.vp.w"], pk[f"s{i}.ukq"], pk[f"s{i}.proj.bf"] = self.fold_attn_weights(a)
         if all(f"s{i}.align.w" in pk for i in range(self.num_stages)) and self.num_stages > 1:
             pk["align_all.w"] = torch.cat([pk[f"s{i}.align.w"] for i in range(self.num_stages)], 0).contiguous()
             pk["align_all.b"] = torch.cat([dec.mid_stages[i].blocks[0].align_conv.bias.detach().float()
@@ -508,6 +537,15 @@ class SalUNet(nn.Module):
                 kk, vv = ops.dwpool_ln_kv(k_src.view(n9, H, W, C), xn.view(n9, H, W, C), pk[f"s{i}.wk"], pk[f"s{i}.wv"],
                                           a.conv_proj_k.bn.weight, a.conv_proj_k.bn.bias, a.conv_proj_v.bn.weight,
                                           a.conv_proj_v.bn.bias, self.kernel_kv[i], a.conv_proj_k.bn.eps)
+        if self._fold_attn(i, kk.shape[1]):
+            # proj_q and proj on the key side: q, k, v and o are never formed.  [G | U = the pooled rows times the folded weights, one
+            # paired launch with N = 2 C] [scores, softmax, P U + bias + residual on the matrix cores, one launch]
+            Gk, Uv = ops.linear_pair(kk, vv, pk[f"s{i}.kq.w"], pk[f"s{i}.vp.w"], None, None)
+            x1 = ops.attn_fold(q, Gk, Uv, kk, pk[f"s{i}.ukq"], xt, pk[f"s{i}.proj.bf"], self.heads[i], float(C) ** -0.5)
+            y = ops.layernorm(x1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
+            y = ops.linear(y, pk[f"s{i}.fc1.w"], blk.mlp.fc1.bias, act=ACT_GELU)
+            x2 = ops.linear(y, pk[f"s{i}.fc2.w"], blk.mlp.fc2.bias, residual=x1)
+            return x2.view(B, T, H, W, C), None
         if (self.group_qkv and self.compute_dtype == torch.float32 and ops.get_gemm_precision() == "fp32"
                 and not getattr(pk[f"s{i}.k.w"], "_diffsal_split", False) and C % 96 == 0
                 and (self.group_qkv_all or -(-(q.numel() // C) // 96) * (C // 96) <= 256)):
@@ -587,6 +625,10 @@ class SalUNet(nn.Module):
     # the pooled launch + the paired projection GEMM at stage 3 (every one of the 648 workgroups re-reads both weight matrices
     # from L2), 43 against 30 us at C = 192: off.
     fold_kv_proj = False
+    # fp32 stages with C = 192 / 384 / 768 (stages 0-2): proj_q and proj re-associated onto the 2 x Lk pooled keys of a frame
+    # (ops.attn_fold, csrc/attn_fold.hip): per token two [. x 2 Lk] contractions instead of two dense C x C products; exact algebra,
+    # another summation order.  Off: the grouped / paired projections, ops.attention and the proj GEMM
+    fold_attn_proj = True
     # fp32 3x3 stride-1 convolutions (ResnetBlock conv1 / conv2, UpEmbed's second convolution) as Winograd F(2x2, 3x3) where the
     # library's planner expects a gain (csrc/wino.hip; ~1e-6 relative transform rounding).  Off: always the direct kernel
     winograd = True

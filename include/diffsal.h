@@ -545,6 +545,18 @@ int diffsal_block16(const void* o, const void* x, const void* wp, const float* b
 int diffsal_attention(const void* q, const void* k, const void* v, void* o, int N, int Lq, int Lk,
                       int C, int heads, float scale, int dtype, diffsal_stream_t stream);
 
+/* ---- attention with proj_q and proj folded onto the key side (fp32, 2 heads; csrc/attn_fold.hip) ---------------------------
+ * R/models/saliency_decoder/attention.py:86-113, transformer.py:150-152, re-associated (exact algebra, another summation order):
+ *   S_h[l,t] = scale * (q_in[n,l,:] . G[n,t,h,:] + kp[n,t,:] . ukq[h,:]);  P_h = softmax_t(S_h);
+ *   out[n,l,:] = x[n,l,:] + bias + sum_h sum_t P_h[l,t] U[n,t,h,:]
+ * with G = kp Wkq_h, U = vp Wvp_h [N, Lk, 2, C] (the caller's paired GEMM on the pooled, LayerNorm-ed key / value rows kp, vp
+ * [N, Lk, C]), ukq [2, C] and bias = bp + Wp bv [C] weight-only folds.  q_in, x, out [N, L, C].  The score terms that are the same
+ * for every key of a head are left out (softmax is shift-invariant).  heads = 2, 1 <= Lk <= 32, C in {192, 384, 768}, any L >= 1.
+ * Deterministic: no atomics, one summation order per token whatever N, L or the grid. */
+int diffsal_attn_fold(const float* q_in, const float* G, const float* U, const float* kp, const float* ukq, const float* x,
+                      const float* bias, float* out, int N, int L, int Lk, int C, int heads, float scale,
+                      diffsal_stream_t stream);
+
 /* ---- K14 tail: 1x1 conv C->1 + sigmoid on NHWC -> [N,H,W] --------------------------------
  * R/.../common_block.py:111-122. */
 int diffsal_head_sigmoid(const void* x, const float* w /*[C]*/, const float* bias /*[1]*/, float* out /*fp32*/,
