@@ -34,7 +34,7 @@ class Wino4Ext(C.Structure):
 
 # must equal diffsal_version() of the loaded binary: bumped whenever a signature or struct in include/diffsal.h changes,
 # so that a stale libdiffsal_hip.so is rejected instead of being called with the wrong argument lists
-ABI_VERSION = 43
+ABI_VERSION = 44
 
 
 SIGNATURES = {
@@ -45,6 +45,7 @@ SIGNATURES = {
     "diffsal_kv_prep_proj": (c_i, [c_f] * 14 + [c_i, c_i, c_i, c_i, c_i, c_fl, c_f, c_f, c_fl, c_i, c_i, c_f]),
     "diffsal_block_front": (c_i, [c_f, c_f, c_f, c_f, c_f, c_fl, c_f, c_f, c_f, c_fl, c_f, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i,
                                   c_i, c_i, c_fl, c_i, c_f]),
+    "diffsal_block_front_fold": (c_i, [c_f] * 7 + [c_fl] + [c_f] * 3 + [c_fl, c_f, c_f] + [c_i] * 6 + [c_fl, c_f]),
     "diffsal_set_tuning": (c_i, [C.c_char_p, c_i]),
     "diffsal_get_tuning": (c_i, [C.c_char_p]),
     "diffsal_temb_mlp": (c_i, [c_f, c_i, c_i, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f]),

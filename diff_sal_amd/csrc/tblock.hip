@@ -590,6 +590,400 @@ static int launch_front(const FrontArgs<T>& a, hipStream_t s) {
   return check_launch("block_front");
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// fp32 storage, C = 96: the same block half with proj_q and proj folded onto the key side (SalUNet.fold_attn_weights,
+// tools/attn_fold_algebra.py; csrc/attn_fold.hip is the form of the coarser stages):
+//
+//     S_h = scale (q_in G_h^T + s0_h),  G_h = kp Wkq_h [Lk x C],  s0_h[j] = kp[j] . ukq_h
+//     x1  = x + bp' + sum_h softmax(S_h) U_h,  U_h = vp Wvp_h [Lk x C]
+//
+// G and U are the paired product of the frame's pooled rows with the folded weights ([N, Lk, 2 C], head-major columns).  Phases A
+// and B are those of block_front_kernel<float, 96>.  Phase C parks G (rows = head * 32 + key) and U^T (rows = channels, columns =
+// head * 32 + key) where the halo tile was, and forms s0.  Phase D: S^T = G_h q_in^T per head with the contraction over all 96
+// channels, seeded with s0; the softmax goes down the registers as above; X1^T = sum_h U_h^T P_h^T seeded with the folded bias.
+// Per wavefront and tile that is 96 + 72 v_mfma_f32_32x32x2_f32 at Lk = 18 against 384; q, k, v and o never exist and no 96 x 96
+// weight is read, so the workgroup keeps 78.4 KB of LDS and two of them share a CU.
+// AHEAD (DIFFSAL_FRONT_FOLD_WGS = 1, an A/B aid): one workgroup per CU with the next tile's halo pieces fetched a tile ahead (512
+// registers); else, as shipped, two per CU (256).
+struct FrontFoldArgs {
+  const float* x;        // [N, H, W, C]
+  const float* G;        // [N, Lk, 2 C]
+  const float* U;        // [N, Lk, 2 C]
+  const float* kp;       // [N, Lk, C] pooled key rows
+  const float* ukq;      // [2][C]
+  const float* g1; const float* b1;      // LayerNorm_1
+  const float* w9;       // [9][C] depthwise taps, tap = 3 * ky + kx
+  const float* gq; const float* bq;      // LayerNorm_q
+  const float* bias;     // [C] folded output bias
+  float* out;            // x1
+  int N, H, W, Lk;
+  float eps1, epsq, scale;
+  int tiles_y, tiles_x;
+#ifdef DIFFSAL_DEV_STAMPS
+  unsigned long long* stamps;
+#endif
+};
+
+struct FrontFoldLds {
+  static constexpr int C = 96;
+  static constexpr int PW = C + 4;                         // G row pitch and halo-tile token pitch
+  static constexpr int PU = 68;                            // U^T row pitch (2 x 32 key columns + pad)
+  static constexpr int vec_floats = 9 * C + 3 * C + 2 * C + 2 * C + 64;      // w9 | gq | bq | bias | ukq | g1 | b1 | s0
+  static constexpr size_t vec_bytes = static_cast<size_t>(vec_floats) * sizeof(float);
+  static constexpr size_t tile_bytes = static_cast<size_t>(FT_TOK) * PW * sizeof(float);
+  static constexpr size_t gu_bytes = (static_cast<size_t>(64) * PW + static_cast<size_t>(C) * PU) * sizeof(float);
+  static constexpr size_t region_bytes = ((tile_bytes > gu_bytes ? tile_bytes : gu_bytes) + 15) / 16 * 16;
+  static constexpr size_t total = vec_bytes + region_bytes;
+};
+static_assert(2 * FrontFoldLds::total <= 160 * 1024, "two workgroups of the folded front share a CU's LDS");
+
+template <bool AHEAD>
+__global__ __launch_bounds__(256, (AHEAD ? 1 : 2)) void block_front_fold_kernel(FrontFoldArgs p) {
+  // only the fmaf calls written below are fused: the two instantiations then round every value alike (left to the compiler's
+  // contraction they differed in the last bit), so the choice between them never shows in a result
+#pragma clang fp contract(off)
+  typedef FrontFoldLds L;
+  constexpr int C = L::C, PW = L::PW, PX = L::PW, PU = L::PU;
+  constexpr int NU = C / 32, NG = C / 8, HEADS = 2, NP = C / 4, G = NP / 3;
+
+  extern __shared__ __attribute__((aligned(16))) unsigned char smraw[];
+  float* vecs = reinterpret_cast<float*>(smraw);                 // w9 [9][C] | gq | bq | bias | ukq [2][C] | g1 | b1 | s0 [2][32]
+  float* ukqs = vecs + 12 * C;
+  float* ln1s = vecs + 14 * C;
+  float* s0s = vecs + 16 * C;
+  float* region = reinterpret_cast<float*>(smraw + L::vec_bytes);
+  float* xns = region;                                           // phase A/B: [FT_TOK][PX]
+  float* Gs = region;                                            // phase C/D: [2 * 32][PW]
+  float* Uts = region + 64 * PW;                                 //            [C][PU]
+
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int ml = lane & 31, hf = lane >> 5;
+
+  for (int i = tid; i < 9 * C; i += 256) vecs[i] = p.w9[i];
+  for (int i = tid; i < C; i += 256) {
+    vecs[9 * C + i] = p.gq[i]; vecs[10 * C + i] = p.bq[i]; vecs[11 * C + i] = p.bias[i];
+    ukqs[i] = p.ukq[i]; ukqs[C + i] = p.ukq[C + i];
+    ln1s[i] = p.g1[i]; ln1s[C + i] = p.b1[i];
+  }
+  const int a_slot = tid / G, a_sub = tid - a_slot * G;
+  // LayerNorm_1's affine: in registers beside the look-ahead (512 of them), else read from LDS per pass
+  float4 ga[3], ba[3];
+  if constexpr (AHEAD) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { ga[i] = ld4(p.g1 + 4 * (a_sub + G * i)); ba[i] = ld4(p.b1 + 4 * (a_sub + G * i)); }
+  }
+  __syncthreads();
+
+  const int n_tiles = p.N * p.tiles_y * p.tiles_x;
+  const int trow = 2 * wave + (ml >> 4), tcol = ml & 15;
+  const int centre = (trow + 1) * FT_HW + (tcol + 1);
+  const float* gf = Gs + ml * PW + 4 * hf;
+  const float* uf = Uts + ml * PU + 4 * hf;
+
+  // The per-thread piece offsets of phases A and C do not change from tile to tile; hoisted out of the tile loop they are ~60
+  // registers that the two-workgroup form does not have (they went to scratch).  An opaque copy of the thread index per phase
+  // makes them cheap integer work of that phase instead
+  auto opaque = [](int v) { asm volatile("" : "+v"(v)); return v; };
+
+  // phase A's global loads (see block_front_kernel): all passes a tile ahead (AHEAD) or all at the top of phase A
+  constexpr int TPP = 256 / G;
+  constexpr int NPASS = (FT_TOK + TPP - 1) / TPP;
+  float4 pre[NPASS][3];
+  unsigned inside_mask = 0;
+  auto fetch_tile = [&](int tile_) -> unsigned {
+    const int tx_ = tile_ % p.tiles_x, t2_ = tile_ / p.tiles_x;
+    const int ty_ = t2_ % p.tiles_y, n_ = t2_ / p.tiles_y;
+    const float* ximg_ = p.x + static_cast<long>(n_) * p.H * p.W * C;
+    unsigned mask = 0;
+    const int t_ = opaque(tid), slot_ = t_ / G, sub_ = t_ - slot_ * G;
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps) {
+      const int tok = ps * TPP + slot_;
+      const int hy = tok / FT_HW, hx = tok - hy * FT_HW;
+      const int gy = ty_ * FT_TH + hy - 1, gx = tx_ * FT_TW + hx - 1;
+      const bool inside = tok < FT_TOK && gy >= 0 && gy < p.H && gx >= 0 && gx < p.W;
+      const float* src = ximg_ + (static_cast<long>(inside ? gy : 0) * p.W + (inside ? gx : 0)) * C;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) pre[ps][i] = ld4(src + 4 * (sub_ + G * i));
+      mask |= (inside ? 1u : 0u) << ps;
+    }
+    return mask;
+  };
+  const bool xcd_walk = (n_tiles & 7) == 0 && (gridDim.x & 7) == 0;
+  auto tile_of = [&](int v) { return xcd_walk ? (v & 7) * (n_tiles >> 3) + (v >> 3) : v; };
+  if (AHEAD && static_cast<int>(blockIdx.x) < n_tiles) inside_mask = fetch_tile(tile_of(blockIdx.x));
+
+#ifdef DIFFSAL_DEV_STAMPS
+  int stamp_it = 0;
+  auto stamp = [&](int k) {
+    if (p.stamps && tid == 0 && stamp_it < 8) p.stamps[(static_cast<long>(blockIdx.x) * 8 + stamp_it) * 8 + k] = wall_clock64();
+  };
+#else
+  auto stamp = [](int) {};
+#endif
+  for (int vt = blockIdx.x; vt < n_tiles; vt += gridDim.x) {
+    const int tile = tile_of(vt);
+    stamp(0);
+    const int tx = tile % p.tiles_x, t2 = tile / p.tiles_x;
+    const int ty = t2 % p.tiles_y, n = t2 / p.tiles_y;
+    const int y0 = ty * FT_TH, x0 = tx * FT_TW;
+    if constexpr (!AHEAD) inside_mask = fetch_tile(tile);
+
+    // ---------------- phase A: halo tile -> LayerNorm_1 -> LDS; zeros outside the frame are the convolution's padding
+#pragma unroll
+    for (int ps = 0; ps < NPASS; ++ps) {
+      const int tok = ps * TPP + a_slot;
+      const bool inside = (inside_mask >> ps) & 1u;
+      float4 vv[3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i) vv[i] = pre[ps][i];
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) s += (vv[i].x + vv[i].y) + (vv[i].z + vv[i].w);
+      s = group_sum<G>(s);
+      const float mean = s * (1.0f / C);
+      float qq = 0.f;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const float a = vv[i].x - mean, b = vv[i].y - mean, c = vv[i].z - mean, d = vv[i].w - mean;
+        qq += (a * a + b * b) + (c * c + d * d);
+      }
+      qq = group_sum<G>(qq);
+      const float rstd = 1.0f / sqrtf(qq * (1.0f / C) + p.eps1);
+      if (tok < FT_TOK) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+          if constexpr (!AHEAD) { ga[i] = ld4(ln1s + 4 * (a_sub + G * i)); ba[i] = ld4(ln1s + C + 4 * (a_sub + G * i)); }
+          float4 o;
+          o.x = inside ? (vv[i].x - mean) * rstd * ga[i].x + ba[i].x : 0.f;
+          o.y = inside ? (vv[i].y - mean) * rstd * ga[i].y + ba[i].y : 0.f;
+          o.z = inside ? (vv[i].z - mean) * rstd * ga[i].z + ba[i].z : 0.f;
+          o.w = inside ? (vv[i].w - mean) * rstd * ga[i].w + ba[i].w : 0.f;
+          st4(xns + tok * PX + 4 * (a_sub + G * i), o);
+        }
+      }
+    }
+    __syncthreads();
+    stamp(1);
+    // this frame's G / U pieces and pooled key rows: in flight during phase B, parked in LDS in phase C.  G piece pc = row * NP +
+    // piece (a wave writes whole rows); U piece pc = piece * 64 + row (a wave writes 64 consecutive columns of a U^T row)
+    constexpr int NGP = 64 * NP / 256;
+    float4 graw[NGP], uraw[NGP], kraw[3];
+    auto fetch_u = [&]() {
+      const float* usrc = p.U + static_cast<long>(n) * p.Lk * 2 * C;
+      const int t_ = opaque(tid);
+#pragma unroll
+      for (int i = 0; i < NGP; ++i) {
+        const int pc = t_ + 256 * i;
+        const int ru = pc & 63, ju = ru & 31;
+        uraw[i] = ld4(usrc + (ju < p.Lk ? ju : 0) * 2 * C + (ru >> 5) * C + 4 * (pc >> 6));
+      }
+    };
+    {
+      const float* gsrc = p.G + static_cast<long>(n) * p.Lk * 2 * C;
+      const int t_ = opaque(tid);
+#pragma unroll
+      for (int i = 0; i < NGP; ++i) {
+        const int pc = t_ + 256 * i;
+        const int rg = pc / NP, jg = rg & 31;
+        graw[i] = ld4(gsrc + (jg < p.Lk ? jg : 0) * 2 * C + (rg >> 5) * C + 4 * (pc - rg * NP));
+      }
+      const int key = t_ >> 3;                                        // eight lanes per key, three pieces each
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+        kraw[i] = ld4(p.kp + (static_cast<long>(n) * p.Lk + (key < p.Lk ? key : 0)) * C + 4 * ((t_ & 7) + 8 * i));
+    }
+    // 256 registers: the U pieces are requested behind the tap loop instead (its two operand buffers are dead there)
+    if constexpr (AHEAD) fetch_u();
+
+    // ---------------- phase B: depthwise 3x3 + LayerNorm_q of this lane's token, channel groups 8 g + 4 hf
+    float4 qin[NG];
+#pragma unroll
+    for (int g = 0; g < NG; ++g) qin[g] = make_float4(0.f, 0.f, 0.f, 0.f);
+    {
+      constexpr int HG = 6, SPT = NG / HG, NSTEP = 9 * SPT;
+      float4 xa[2][HG], wa[2][HG];
+      auto issue = [&](int step, float4 (&xd)[HG], float4 (&wd)[HG]) {
+        const int tap = step / SPT, g0 = (step % SPT) * HG;
+        const int off = (tap / 3 - 1) * FT_HW + (tap % 3 - 1);
+        const float* xs = xns + (centre + off) * PX + 4 * hf + 8 * g0;
+        const float* ws = vecs + tap * C + 4 * hf + 8 * g0;
+#pragma unroll
+        for (int g = 0; g < HG; ++g) { xd[g] = ld4(xs + 8 * g); wd[g] = ld4(ws + 8 * g); }
+      };
+      issue(0, xa[0], wa[0]);
+#pragma unroll
+      for (int step = 0; step < NSTEP; ++step) {
+        if (step + 1 < NSTEP) issue(step + 1, xa[(step + 1) & 1], wa[(step + 1) & 1]);
+        __builtin_amdgcn_sched_barrier(0);
+        const int g0 = (step % SPT) * HG;
+#pragma unroll
+        for (int g = 0; g < HG; ++g) {
+          const float4 a = xa[step & 1][g], w = wa[step & 1][g];
+          qin[g0 + g].x = fmaf(a.x, w.x, qin[g0 + g].x); qin[g0 + g].y = fmaf(a.y, w.y, qin[g0 + g].y);
+          qin[g0 + g].z = fmaf(a.z, w.z, qin[g0 + g].z); qin[g0 + g].w = fmaf(a.w, w.w, qin[g0 + g].w);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    if constexpr (!AHEAD) fetch_u();
+    {
+      float s = 0.f;
+#pragma unroll
+      for (int g = 0; g < NG; ++g) s += (qin[g].x + qin[g].y) + (qin[g].z + qin[g].w);
+      s += lane_xor32(s);
+      const float mean = s * (1.0f / C);
+      float qq = 0.f;
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const float a = qin[g].x - mean, b = qin[g].y - mean, c = qin[g].z - mean, d = qin[g].w - mean;
+        qq += (a * a + b * b) + (c * c + d * d);
+      }
+      qq += lane_xor32(qq);
+      const float rstd = 1.0f / sqrtf(qq * (1.0f / C) + p.epsq);
+#pragma unroll
+      for (int g = 0; g < NG; ++g) {
+        const float4 gm = ld4(vecs + 9 * C + 8 * g + 4 * hf), bt = ld4(vecs + 10 * C + 8 * g + 4 * hf);
+        qin[g].x = (qin[g].x - mean) * rstd * gm.x + bt.x; qin[g].y = (qin[g].y - mean) * rstd * gm.y + bt.y;
+        qin[g].z = (qin[g].z - mean) * rstd * gm.z + bt.z; qin[g].w = (qin[g].w - mean) * rstd * gm.w + bt.w;
+      }
+    }
+    __syncthreads();                                                  // every wave is done with the halo tile
+    stamp(2);
+
+    // ---------------- phase C: G (rows = head, key) and U^T (rows = channels) of this frame replace it; pads are zero.
+    // s0[h][key] = kp[key] . ukq[h] in a fixed order (eight lanes of twelve channels, then the lane tree)
+    const int tc = opaque(tid);
+#pragma unroll
+    for (int i = 0; i < NGP; ++i) {
+      const int pc = tc + 256 * i;
+      const int rg = pc / NP;
+      st4(Gs + rg * PW + 4 * (pc - rg * NP), (rg & 31) < p.Lk ? graw[i] : make_float4(0.f, 0.f, 0.f, 0.f));
+      const int ru = pc & 63, c4 = 4 * (pc >> 6);
+      const bool oku = (ru & 31) < p.Lk;
+      Uts[(c4 + 0) * PU + ru] = oku ? uraw[i].x : 0.f;
+      Uts[(c4 + 1) * PU + ru] = oku ? uraw[i].y : 0.f;
+      Uts[(c4 + 2) * PU + ru] = oku ? uraw[i].z : 0.f;
+      Uts[(c4 + 3) * PU + ru] = oku ? uraw[i].w : 0.f;
+    }
+    {
+      float d0 = 0.f, d1 = 0.f;
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const float4 u0 = ld4(ukqs + 4 * ((tc & 7) + 8 * i)), u1 = ld4(ukqs + C + 4 * ((tc & 7) + 8 * i));
+        d0 = fmaf(kraw[i].x, u0.x, d0); d0 = fmaf(kraw[i].y, u0.y, d0); d0 = fmaf(kraw[i].z, u0.z, d0); d0 = fmaf(kraw[i].w, u0.w, d0);
+        d1 = fmaf(kraw[i].x, u1.x, d1); d1 = fmaf(kraw[i].y, u1.y, d1); d1 = fmaf(kraw[i].z, u1.z, d1); d1 = fmaf(kraw[i].w, u1.w, d1);
+      }
+      d0 = group_sum<8>(d0);
+      d1 = group_sum<8>(d1);
+      const int key = tc >> 3;
+      if ((tc & 7) == 0) {
+        s0s[key] = key < p.Lk ? d0 : 0.f;
+        s0s[32 + key] = key < p.Lk ? d1 : 0.f;
+      }
+    }
+    __syncthreads();
+    stamp(3);
+    if (AHEAD && vt + static_cast<int>(gridDim.x) < n_tiles) inside_mask = fetch_tile(tile_of(vt + gridDim.x));
+
+    // the residual pieces: L2 hits (the halo tile came from there), in flight during the score product
+    const int gy = y0 + trow, gx = x0 + tcol;
+    const bool live = gy < p.H && gx < p.W;
+    const long tokoff = ((static_cast<long>(n) * p.H + (live ? gy : 0)) * p.W + (live ? gx : 0)) * C + 4 * hf;
+    float4 xres[NU * 4];
+#pragma unroll
+    for (int i = 0; i < NU * 4; ++i) xres[i] = ld4(p.x + tokoff + 8 * i);
+
+    // ---------------- phase D (per wave, transposed): S^T = G_h q_in^T + s0_h (rows = keys), softmax over the keys, P^T
+    f32x16 pt[HEADS];
+#pragma unroll
+    for (int hd = 0; hd < HEADS; ++hd) {
+      f32x16 st;
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {                                    // registers 4 g .. 4 g + 3 = keys 8 g + 4 hf ..
+        const float4 s4 = ld4(s0s + 32 * hd + 8 * g + 4 * hf);
+        st[4 * g + 0] = s4.x; st[4 * g + 1] = s4.y; st[4 * g + 2] = s4.z; st[4 * g + 3] = s4.w;
+      }
+      mfma_groups_f32<NG>([&](int i) { return gf + 32 * hd * PW + 8 * i; },
+                          [&](int i, float4 a) { DS_MFMA4(st, a, qin[i].x, qin[i].y, qin[i].z, qin[i].w); });
+      float mx = -3.0e38f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const bool ok = (r & 3) + 8 * (r >> 2) + 4 * hf < p.Lk;
+        mx = ok ? fmaxf(mx, st[r]) : mx;
+      }
+      mx = fmaxf(mx, lane_xor32(mx));
+      float sum = 0.f;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        const bool ok = (r & 3) + 8 * (r >> 2) + 4 * hf < p.Lk;
+        const float e = ok ? __expf((st[r] - mx) * p.scale) : 0.f;
+        st[r] = e;
+        sum += e;
+      }
+      sum += lane_xor32(sum);
+      const float inv = 1.0f / sum;
+#pragma unroll
+      for (int r = 0; r < 16; ++r) pt[hd][r] = st[r] * inv;
+    }
+
+    // ---------------- phase E: X1^T = sum_h U_h^T P_h^T + bp' + x^T (rows = channels; key groups of 8 up to Lk)
+    stamp(4);
+    f32x16 x1[NU];
+#pragma unroll
+    for (int t = 0; t < NU; ++t)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        const float4 b4 = ld4(vecs + 11 * C + 32 * t + 8 * g + 4 * hf);
+        x1[t][4 * g + 0] = b4.x; x1[t][4 * g + 1] = b4.y; x1[t][4 * g + 2] = b4.z; x1[t][4 * g + 3] = b4.w;
+      }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      if (8 * g < p.Lk) {
+        mfma_groups_f32<HEADS * NU>([&](int i) { return uf + 32 * (i % NU) * PU + 32 * (i / NU) + 8 * g; },   // i = hd NU + t
+                                    [&](int i, float4 a) {
+                                      const int t = i % NU, hd = i / NU;
+                                      DS_MFMA4(x1[t], a, pt[hd][4 * g + 0], pt[hd][4 * g + 1], pt[hd][4 * g + 2], pt[hd][4 * g + 3]);
+                                    });
+      }
+    }
+    if (live) {
+      float* dst = p.out + tokoff;
+#pragma unroll
+      for (int t = 0; t < NU; ++t)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+          const float4 r4 = xres[4 * t + g];
+          st4(dst + 32 * t + 8 * g, make_float4(x1[t][4 * g + 0] + r4.x, x1[t][4 * g + 1] + r4.y, x1[t][4 * g + 2] + r4.z,
+                                                x1[t][4 * g + 3] + r4.w));
+        }
+    }
+    __syncthreads();                                                  // G / U^T are dead: the next halo tile may land
+    stamp(5);
+#ifdef DIFFSAL_DEV_STAMPS
+    ++stamp_it;
+#endif
+  }
+}
+
+template <bool AHEAD>
+static int launch_front_fold(const FrontFoldArgs& a, hipStream_t s) {
+  typedef FrontFoldLds L;
+  DS_RAISE_DYNAMIC_LDS((block_front_fold_kernel<AHEAD>), 160 * 1024);
+  const int n_tiles = a.N * a.tiles_y * a.tiles_x;
+  const int resident = 256 * (AHEAD ? 1 : 2);
+  const int grid = n_tiles < resident ? n_tiles : resident;
+#ifdef DIFFSAL_DEV_STAMPS
+  FrontFoldArgs b = a;
+  b.stamps = (g_front_stamps && static_cast<size_t>(grid) * 64 * 8 <= g_front_stamp_bytes) ? g_front_stamps : nullptr;
+  hipLaunchKernelGGL((block_front_fold_kernel<AHEAD>), dim3(grid), dim3(256), L::total, s, b);
+#else
+  hipLaunchKernelGGL((block_front_fold_kernel<AHEAD>), dim3(grid), dim3(256), L::total, s, a);
+#endif
+  return check_launch("block_front_fold");
+}
+
 }  // namespace diffsal
 
 using namespace diffsal;
@@ -636,4 +1030,23 @@ extern "C" int diffsal_block_front(const void* x, const void* k, const void* v, 
   if (dtype == DIFFSAL_BF16) DS_FRONT(bf16_t, 192)
   DS_FRONT(f16_t, 192)
 #undef DS_FRONT
+}
+
+extern "C" int diffsal_block_front_fold(const float* x, const float* G, const float* U, const float* kp, const float* ukq,
+                                        const float* g1, const float* b1, float eps1, const float* w9, const float* gq,
+                                        const float* bq, float epsq, const float* bias, float* out, int N, int H, int W, int C,
+                                        int Lk, int heads, float scale, diffsal_stream_t stream) {
+  DS_REQUIRE(x && G && U && kp && ukq && g1 && b1 && w9 && gq && bq && bias && out, DIFFSAL_E_ARG, "block_front_fold: null argument");
+  DS_REQUIRE(C == 96 && heads == 2, DIFFSAL_E_SHAPE, "block_front_fold: built for C = 96, 2 heads (got C = %d, %d heads)", C, heads);
+  DS_REQUIRE(N > 0 && H > 0 && W > 0 && Lk > 0 && Lk <= 32, DIFFSAL_E_SHAPE, "block_front_fold: N=%d H=%d W=%d Lk=%d (Lk <= 32)", N, H, W, Lk);
+  DS_REQUIRE(static_cast<long>(N) * H * W * C < (1L << 31), DIFFSAL_E_SHAPE, "block_front_fold: tensor too large for one launch");
+  DS_REQUIRE(aligned16(x) && aligned16(out) && aligned16(G) && aligned16(U) && aligned16(kp) && aligned16(ukq) && aligned16(g1) &&
+                 aligned16(b1) && aligned16(w9) && aligned16(gq) && aligned16(bq) && aligned16(bias),
+             DIFFSAL_E_ALIGN, "block_front_fold: misaligned pointer (every operand is read in 16-byte pieces)");
+  DS_REQUIRE(out != x, DIFFSAL_E_ARG, "block_front_fold: in-place operation is not supported (neighbouring tiles read the halo)");
+  FrontFoldArgs a{x, G, U, kp, ukq, g1, b1, w9, gq, bq, bias, out, N, H, W, Lk, eps1, epsq, scale,
+                  (H + FT_TH - 1) / FT_TH, (W + FT_TW - 1) / FT_TW};
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (tune(TUNE_FRONT_FOLD_WGS) == 1) return launch_front_fold<true>(a, s);      // A/B aid: one workgroup per CU, look-ahead
+  return launch_front_fold<false>(a, s);
 }

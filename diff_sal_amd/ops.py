@@ -1153,6 +1153,34 @@ def block_front(x: Tensor, k: Tensor, v: Tensor, norm1, w9: Tensor, norm_q, lin_
     return out
 
 
+def block_front_fold_supported(C: int, heads: int, Lk: int, dtype: torch.dtype = torch.float32) -> bool:
+    """csrc/tblock.hip, the folded form: fp32 storage, C = 96, 2 heads, up to 32 keys per frame."""
+    return dtype == torch.float32 and heads == 2 and 0 < Lk <= 32 and C == 96
+
+
+def block_front_fold(x: Tensor, G: Tensor, U: Tensor, kp: Tensor, ukq: Tensor, norm1, w9: Tensor, norm_q, bias: Tensor, heads: int,
+                     scale: float) -> Tensor:
+    """``block_front`` on fp32 storage with proj_q / proj folded onto the key side (csrc/tblock.hip): LayerNorm -> depthwise 3x3 ->
+    LayerNorm -> x1 = x + bias + sum_h softmax_t(scale (q_in . G[:, t, h] + kp[:, t] . ukq[h])) U[:, t, h].  x [N,H,W,C]; G, U
+    [N, Lk, 2 C] (the paired product of the pooled rows kp, vp [N, Lk, C] with the folded weights of SalUNet.packed()); ukq [2, C];
+    bias [C]. The tuning switch DIFFSAL_FRONT_FOLD_WGS = 1 takes the one-workgroup form (A/B aid; bit-equal)."""
+    lib = _lib.load()
+    N, H, W, Cc = x.shape
+    Lk = kp.shape[1]
+    if (x.dtype != torch.float32 or G.shape != (N, Lk, heads * Cc) or U.shape != G.shape or kp.shape != (N, Lk, Cc)
+            or ukq.shape != (heads, Cc) or bias.shape != (Cc,)):
+        raise RuntimeError(f"block_front_fold: inconsistent shapes x {tuple(x.shape)} G {tuple(G.shape)} U {tuple(U.shape)} "
+                           f"kp {tuple(kp.shape)} ukq {tuple(ukq.shape)} bias {tuple(bias.shape)}")
+    out = torch.empty_like(x)
+    M = N * H * W
+    fl = 2.0 * M * Cc * 64 + 2.0 * M * Cc * heads * (-(-Lk // 8) * 8) + 22.0 * M * Cc      # both products as issued
+    with _prof("K10f", fl, _nb(x, out, G, U, kp), f"block_front_fold M={M} C={Cc}", kernel="block_front_fold_kernel"):
+        _lib.check(lib.diffsal_block_front_fold(_p(x), _p(G), _p(U), _p(kp), _p(ukq), _p(norm1[0]), _p(norm1[1]), float(norm1[2]),
+                                                _p(w9), _p(norm_q[0]), _p(norm_q[1]), float(norm_q[2]), _p(bias), _p(out), N, H, W,
+                                                Cc, Lk, heads, float(scale), _stream()), "block_front_fold")
+    return out
+
+
 def dwpool_ln_kv(xk: Tensor, xv: Tensor, wk: Tensor, wv: Tensor, gk: Tensor, bk: Tensor, gv: Tensor, bv: Tensor,
                  k: int, eps: float = 1e-5):
     lib = _lib.load()

@@ -233,7 +233,7 @@ class SalUNet(nn.Module):
         return self.gemm_precision or ops.get_gemm_precision()
 
     def _cache_key(self):
-        return (self._pack_epoch, self._precision(), self.compute_dtype, self.winograd, self.fold_attn_proj) + tuple(
+        return (self._pack_epoch, self._precision(), self.compute_dtype, self.winograd, self.fold_attn_proj, self.fold_front_proj, self.fused_front) + tuple(
             (p.data_ptr(), p._version) for p in list(self.parameters()) + list(self.buffers()))
 
     def pack_epoch(self):
@@ -288,10 +288,16 @@ class SalUNet(nn.Module):
         return (self.fold_attn_proj and self.compute_dtype == torch.float32 and self._precision() == "fp32"
                 and ops.attn_fold_supported(self.up_channels[i], self.heads[i], Lk, torch.float32))
 
+    def _fold_front(self, i: int, Lk: int) -> bool:
+        """Stage i takes the key-side form of the fused block front (ops.block_front_fold): switch on, fp32 storage, exact fp32
+        arithmetic and the shape csrc/tblock.hip builds it for (C = 96)."""
+        return (self.fold_front_proj and self.fused_front and self.compute_dtype == torch.float32 and self._precision() == "fp32"
+                and ops.block_front_fold_supported(self.up_channels[i], self.heads[i], Lk, torch.float32))
+
     @staticmethod
-    def fold_attn_weights(a: nn.Module):
+    def fold_attn_weights(a: nn.Module, dtype: torch.dtype = torch.float32):
         """(kq.w [2C, C], vp.w [2C, C], ukq [2, C], proj.bf [C]) of an attention module (proj_q, proj_k, proj_v, proj): proj_q and
-        proj re-associated onto the key side (weight-only, formed in fp64 on the device, rounded once).  Per head h
+        proj re-associated onto the key side (weight-only, formed in fp64 on the device, rounded once to ``dtype``).  Per head h
         with channel slice s_h:  kq.w rows h C .. = (Wk[s_h]^T Wq[s_h])^T,  vp.w rows h C .. = (Wv[s_h]^T Wp[:, s_h]^T)^T, so that
         ops.linear_pair (x @ w^T) gives G = kp Wkq_h and U = vp Wvp_h as [N Lk, 2 C];  ukq[h] = Wk[s_h]^T bq[s_h];
         proj.bf = bp + Wp bv (the softmax rows sum to 1).  The score terms that do not depend on the key are dropped."""
@@ -306,8 +312,7 @@ class SalUNet(nn.Module):
             kq.append(wq[s].t() @ wk[s])
             vp.append(wp[:, s] @ wv[s])
             ukq.append(wk[s].t() @ bq[s])
-        return (torch.cat(kq, 0).float().contiguous(), torch.cat(vp, 0).float().contiguous(),
-                torch.stack(ukq, 0).float().contiguous(), (bp + wp @ bv).float().contiguous())
+        return tuple(t.to(dtype).contiguous() for t in (torch.cat(kq, 0), torch.cat(vp, 0), torch.stack(ukq, 0), bp + wp @ bv))
 
     @staticmethod
     def _bn_affine(bn: nn.BatchNorm2d):
@@ -371,7 +376,7 @@ class SalUNet(nn.Module):
                             ("fc2", blk.mlp.fc2)):
                 pk[f"s{i}.{nm}.w"] = self._gemm_w(lin.weight)
             pk[f"s{i}.redu.w"] = self._pack_conv(dec.redu_chan_up[i].proj[0].weight)  # [Co, C, kt, 1, 1]
-            if self._fold_attn(i, 1):
+            if self._fold_attn(i, 1) or self._fold_front(i, 1):
                 pk[f"s{i}.kq.w"], pk[f"s{i}.vp.w"], pk[f"s{i}.ukq"], pk[f"s{i}.proj.bf"] = self.fold_attn_weights(a)
         if all(f"s{i}.align.w" in pk for i in range(self.num_stages)) and self.num_stages > 1:
             pk["align_all.w"] = torch.cat([pk[f"s{i}.align.w"] for i in range(self.num_stages)], 0).contiguous()
@@ -488,17 +493,27 @@ class SalUNet(nn.Module):
             xk_ = xv_ if k_src is None else k_src.view(n9, H, W, C)
             kvn = (a.conv_proj_k.bn.weight, a.conv_proj_k.bn.bias, a.conv_proj_v.bn.weight, a.conv_proj_v.bn.bias)
             pre = (blk.norm.weight, blk.norm.bias, blk.norm.eps, k_src is None)
-            if self.fold_kv_proj and C == 96:
+            f32 = x.dtype == torch.float32
+            fold = f32 and self._fold_front(i, gh * gw)
+            if fold:
+                # proj_q and proj on the key side: [pooled rows] [G | U = the pooled rows times the folded weights, one paired launch
+                # with N = 2 C] [block_front_fold]: the same three launches, q, k, v and o are never formed
+                kk, vv = ops.kv_prep(xk_, xv_, pk[f"s{i}.wk"], pk[f"s{i}.wv"], *kvn, self.kernel_kv[i], a.conv_proj_k.bn.eps, pre_ln=pre)
+                Gk, Uv = ops.linear_pair(kk, vv, pk[f"s{i}.kq.w"], pk[f"s{i}.vp.w"], None, None)
+                y = ops.block_front_fold(xv_, Gk, Uv, kk, pk[f"s{i}.ukq"], (blk.norm.weight, blk.norm.bias, blk.norm.eps),
+                                         pk[f"s{i}.wq9"], (a.conv_proj_q.bn.weight, a.conv_proj_q.bn.bias, a.conv_proj_q.bn.eps),
+                                         pk[f"s{i}.proj.bf"], self.heads[i], float(C) ** -0.5).view(n9, H * W, C)
+            elif self.fold_kv_proj and C == 96:
                 kk, vv = ops.kv_prep_proj(xk_, xv_, pk[f"s{i}.wk"], pk[f"s{i}.wv"], *kvn, self.kernel_kv[i], a.conv_proj_k.bn.eps, pre,
                                           (pk[f"s{i}.k.w"], a.proj_k.bias), (pk[f"s{i}.v.w"], a.proj_v.bias))
             else:
                 kk, vv = ops.kv_prep(xk_, xv_, pk[f"s{i}.wk"], pk[f"s{i}.wv"], *kvn, self.kernel_kv[i], a.conv_proj_k.bn.eps, pre_ln=pre)
                 kk, vv = ops.linear_pair(kk, vv, pk[f"s{i}.k.w"], pk[f"s{i}.v.w"], a.proj_k.bias, a.proj_v.bias)
-            f32 = x.dtype == torch.float32
-            y = ops.block_front(xv_, kk, vv, (blk.norm.weight, blk.norm.bias, blk.norm.eps), pk[f"s{i}.wq9"],
-                                (a.conv_proj_q.bn.weight, a.conv_proj_q.bn.bias, a.conv_proj_q.bn.eps),
-                                (pk[f"s{i}.q.w"], a.proj_q.bias), (pk[f"s{i}.proj.w"], a.proj.bias) if f32 else None,
-                                self.heads[i], float(C) ** -0.5).view(n9, H * W, C)
+            if not fold:
+                y = ops.block_front(xv_, kk, vv, (blk.norm.weight, blk.norm.bias, blk.norm.eps), pk[f"s{i}.wq9"],
+                                    (a.conv_proj_q.bn.weight, a.conv_proj_q.bn.bias, a.conv_proj_q.bn.eps),
+                                    (pk[f"s{i}.q.w"], a.proj_q.bias), (pk[f"s{i}.proj.w"], a.proj.bias) if f32 else None,
+                                    self.heads[i], float(C) ** -0.5).view(n9, H * W, C)
             nz = None if norm_z is None else (norm_z.weight, norm_z.bias, norm_z.eps)
             if C == 96 and blk.mlp.fc1.out_features == 192:
                 if f32:
@@ -629,6 +644,10 @@ class SalUNet(nn.Module):
     # (ops.attn_fold, csrc/attn_fold.hip): per token two [. x 2 Lk] contractions instead of two dense C x C products; exact algebra,
     # another summation order.  Off: the grouped / paired projections, ops.attention and the proj GEMM
     fold_attn_proj = True
+    # the same re-association inside the fused block front of the fp32 C = 96 stage (ops.block_front_fold, csrc/tblock.hip): 168
+    # instead of 384 matrix instructions per wavefront and tile, no 96 x 96 weight in LDS, two workgroups per CU; same launch count.
+    # Independent of fold_attn_proj.  Off: ops.block_front on the projected keys / values
+    fold_front_proj = True
     # fp32 3x3 stride-1 convolutions (ResnetBlock conv1 / conv2, UpEmbed's second convolution) as Winograd F(2x2, 3x3) where the
     # library's planner expects a gain (csrc/wino.hip; ~1e-6 relative transform rounding).  Off: always the direct kernel
     winograd = True

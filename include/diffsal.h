@@ -57,7 +57,7 @@ const char* diffsal_last_gemm_kernel(void);
  * DIFFSAL_WGRAD_VERBOSE, DIFFSAL_NO_FUSED_BLOCK, ... (the full list: kTuneNames in csrc/misc.hip); round 6:
  * DIFFSAL_NO_STREAM16 = 1 routes 16-bit storage back to the 8-byte forms of the HBM-bound kernels and to the kernels the planner took before
  * conv16_dma / gemm16_dma2; DIFFSAL_FORCE_HALO = 2 and DIFFSAL_GEMM_DMA16 = 3 / 4 take those two (gemm16_dma2 with its 256 x 96 / 192 x 192
- * tile) on every shape they can run; DIFFSAL_CONV16_TILE = 0 / 1 keeps conv16_dma off / on its 8 x 24 x 192-channel tile, DIFFSAL_CONV16_HALF = 0 / 1 off / on its 128-pixel tiles;
+ * tile) on every shape they can run; DIFFSAL_CONV16_TILE = 0 / 1 keeps conv16_dma off / on its 8 x 24 x 192-channel tile, DIFFSAL_CONV16_HALF = 0 / 1 off / on its 128-pixel tiles; DIFFSAL_FRONT_FOLD_WGS = 1 runs diffsal_block_front_fold as one workgroup per CU with a next-tile look-ahead;
  * DIFFSAL_BLOCK16_WAVES = 4 / 8 fixes the wavefronts per workgroup of the fused C = 96 block; DIFFSAL_TAPSUM_ROWS_FORM = 1 .. 4 takes the
  * row-streamed head gather (and its lane mapping) instead of the LDS-staged one; DIFFSAL_NO_ATTN16_MFMA = 1 keeps the 16-bit attention core
  * of head dims 192 / 384 off the matrix cores.
@@ -585,6 +585,19 @@ int diffsal_block_front(const void* x, const void* k, const void* v, const float
                         const float* w9, const float* gq, const float* bq, float epsq, const void* wq, const float* bias_q,
                         const void* wp, const float* bias_p, void* out, int N, int H, int W, int C, int Lk, int heads,
                         float scale, int dtype, diffsal_stream_t stream);
+
+/* The same block half on fp32 storage (C = 96, 2 heads) with proj_q and proj folded onto the key side, as diffsal_attn_fold does for
+ * the coarser stages (exact algebra, another summation order):
+ *   xn = LayerNorm(x; g1, b1, eps1);  q_in = LayerNorm(dwconv3x3(xn; w9); gq, bq, epsq);
+ *   S_h[l,t] = scale * (q_in[l,:] . G[n,t,h,:] + kp[n,t,:] . ukq[h,:]);  P_h = softmax_t(S_h);
+ *   out = x + bias + sum_h sum_t P_h[l,t] U[n,t,h,:]
+ * G, U [N, Lk <= 32, 2 C]: the pooled key / value rows kp, vp [N, Lk, C] times the folded weights (one paired GEMM, N = 2 C);
+ * ukq [2, C]; bias [C] = bp + Wp bv.  q, k, v and o are never formed and no C x C weight is read.  Two workgroups per CU;
+ * diffsal_set_tuning("DIFFSAL_FRONT_FOLD_WGS", 1) selects the one-workgroup form with a next-tile look-ahead (bit-equal results). */
+int diffsal_block_front_fold(const float* x, const float* G, const float* U, const float* kp, const float* ukq, const float* g1,
+                             const float* b1, float eps1, const float* w9, const float* gq, const float* bq, float epsq,
+                             const float* bias, float* out, int N, int H, int W, int C, int Lk, int heads, float scale,
+                             diffsal_stream_t stream);
 
 /* ---- storage-type conversion: dst[i] = (dst type) src[i], round to nearest even.  Used once per parameter version to
  * put packed convolution / linear weights into the 16-bit storage type of a reduced-precision module (the reference

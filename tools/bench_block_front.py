@@ -6,7 +6,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from diff_sal_amd import ops  # noqa: E402
+from diff_sal_amd import _lib, ops  # noqa: E402
 
 
 def timed(fn, n=20):
@@ -20,6 +20,35 @@ def timed(fn, n=20):
     e1.record()
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / n * 1e3
+
+
+def fold_leg(x, kp, vp, norm1, w9, norm_q, r, unfolded):
+    """ops.block_front_fold (proj_q / proj on the key side) beside ops.block_front on the same tokens: the shipped form, the one-
+    and the two-workgroup variants, and the paired product that feeds each (N = C against N = 2 C); interleaved rounds, median."""
+    N, H, W, C = x.shape
+    wk, wv = r(C, C, sc=C ** -0.5), r(C, C, sc=C ** -0.5)
+    kq, vpw, ukq, bf = r(2 * C, C, sc=C ** -0.5), r(2 * C, C, sc=C ** -0.5), r(2, C, sc=0.1), r(C, sc=0.1)
+    bk, bv = r(C, sc=0.1), r(C, sc=0.1)
+    G, U = ops.linear_pair(kp, vp, kq, vpw, None, None)
+    fold = lambda: ops.block_front_fold(x, G, U, kp, ukq, norm1, w9, norm_q, bf, 2, C ** -0.5)
+
+    def fold_one_wg():      # timed() synchronises before it returns: the switch covers exactly its launches
+        _lib.set_tuning("DIFFSAL_FRONT_FOLD_WGS", 1)
+        try:
+            return timed(fold)
+        finally:
+            _lib.set_tuning("DIFFSAL_FRONT_FOLD_WGS", None)
+
+    legs = {"block_front": unfolded, "fold, 2 workgroups / CU (shipped)": fold, "fold, 1 workgroup / CU": None,
+            "linear_pair N = C": lambda: ops.linear_pair(kp, vp, wk, wv, bk, bv),
+            "linear_pair N = 2C": lambda: ops.linear_pair(kp, vp, kq, vpw, None, None)}
+    times = {k_: [] for k_ in legs}
+    for _ in range(7):
+        for k_, fn in legs.items():
+            times[k_].append(timed(fn) if fn is not None else fold_one_wg())
+    for k_, t in times.items():
+        t.sort()
+        print(f"{'':15s} {k_:34s} median {t[len(t) // 2]:7.1f} us   min {t[0]:7.1f}   max {t[-1]:7.1f}")
 
 
 def main():
@@ -52,6 +81,8 @@ def main():
         tf, tu = timed(fused), timed(unfused)
         nb = 2 * M * C * x.element_size()
         print(f"{str(dt):15s} C={C} M={M}: fused {tf:7.1f} us ({nb / tf / 1e3:6.0f} GB/s once-through)   unfused {tu:7.1f} us")
+        if f32 and ops.block_front_fold_supported(C, heads, Lk, dt):
+            fold_leg(x, k, v, (g1, b1, 1e-5), w9, (gq, bq, 1e-5), r, fused)
         if C != 96:
             continue
         # the block's second half on the same tokens
