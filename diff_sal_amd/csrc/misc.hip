@@ -955,6 +955,151 @@ __global__ __launch_bounds__(256) void resize_update_kernel(const float* __restr
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Sampler noise from a counter-based generator (include/diffsal.h, "sampler noise"): Philox4x32-10 keyed by the seed, counted
+// by (quad, draw, clip id).  One thread = one quad of four consecutive elements of a clip; the seed and the ids are read from
+// device memory so that a captured graph can be replayed for other clips.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&r)[4]) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
+__device__ __forceinline__ void philox_quad(const long long* __restrict__ ids, const unsigned long long* __restrict__ seed,
+                                            long n, uint32_t q, uint32_t draw, uint32_t (&r)[4]) {
+  const unsigned long long sd = seed[0], id = static_cast<unsigned long long>(ids[n]);
+  philox4x32_10(q, draw, static_cast<uint32_t>(id), static_cast<uint32_t>(id >> 32), static_cast<uint32_t>(sd),
+                static_cast<uint32_t>(sd >> 32), r);
+}
+
+// Box-Muller on two words: both uniforms are exact in fp32 (24 bits; u1 in (0, 1], u2 in [0, 1)) and the angle goes to
+// sincospi as 2 u2, exact as well, so the only roundings are those of log, sqrt, sincospi and the final products.
+__device__ __forceinline__ void box_muller(uint32_t ra, uint32_t rb, float& za, float& zb) {
+  const float u1 = static_cast<float>((ra >> 8) + 1u) * 0x1p-24f;
+  const float u2 = static_cast<float>(rb >> 8) * 0x1p-24f;
+  const float rad = sqrtf(-2.f * logf(u1));
+  float s, c;
+  sincospif(2.f * u2, &s, &c);
+  za = rad * c;
+  zb = rad * s;
+}
+
+__device__ __forceinline__ void philox_normal4(const long long* __restrict__ ids, const unsigned long long* __restrict__ seed,
+                                               long n, uint32_t q, uint32_t draw, float (&z)[4]) {
+  uint32_t r[4];
+  philox_quad(ids, seed, n, q, draw, r);
+  box_muller(r[0], r[1], z[0], z[1]);
+  box_muller(r[2], r[3], z[2], z[3]);
+}
+
+// NORMAL: out = scale * z (float), else the raw words.  vec: per % 4 == 0 and out 16-byte aligned -> one 16-byte store per quad.
+template <bool NORMAL>
+__global__ __launch_bounds__(256) void philox_kernel(void* __restrict__ out, const long long* __restrict__ ids,
+                                                     const unsigned long long* __restrict__ seed, uint32_t draw, float scale,
+                                                     long per, long nq, long total, int vec) {
+  for (long i = static_cast<long>(blockIdx.x) * 256 + threadIdx.x; i < total; i += static_cast<long>(gridDim.x) * 256) {
+    const long n = i / nq;
+    const uint32_t q = static_cast<uint32_t>(i - n * nq);
+    uint32_t r[4];
+    if (NORMAL) {
+      float z[4];
+      philox_normal4(ids, seed, n, q, draw, z);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) r[j] = __builtin_bit_cast(uint32_t, scale * z[j]);
+    } else {
+      philox_quad(ids, seed, n, q, draw, r);
+    }
+    const long e0 = static_cast<long>(q) * 4;
+    uint32_t* o = static_cast<uint32_t*>(out) + n * per + e0;
+    if (vec) {
+      *reinterpret_cast<uint4*>(o) = make_uint4(r[0], r[1], r[2], r[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (e0 + j < per) o[j] = r[j];
+    }
+  }
+}
+
+// Fused step tail with a direct x0 term and in-kernel noise (include/diffsal.h: diffsal_resize_update_noise).  The same bilerp1 /
+// lincomb3 sequence as resize_update_kernel; x_next adds its terms in the fixed order x0, x, z, m, m_prev.
+__device__ __forceinline__ float update_terms(float b0, float x0, float A, float xv, float cz, float z, float c0, float m, float c1,
+                                              float mp, bool has_mp, bool ext) {
+  if (!ext) return lincomb3(A, xv, c0, m, true, c1, mp, has_mp);       // == resize_update_kernel
+  float r = 0.f;
+  bool any = false;
+  auto add = [&](float c, float v) {
+    r = any ? fmaf(c, v, r) : c * v;
+    any = true;
+  };
+  if (b0 != 0.f) add(b0, x0);
+  if (A != 0.f) add(A, xv);
+  if (cz != 0.f) add(cz, z);
+  if (c0 != 0.f) add(c0, m);
+  if (has_mp && c1 != 0.f) add(c1, mp);
+  return r;
+}
+
+__global__ __launch_bounds__(256) void resize_update_noise_kernel(
+    const float* __restrict__ s_low, const float* __restrict__ x, const float* __restrict__ m_prev, float* __restrict__ x0_out,
+    float* __restrict__ m_out, float* __restrict__ x_next, int h, int w, int H, int W, float sy, float sx, float ex, float e0,
+    float A, float b0, float c0, float c1, float cz, const long long* __restrict__ ids, const unsigned long long* __restrict__ seed,
+    uint32_t draw, long per, long nq, long total, int vec) {
+  const bool ext = b0 != 0.f || cz != 0.f;
+  for (long i = static_cast<long>(blockIdx.x) * 256 + threadIdx.x; i < total; i += static_cast<long>(gridDim.x) * 256) {
+    const long n = i / nq;
+    const uint32_t q = static_cast<uint32_t>(i - n * nq);
+    const long e_first = static_cast<long>(q) * 4, base = n * per + e_first;
+    const int cnt = per - e_first < 4 ? static_cast<int>(per - e_first) : 4;
+    float z[4] = {0.f, 0.f, 0.f, 0.f}, xv[4], mp[4] = {0.f, 0.f, 0.f, 0.f}, x0[4], m[4], xn[4];
+    if (cz != 0.f) philox_normal4(ids, seed, n, q, draw, z);
+    if (vec) {
+      const float4 a = ld4(x + base);
+      xv[0] = a.x; xv[1] = a.y; xv[2] = a.z; xv[3] = a.w;
+      if (m_prev) {
+        const float4 b = ld4(m_prev + base);
+        mp[0] = b.x; mp[1] = b.y; mp[2] = b.z; mp[3] = b.w;
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        xv[j] = j < cnt ? x[base + j] : 0.f;
+        if (m_prev && j < cnt) mp[j] = m_prev[base + j];
+      }
+    }
+    const float* img = s_low + n * h * w;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const long e = j < cnt ? e_first + j : e_first;       // lanes past the end of the map repeat its element (never stored)
+      const int Y = static_cast<int>(e / W), X = static_cast<int>(e - static_cast<long>(Y) * W);
+      x0[j] = bilerp1(img, h, w, Y, X, sy, sx);
+      m[j] = ex == 0.f ? e0 * x0[j] : lincomb3(ex, xv[j], e0, x0[j], true, 0.f, 0.f, false);
+      xn[j] = update_terms(b0, x0[j], A, xv[j], cz, z[j], c0, m[j], c1, mp[j], m_prev != nullptr, ext);
+    }
+    if (vec) {
+      if (x0_out) st4(x0_out + base, make_float4(x0[0], x0[1], x0[2], x0[3]));
+      st4(m_out + base, make_float4(m[0], m[1], m[2], m[3]));
+      if (x_next) st4(x_next + base, make_float4(xn[0], xn[1], xn[2], xn[3]));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < cnt) {
+          if (x0_out) x0_out[base + j] = x0[j];
+          m_out[base + j] = m[j];
+          if (x_next) x_next[base + j] = xn[j];
+        }
+    }
+  }
+}
+
 // storage-type conversion (weights once per parameter version; fp32 <-> bf16 / fp16), round to nearest even
 template <typename S, typename D>
 __global__ __launch_bounds__(256) void cast_kernel(const S* __restrict__ src, D* __restrict__ dst, long n) {
@@ -1015,7 +1160,7 @@ extern "C" size_t diffsal_workspace_bytes(int op, const diffsal_conv_desc* d, co
   }
 }
 
-extern "C" int diffsal_version(void) { return 44; }  // = _lib.ABI_VERSION
+extern "C" int diffsal_version(void) { return 45; }  // = _lib.ABI_VERSION
 extern "C" const char* diffsal_last_error(void) { return g_err; }
 extern "C" const char* diffsal_last_gemm_kernel(void) { return g_kernel; }
 
@@ -1603,4 +1748,44 @@ extern "C" int diffsal_resize_update(const float* s_low, const float* x, const f
                      m_prev, x0_out, m_out, x_next, h, w, H, W, static_cast<float>(h) / static_cast<float>(H),
                      static_cast<float>(w) / static_cast<float>(W), ex, e0, A, c0, c1, total);
   return check_launch("resize_update");
+}
+
+static int philox_args(const char* what, const void* out, int N, long per, const void* ids, const void* seed) {
+  DS_REQUIRE(out && ids && seed, DIFFSAL_E_ARG, "%s: null argument", what);
+  DS_REQUIRE(N > 0 && per > 0 && per <= (1L << 34), DIFFSAL_E_SHAPE, "%s: bad shape (N = %d, per = %ld; 1 <= per <= 2^34)", what, N, per);
+  return DIFFSAL_OK;
+}
+
+extern "C" int diffsal_philox_bits(unsigned int* out, int N, long per, const long long* ids, const unsigned long long* seed,
+                                   unsigned int draw, diffsal_stream_t stream) {
+  if (int rc = philox_args("philox_bits", out, N, per, ids, seed)) return rc;
+  const long nq = (per + 3) / 4, total = static_cast<long>(N) * nq;
+  hipLaunchKernelGGL((philox_kernel<false>), dim3(ew_grid(total)), dim3(256), 0, static_cast<hipStream_t>(stream), out, ids, seed,
+                     draw, 1.f, per, nq, total, (per % 4 == 0 && aligned16(out)) ? 1 : 0);
+  return check_launch("philox_bits");
+}
+
+extern "C" int diffsal_philox_normal(float* out, int N, long per, const long long* ids, const unsigned long long* seed,
+                                     unsigned int draw, float scale, diffsal_stream_t stream) {
+  if (int rc = philox_args("philox_normal", out, N, per, ids, seed)) return rc;
+  const long nq = (per + 3) / 4, total = static_cast<long>(N) * nq;
+  hipLaunchKernelGGL((philox_kernel<true>), dim3(ew_grid(total)), dim3(256), 0, static_cast<hipStream_t>(stream), out, ids, seed,
+                     draw, scale, per, nq, total, (per % 4 == 0 && aligned16(out)) ? 1 : 0);
+  return check_launch("philox_normal");
+}
+
+extern "C" int diffsal_resize_update_noise(const float* s_low, const float* x, const float* m_prev, float* x0_out, float* m_out,
+                                           float* x_next, int N, int h, int w, int H, int W, float ex, float e0, float A, float b0,
+                                           float c0, float c1, float cz, const long long* ids, const unsigned long long* seed,
+                                           unsigned int draw, diffsal_stream_t stream) {
+  DS_REQUIRE(s_low && x && m_out, DIFFSAL_E_ARG, "resize_update_noise: null argument");
+  DS_REQUIRE(N > 0 && h > 0 && w > 0 && H > 0 && W > 0, DIFFSAL_E_SHAPE, "resize_update_noise: bad shape");
+  DS_REQUIRE(cz == 0.f || (ids && seed && x_next), DIFFSAL_E_ARG, "resize_update_noise: cz != 0 needs ids, seed and x_next");
+  const long per = static_cast<long>(H) * W, nq = (per + 3) / 4, total = static_cast<long>(N) * nq;
+  const int vec = per % 4 == 0 && aligned16(x) && aligned16(m_out) && (!m_prev || aligned16(m_prev)) &&
+                  (!x0_out || aligned16(x0_out)) && (!x_next || aligned16(x_next));
+  hipLaunchKernelGGL(resize_update_noise_kernel, dim3(ew_grid(total)), dim3(256), 0, static_cast<hipStream_t>(stream), s_low, x,
+                     m_prev, x0_out, m_out, x_next, h, w, H, W, static_cast<float>(h) / static_cast<float>(H),
+                     static_cast<float>(w) / static_cast<float>(W), ex, e0, A, b0, c0, c1, cz, ids, seed, draw, per, nq, total, vec);
+  return check_launch("resize_update_noise");
 }

@@ -47,32 +47,44 @@ def max_over_ranks(value: float, device=None) -> float:
     return float(t.item())
 
 
-def sample_sharded(sampler, x_T: torch.Tensor, feats: List[torch.Tensor], audio: Optional[torch.Tensor],
-                   batch: int, gather: bool = False):
+def sample_sharded(sampler, x_T: Optional[torch.Tensor], feats: List[torch.Tensor], audio: Optional[torch.Tensor],
+                   batch: int, gather: bool = False, clip_ids=None):
     """Sample ``x_T.shape[0]`` clips split over the ranks of the default group, ``batch`` clips at a time.
 
     Every argument holds ALL clips on every rank (host or device); each rank only touches its shard.
-    Returns this rank's predictions, or (gather=True) the full tensor in clip order on every rank."""
+    Returns this rank's predictions, or (gather=True) the full tensor in clip order on every rank.
+
+    ``x_T=None, clip_ids=[...]`` (a sampler with noise_source="device"): each rank draws the noise of the clips it owns
+    from the counter-based generator, so the sweep's predictions do not depend on the number of ranks or on ``batch``."""
     world = dist.get_world_size() if dist.is_initialized() else 1
     rank = dist.get_rank() if dist.is_initialized() else 0
-    mine = shard_range(x_T.shape[0], rank, world)
+    if x_T is None and clip_ids is None:
+        raise ValueError("sample_sharded: x_T=None needs clip_ids")
+    n_clips = x_T.shape[0] if x_T is not None else len(clip_ids)
+    if clip_ids is not None and len(clip_ids) != n_clips:
+        raise ValueError(f"sample_sharded: {len(clip_ids)} clip ids for {n_clips} clips")
+    mine = shard_range(n_clips, rank, world)
     outs = []
     for s in range(mine.start, mine.stop, batch):
         e = min(s + batch, mine.stop)
         a = None if audio is None else audio[s:e]
         fs = [f[s:e] for f in feats]
+        x = None if x_T is None else x_T[s:e]
+        kw = {} if clip_ids is None else {"clip_ids": clip_ids[s:e]}
         if sampler.sample_type == "ddim":          # same dispatch as DiffusionSampler.sample_image
-            outs.append(sampler.sample_ddim(x_T[s:e], fs, a))
+            outs.append(sampler.sample_ddim(x, fs, a, **kw))
         elif sampler.sample_type in ("dpmsolver", "dpmsolver++"):
-            outs.append(sampler.sample_dpm_solver(x_T[s:e], fs, a))
+            outs.append(sampler.sample_dpm_solver(x, fs, a, **kw))
         elif sampler.sample_type == "ddpm":
-            outs.append(sampler.sample_ddpm(x_T[s:e], fs, a))
+            outs.append(sampler.sample_ddpm(x, fs, a, **kw))
         else:
             raise NotImplementedError(sampler.sample_type)
+    if x_T is None and not outs:       # an empty shard still needs the prediction's shape for the gather
+        x_T = torch.empty(sampler._state_shape(0), device=sampler._noise_device())
     local = torch.cat(outs) if outs else x_T[:0]
     if not gather or world == 1:
         return local
-    sizes = [len(shard_range(x_T.shape[0], r, world)) for r in range(world)]
+    sizes = [len(shard_range(n_clips, r, world)) for r in range(world)]
     pad = max(sizes)
     buf = torch.zeros((pad,) + tuple(local.shape[1:]), dtype=local.dtype, device=local.device)
     buf[: local.shape[0]] = local

@@ -1998,6 +1998,104 @@ def resize_update(s_low: Tensor, x: Tensor, m_prev: Optional[Tensor], ex: float,
     return m, xn, x0
 
 
+# ---- sampler noise from the counter-based generator (include/diffsal.h, "sampler noise") ----
+def noise_key(ids, seed, device) -> Tuple[Tensor, Tensor]:
+    """(ids int64 [N], seed int64 [1]) on ``device``, the two buffers the noise kernels read.  Host-side ids (a sequence or a
+    CPU tensor) are checked to be non-negative before they are uploaded; a device tensor is taken as it is (reading it back
+    would synchronise).  ``seed`` is a Python int in [0, 2^64) or an int64 device tensor holding its 64-bit pattern."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("diff_sal_amd device noise runs on the GPU only (no CPU fallback); got device " + str(device))
+    # everything is checked before anything is uploaded
+    host = None
+    if isinstance(ids, Tensor) and ids.is_cuda:
+        if ids.dtype != torch.int64 or ids.dim() != 1:
+            raise ValueError(f"clip ids must be a 1-D int64 tensor, got {ids.dtype} {tuple(ids.shape)}")
+    else:
+        host = [int(v) for v in (ids.reshape(-1).tolist() if isinstance(ids, Tensor) else ids)]
+        if any(v < 0 or v >= 1 << 63 for v in host):
+            raise ValueError(f"clip ids must be non-negative int64 values, got {host}")
+    if isinstance(seed, Tensor):
+        if not seed.is_cuda or seed.dtype != torch.int64 or seed.numel() != 1:
+            raise ValueError("a seed tensor must be one int64 element on the GPU")
+    else:
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed must be in [0, 2^64), got {seed}")
+    ids_t = ids.contiguous() if host is None else torch.tensor(host, dtype=torch.int64).to(device)
+    seed_t = (seed.contiguous() if isinstance(seed, Tensor)
+              else torch.tensor([seed - (1 << 64) if seed >= 1 << 63 else seed], dtype=torch.int64).to(device))
+    return ids_t, seed_t
+
+
+def _draw(draw) -> int:
+    draw = int(draw)
+    if not 0 <= draw < 1 << 32:
+        raise ValueError(f"draw must be a uint32, got {draw}")
+    return draw
+
+
+def philox_bits(ids, seed, draw: int, per: int, device="cuda") -> Tensor:
+    """Raw Philox4x32-10 words of (seed, ids[n], draw) as an int32 tensor [N, per] holding the 32-bit patterns (a test aid)."""
+    lib = _lib.load()
+    if int(per) <= 0:
+        raise ValueError(f"per must be positive, got {per}")
+    ids_t, seed_t = noise_key(ids, seed, ids.device if isinstance(ids, Tensor) and ids.is_cuda else device)
+    out = torch.empty((ids_t.numel(), int(per)), device=ids_t.device, dtype=torch.int32)
+    with _prof("K15", 0.0, _nb(out)):
+        _lib.check(lib.diffsal_philox_bits(out.data_ptr(), ids_t.numel(), int(per), ids_t.data_ptr(), seed_t.data_ptr(), _draw(draw),
+                                           _stream()), "philox_bits")
+    return out
+
+
+def philox_normal(ids, seed, draw: int, shape: Sequence[int], scale: float = 1.0, device="cuda") -> Tensor:
+    """scale * N(0, 1) for the clips ``ids``: fp32 [N, *shape] with ``shape`` the per-clip shape (e.g. (1, H, W)); a pure function
+    of (seed, id, draw, element index inside the clip)."""
+    lib = _lib.load()
+    shape = tuple(int(v) for v in shape)
+    per = 1
+    for v in shape:
+        per *= v
+    if per <= 0:
+        raise ValueError(f"empty per-clip shape {shape}")
+    ids_t, seed_t = noise_key(ids, seed, ids.device if isinstance(ids, Tensor) and ids.is_cuda else device)
+    out = torch.empty((ids_t.numel(),) + shape, device=ids_t.device, dtype=torch.float32)
+    with _prof("K15", 0.0, _nb(out)):
+        _lib.check(lib.diffsal_philox_normal(_p(out), ids_t.numel(), per, ids_t.data_ptr(), seed_t.data_ptr(), _draw(draw),
+                                             float(scale), _stream()), "philox_normal")
+    return out
+
+
+def resize_update_noise(s_low: Tensor, x: Tensor, m_prev: Optional[Tensor], ex: float, e0: float, A: float, c0: float, c1: float = 0.0,
+                        *, b0: float = 0.0, cz: float = 0.0, noise_key=None, want_x0: bool = False, want_next: bool = True):
+    """``resize_update`` with a direct x0 term and in-kernel noise (include/diffsal.h): -> (m, x_next, x0) with
+    x_next = b0 x0 + A x + cz z + c0 m + c1 m_prev, z = the normals of ``noise_key = (ids, seed, draw)`` (device tensors from
+    ``noise_key()`` and the draw index) generated in place when cz != 0."""
+    lib = _lib.load()
+    N, h, w = s_low.shape[0], s_low.shape[1], s_low.shape[2]
+    H, W = x.shape[-2], x.shape[-1]
+    ids_p = seed_p = None
+    draw = 0
+    if float(cz) != 0.0:
+        if noise_key is None:
+            raise ValueError("resize_update_noise: cz != 0 needs noise_key = (ids, seed, draw)")
+        ids_t, seed_t, draw = noise_key
+        if not (ids_t.is_cuda and ids_t.dtype == torch.int64 and ids_t.is_contiguous() and ids_t.numel() == N
+                and seed_t.is_cuda and seed_t.dtype == torch.int64 and seed_t.numel() == 1):
+            raise ValueError("resize_update_noise: noise_key must hold int64 GPU tensors, one id per clip and one seed")
+        if not want_next:
+            raise ValueError("resize_update_noise: cz != 0 without x_next")
+        ids_p, seed_p = ids_t.data_ptr(), seed_t.data_ptr()
+    m = torch.empty_like(x)
+    xn = torch.empty_like(x) if want_next else None
+    x0 = torch.empty_like(x) if want_x0 else None
+    with _prof("K15", 0.0, _nb(s_low, x, m_prev, m, xn, x0)):
+        _lib.check(lib.diffsal_resize_update_noise(_p(s_low), _p(x), _p(m_prev), _p(x0), _p(m), _p(xn), N, h, w, H, W, float(ex),
+                                                   float(e0), float(A), float(b0), float(c0), float(c1), float(cz), ids_p, seed_p,
+                                                   _draw(draw), _stream()), "resize_update_noise")
+    return m, xn, x0
+
+
 # ---- training of the encoders: forward variants that keep what the backward needs, and the backward kernels ----
 def pool3d(x: Tensor, w27: Tensor, size, stride) -> Tensor:
     """attention_pool's depthwise Conv3d alone (no LayerNorm): x [B,N,heads,D] view -> [B,heads,1+Lo,D]."""

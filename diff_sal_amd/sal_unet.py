@@ -710,10 +710,13 @@ class SalUNet(nn.Module):
             return self._forward_eval(x, t, feat_list, audio_feat_list, taps)
 
     def forward_fused_update(self, x: Tensor, t: Tensor, feat_list: Sequence[Tensor], audio_feat_list: Optional[Tensor], *,
-                             ex: float, e0: float, A: float, c0: float, c1: float = 0.0, m_prev: Optional[Tensor] = None):
+                             ex: float, e0: float, A: float, c0: float, c1: float = 0.0, m_prev: Optional[Tensor] = None,
+                             b0: float = 0.0, cz: float = 0.0, noise_key=None):
         """One evaluation whose last kernel also does the solver's work: returns (m, x_next) with
         x0 = the network output, m = ex x + e0 x0 (the wrapper's x_start -> noise conversion), x_next = A x + c0 m + c1 m_prev
-        (the multistep update).  Eval mode only; bit-equal to forward() followed by the stand-alone sampler kernels."""
+        (the multistep update).  Eval mode only; bit-equal to forward() followed by the stand-alone sampler kernels.
+        b0 / cz (DDIM and DDPM steps): x_next = b0 x0 + A x + cz z + c0 m + c1 m_prev with z the device noise of
+        ``noise_key = (ids [B] int64, seed [1] int64, draw)`` generated inside that kernel (ops.resize_update_noise)."""
         if self.training:
             raise RuntimeError("forward_fused_update is an inference path")
         if not x.is_cuda:
@@ -727,7 +730,12 @@ class SalUNet(nn.Module):
                 e = min(B, s + cpp)
                 low = self._forward_eval(x[s:e], t[s:e], [f[s:e] for f in feat_list],
                                          None if audio_feat_list is None else audio_feat_list[s:e], None, lowres=True)
-                m, xn, _ = ops.resize_update(low, x[s:e], None if m_prev is None else m_prev[s:e].contiguous(), ex, e0, A, c0, c1)
+                mp = None if m_prev is None else m_prev[s:e].contiguous()
+                if b0 == 0.0 and cz == 0.0:
+                    m, xn, _ = ops.resize_update(low, x[s:e], mp, ex, e0, A, c0, c1)
+                else:
+                    nk = None if noise_key is None else (noise_key[0][s:e], noise_key[1], noise_key[2])
+                    m, xn, _ = ops.resize_update_noise(low, x[s:e], mp, ex, e0, A, c0, c1, b0=b0, cz=cz, noise_key=nk)
                 ms.append(m)
                 xs.append(xn)
         return (ms[0], xs[0]) if len(ms) == 1 else (torch.cat(ms), torch.cat(xs))

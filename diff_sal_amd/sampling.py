@@ -13,6 +13,7 @@ no device->host synchronisation.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Optional, Sequence
 
 import torch
@@ -28,11 +29,13 @@ class DiffusionSampler:
                  num_diffusion_timesteps=1000, training_target="x0", sample_type="ddim", timesteps=1, eta=0.0,
                  skip_type="logSNR", dpm_solver_order=2, dpm_solver_method="multistep", dpm_solver_type="dpmsolver",
                  lower_order_final=False, denoise=True, thresholding=False, device=None, hip_graph="auto",
-                 step_invariant_shortcut=False, fused_update=True):
+                 step_invariant_shortcut=False, fused_update=True, noise_source="torch", seed=0, clip_passes=None):
         """``model`` exposes ``decoder_net`` and optionally ``visual_net`` / ``audio_net`` / ``forward_vggish``
         (a ``VideoSaliencyModel``; a DDP/DataParallel wrapper is unwrapped through ``.module``).
         Keyword names = the YAML fields the trainer reads (R/cfgs/diffusion.yml:24-28, 37, 63-78)."""
         assert training_target in ("x0", "noise")
+        if noise_source not in ("torch", "device"):
+            raise ValueError(f"unknown noise_source {noise_source!r}; choose 'torch' or 'device'")
         self.model = getattr(model, "module", model)
         self.training_target = training_target
         self.sample_type, self.timesteps, self.eta = sample_type, int(timesteps), float(eta)
@@ -73,6 +76,18 @@ class DiffusionSampler:
         #  fused_update (ON by default: same arithmetic, bit-equal results): the DPM-Solver branch folds each step's final
         #    resize + x0->noise conversion + multistep update into the denoiser's last kernel (SalUNet.forward_fused_update).
         self.fused_update = bool(fused_update)
+        #  noise_source: "torch" (the default) draws x_T and the per-step noise of DDIM with eta > 0 / DDPM from torch's stateful
+        #    generator, as the reference does.  "device": a counter-based generator (Philox4x32-10, include/diffsal.h) keyed by
+        #    ``seed`` and counted by (clip id, draw, element): a clip's prediction no longer depends on the batch it sits in, its
+        #    position there or the number of ranks of a sweep; the step noise is generated inside the fused step tail, and a
+        #    stochastic trajectory can be replayed from a graph (ids and seed are device buffers rewritten before a replay).
+        #  clip_passes (None: on with "device", off with "torch"): the denoiser evaluates a batch one clip per pass
+        #    (SalUNet.max_clips_per_pass = 1 for the trajectory).  Its kernels choose tiles by the batch size, so a clip's output moves
+        #    by ~1e-6 with the batch it is evaluated in; one clip per pass makes the whole prediction, not only the noise, bit-equal
+        #    on any layout, at the price of the batched launches (B = 1 is unaffected).  False keeps the batched passes: the noise
+        #    is still layout-independent, the prediction then agrees across layouts to ~1e-6.
+        self.noise_source, self.seed = noise_source, int(seed)
+        self.clip_passes = (noise_source == "device") if clip_passes is None else bool(clip_passes)
         if self.step_invariant_shortcut:
             self._check_shortcut_precondition()
         self._graphs = {}
@@ -122,25 +137,129 @@ class DiffusionSampler:
         x_recon = out if self.training_target == "x0" else self.predict_start_from_noise(x, t, out)
         return self.q_posterior(x_recon, x, t)
 
+    # ---- device noise (noise_source="device") ----
+    def _noise_device(self, like=None):
+        dev = like.device if like is not None else torch.device(self.device if self.device is not None else "cuda")
+        if torch.device(dev).type != "cuda":
+            raise RuntimeError("diff_sal_amd device noise runs on the GPU only (no CPU fallback); got a CPU tensor")
+        return dev
+
+    def _noise_key(self, clip_ids, x):
+        """(ids, seed) device buffers of a trajectory, or None with noise_source="torch" / without clip ids."""
+        if self.noise_source != "device":
+            if clip_ids is not None:
+                raise ValueError("clip_ids are only used with noise_source='device'")
+            return None
+        dev = self._noise_device(x)
+        if clip_ids is None:
+            return None
+        from . import ops
+        ids, seed = ops.noise_key(clip_ids, self.seed, dev)
+        if ids.numel() != x.shape[0]:
+            raise ValueError(f"{ids.numel()} clip ids for {x.shape[0]} clips")
+        return ids, seed
+
+    def _step_noise(self, x, key, draw):
+        """N(0, 1) of the shape of ``x`` for step noise number ``draw``: torch's generator, or the device generator."""
+        if self.noise_source != "device":
+            return torch.randn_like(x)
+        if key is None:
+            raise ValueError("noise_source='device': a stochastic trajectory needs clip_ids")
+        from . import ops
+        return ops.philox_normal(key[0], key[1], draw, tuple(x.shape[1:]))
+
+    @contextlib.contextmanager
+    def _passes(self):
+        """One clip per denoiser pass for the duration of a trajectory when ``clip_passes`` is on (see __init__)."""
+        net = self.model.decoder_net
+        if not self.clip_passes or not hasattr(net, "max_clips_per_pass"):
+            yield
+            return
+        own = net.__dict__.get("max_clips_per_pass")
+        net.max_clips_per_pass = 1
+        try:
+            yield
+        finally:
+            if own is None:
+                del net.max_clips_per_pass          # back to the class default
+            else:
+                net.max_clips_per_pass = own
+
+    def _state_shape(self, n):
+        h, w = self.model.decoder_net.img_size
+        return (int(n), 1, int(h), int(w))
+
+    def initial_noise(self, clip_ids, shape=None, device=None) -> Tensor:
+        """x_T of the clips ``clip_ids`` (draw 0 of the device generator): [len(clip_ids), *shape[1:]] fp32.  ``shape`` is the
+        shape of the whole batch, as in ``torch.randn(shape)`` (default: [N, 1, *decoder_net.img_size])."""
+        if self.noise_source != "device":
+            raise ValueError("initial_noise needs noise_source='device' (torch noise: the caller draws x_T)")
+        from . import ops
+        dev = clip_ids.device if isinstance(clip_ids, Tensor) and clip_ids.is_cuda else (device if device is not None else self._noise_device())
+        ids, seed = ops.noise_key(clip_ids, self.seed, dev)
+        shape = self._state_shape(ids.numel()) if shape is None else tuple(int(v) for v in shape)
+        if shape[0] != ids.numel():
+            raise ValueError(f"{ids.numel()} clip ids for a batch of shape {shape}")
+        return ops.philox_normal(ids, seed, 0, shape[1:])
+
+    def _start(self, x, clip_ids, img):
+        """(x, key) at the start of a trajectory: x_T from the device generator when the caller passed x=None."""
+        if self.noise_source == "device" and x is not None and not x.is_cuda:
+            raise RuntimeError("diff_sal_amd device noise runs on the GPU only (no CPU fallback); got a CPU tensor")
+        if x is None:
+            if self.noise_source != "device" or clip_ids is None:
+                raise ValueError("x=None needs noise_source='device' and clip_ids")
+            dev = img[0].device if img else None
+            x = self.initial_noise(clip_ids, device=dev)
+        return x, self._noise_key(clip_ids, x)
+
     @torch.no_grad()
     def p_sample(self, x: Tensor, t: int, img, clip_denoised: bool = True, audio_cond: Optional[Tensor] = None,
-                 noise: Optional[Tensor] = None) -> Tensor:
+                 noise: Optional[Tensor] = None, noise_key=None) -> Tensor:
+        """``noise_key = (ids, seed, draw)`` (noise_source="device"): the step noise comes from the device generator, inside
+        the denoiser's last kernel where the fused tail applies."""
+        if noise is None and noise_key is not None and self._tail_fusable(x):
+            net = self.model.decoder_net
+            t_tensor = torch.full((x.shape[0],), t, dtype=torch.int64, device=x.device)
+            cz = 0.0 if t == 0 else float(torch.exp(0.5 * self.posterior_log_variance_clipped[t]))
+            _, xn = net.forward_fused_update(x, t_tensor, img, audio_cond, ex=0.0, e0=1.0, A=float(self.posterior_mean_coef2[t]),
+                                             c0=0.0, b0=float(self.posterior_mean_coef1[t]), cz=cz,
+                                             noise_key=noise_key if cz != 0.0 else None)
+            return xn
         mean, _, log_var = self.p_mean_variance(x, t, img, clip_denoised=clip_denoised, audio_cond=audio_cond)
         if t == 0:
             return mean                                   # no noise at the last step (:517-519)
         if noise is None:
-            noise = torch.randn_like(x)
+            noise = torch.randn_like(x) if noise_key is None else self._step_noise(x, noise_key[:2], noise_key[2])
         return _lincomb(mean, 1.0, noise, float(torch.exp(0.5 * log_var)))
 
     @torch.no_grad()
-    def sample_ddpm(self, x: Tensor, img=None, audio_cond: Optional[Tensor] = None, noises=None) -> Tensor:
+    def sample_ddpm(self, x: Optional[Tensor], img=None, audio_cond: Optional[Tensor] = None, noises=None, clip_ids=None) -> Tensor:
         """``timesteps`` ancestral steps on the grid ``range(0, T, T // timesteps)`` reversed (:574-578).  The conditioning
-        list is never mutated here, so the reference's per-step ``copy.deepcopy`` is not needed."""
+        list is never mutated here, so the reference's per-step ``copy.deepcopy`` is not needed.
+        noise_source="device": ``clip_ids`` (one int64 per row) name the clips; ``x=None`` starts from their x_T."""
+        x, key = self._start(x, clip_ids, img)
+        if noises is None and self.noise_source == "device" and key is None:
+            raise ValueError("noise_source='device': a stochastic trajectory needs clip_ids")
+        with self._passes():
+            # torch noise stays eager (a seeded run draws the numbers the eager loop draws); device noise replays like DDIM
+            if noises is None and key is not None and self._use_graph(x, device_noise=True):
+                return self._graphed(self._sample_ddpm, x, img, audio_cond, key)
+            return self._sample_ddpm(x, img, audio_cond, key, noises)
+
+    def _sample_ddpm(self, x, img, audio_cond, key=None, noises=None):
         skip = self.num_timesteps // self.timesteps
         seq = list(range(0, self.num_timesteps, skip))
         for i, t in enumerate(reversed(seq)):
-            x = self.p_sample(x, t, img, audio_cond=audio_cond, noise=None if noises is None else noises[i])
+            nk = None if key is None or noises is not None else (key[0], key[1], i + 1)
+            x = self.p_sample(x, t, img, audio_cond=audio_cond, noise=None if noises is None else noises[i], noise_key=nk)
         return x
+
+    def _tail_fusable(self, x) -> bool:
+        """The fused DDIM / DDPM step tail applies when the denoiser is ours in eval mode and predicts x0."""
+        net = self.model.decoder_net
+        return (self.fused_update and hasattr(net, "forward_fused_update") and not getattr(net, "training", False)
+                and x.is_cuda and self.training_target == "x0")
 
     # ---- DDIM (the reference's live sampler) ----
     def _shortcut(self, x, img, audio_cond):
@@ -148,16 +267,17 @@ class DiffusionSampler:
         t = torch.full((x.size(0),), self.num_timesteps - 1, dtype=torch.int64, device=x.device)
         return net(x, t, img, None)
 
-    def _use_graph(self, x) -> bool:
+    def _use_graph(self, x, device_noise: bool = False) -> bool:
         if not x.is_cuda or torch.cuda.is_current_stream_capturing():
             return False
         if self.hip_graph == "auto":
             net = self.model.decoder_net
             from . import ops
             # only our own denoiser in eval mode is known to be capturable (no host sync, no allocation outside the pool); a
-            # stochastic trajectory (DDIM with eta > 0) stays eager so that a seeded run draws the numbers the eager loop draws;
+            # stochastic trajectory (DDIM with eta > 0) on torch's generator stays eager so that a seeded run draws the numbers
+            # the eager loop draws -- device noise has no state to advance and is replayed like a deterministic trajectory;
             # per-launch profiling events cannot be recorded inside a capture
-            if ops.PROFILE is not None or (self.sample_type != "dpmsolver" and self.eta != 0.0):
+            if ops.PROFILE is not None or (self.sample_type != "dpmsolver" and self.eta != 0.0 and not device_noise):
                 return False
             return x.size(0) <= self.graph_batch_max and hasattr(net, "forward_fused_update") and not getattr(net, "training", False)
         return bool(self.hip_graph)
@@ -170,33 +290,38 @@ class DiffusionSampler:
         epoch = net.pack_epoch() if hasattr(net, "pack_epoch") else None
         return (epoch, bool(getattr(net, "training", False)), self.sample_type, self.timesteps, self.eta, self.skip_type,
                 self.dpm_solver_order, self.dpm_solver_method, self.dpm_solver_type, self.lower_order_final, self.denoise,
-                self.thresholding, self.training_target, self.fused_update)
+                self.thresholding, self.training_target, self.fused_update, self.clip_passes, self.noise_source)
 
-    def _graphed(self, fn, x, img, audio_cond):
+    def _graphed(self, fn, x, img, audio_cond, noise_key=None):
         """Replay (capturing on first use) ``fn(x, img, audio_cond)`` as one HIP graph per input signature; a graph is
-        re-captured when the decoder's packed weights or the sampler's hyper-parameters changed since its capture."""
-        key = (fn.__name__, tuple(x.shape), tuple(tuple(f.shape) for f in img), None if audio_cond is None else tuple(audio_cond.shape))
+        re-captured when the decoder's packed weights or the sampler's hyper-parameters changed since its capture.
+        ``noise_key`` (ids, seed): device noise; the two buffers are static inputs like x, so other clips or another seed
+        replay the same capture."""
+        key = (fn.__name__, tuple(x.shape), tuple(tuple(f.shape) for f in img), None if audio_cond is None else tuple(audio_cond.shape),
+               noise_key is not None)
+        call = fn if noise_key is None else (lambda a, b, c: fn(a, b, c, sk))
         state = self._graph_state()
         ent = self._graphs.get(key)
         if ent is not None and ent[0] != state:
             ent = None              # stale: drop it (frees its private pool) and capture again
             del self._graphs[key]
         if ent is not None and ent[1] is None:
-            return fn(x, img, audio_cond)          # this signature failed to capture once: eager from then on
+            return fn(x, img, audio_cond) if noise_key is None else fn(x, img, audio_cond, noise_key)   # failed to capture once: eager
         if ent is None:
             sx, simg = x.clone(), [f.clone() for f in img]
             sa = None if audio_cond is None else audio_cond.clone()
+            sk = None if noise_key is None else tuple(t.clone() for t in noise_key)
             # the warm-up (library load, weight packing, allocator pools) must not move the caller's random stream
             dev = x.device
             rng_cpu, rng_dev = torch.get_rng_state(), torch.cuda.get_rng_state(dev)
             try:
-                fn(sx, simg, sa)
+                call(sx, simg, sa)
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 # thread_local: a HIP call from another thread of the process (pin-memory thread, collective watchdog) must
                 # not invalidate this capture
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                    out = fn(sx, simg, sa)
+                    out = call(sx, simg, sa)
             except Exception as e:  # noqa: BLE001 -- any capture failure: remember it, run the loop eagerly
                 if self.hip_graph != "auto":
                     raise
@@ -204,40 +329,61 @@ class DiffusionSampler:
                 warnings.warn(f"diff_sal_amd: HIP-graph capture of {fn.__name__} failed ({type(e).__name__}: {e}); "
                               "this input signature runs eagerly from now on")
                 torch.cuda.synchronize()
-                self._graphs[key] = (state, None, None, None, None, None)
+                self._graphs[key] = (state, None, None, None, None, None, None)
                 torch.set_rng_state(rng_cpu)
                 torch.cuda.set_rng_state(rng_dev, dev)
-                return fn(x, img, audio_cond)
+                return fn(x, img, audio_cond) if noise_key is None else fn(x, img, audio_cond, noise_key)
             torch.set_rng_state(rng_cpu)
             torch.cuda.set_rng_state(rng_dev, dev)
-            ent = (state, g, sx, simg, sa, out)
+            ent = (state, g, sx, simg, sa, out, sk)
             self._graphs[key] = ent
-        _, g, sx, simg, sa, out = ent
+        _, g, sx, simg, sa, out, sk = ent
         sx.copy_(x)
         for d, s_ in zip(simg, img):
             d.copy_(s_)
         if sa is not None:
             sa.copy_(audio_cond)
+        if sk is not None:
+            for d, s_ in zip(sk, noise_key):
+                d.copy_(s_)
         g.replay()
         return out.clone()
 
     @torch.no_grad()
-    def sample_ddim(self, x: Tensor, img: Optional[Sequence[Tensor]] = None, audio_cond: Optional[Tensor] = None) -> Tensor:
+    def sample_ddim(self, x: Optional[Tensor], img: Optional[Sequence[Tensor]] = None, audio_cond: Optional[Tensor] = None,
+                    clip_ids=None) -> Tensor:
+        """noise_source="device": ``clip_ids`` (one int64 per row) name the clips; ``x=None`` starts from their x_T."""
+        x, key = self._start(x, clip_ids, img)
         if self.step_invariant_shortcut and audio_cond is None:
             return self._shortcut(x, img, audio_cond)
-        if self._use_graph(x):
-            return self._graphed(self._sample_ddim, x, img, audio_cond)
-        return self._sample_ddim(x, img, audio_cond)
+        if self.eta != 0.0 and self.noise_source == "device" and key is None and self.timesteps > 1:
+            raise ValueError("noise_source='device': a stochastic trajectory needs clip_ids")
+        with self._passes():
+            if self._use_graph(x, device_noise=key is not None):
+                return self._graphed(self._sample_ddim, x, img, audio_cond, key)
+            return self._sample_ddim(x, img, audio_cond, key)
 
-    def _sample_ddim(self, x, img, audio_cond):
+    def _sample_ddim(self, x, img, audio_cond, key=None):
         skip = self.num_timesteps // self.timesteps
         seq = list(range(0, self.num_timesteps, skip))
         seq_next = [-1] + seq[:-1]
         n = x.size(0)
         net = self.model.decoder_net
-        for time, time_next in zip(reversed(seq), reversed(seq_next)):
+        # fused tail (one forward_fused_update per step, nothing after the network): whenever the step draws nothing (eta = 0)
+        # or draws from the device generator; torch noise keeps the stand-alone launches and its generator's numbers
+        fused = self._tail_fusable(x) and (self.eta == 0.0 or key is not None)
+        for step, (time, time_next) in enumerate(zip(reversed(seq), reversed(seq_next))):
             t_tensor = torch.full((n,), time, dtype=torch.int64, device=x.device)
             alpha = float(self.alphas_hat[time])
+            if fused and time_next >= 0:
+                alpha_next = float(self.alphas_hat[time_next])
+                c1 = self.eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)) ** 0.5
+                c2 = ((1 - alpha_next) - c1 ** 2) ** 0.5
+                r, rm1 = float(self.sqrt_recip_alphas_hat[time]), float(self.sqrt_recipm1_alphas_hat[time])
+                _, x = net.forward_fused_update(x, t_tensor, img, audio_cond, ex=r / rm1, e0=-1.0 / rm1, A=0.0, c0=c2,
+                                                b0=float(self.sqrt_alphas_hat[time_next]), cz=c1,
+                                                noise_key=None if c1 == 0.0 else (key[0], key[1], step + 1))
+                continue
             out = net(x, t_tensor, img, audio_cond)
             if self.training_target == "x0":
                 x_start = out
@@ -252,19 +398,22 @@ class DiffusionSampler:
             c1 = self.eta * ((1 - alpha / alpha_next) * (1 - alpha_next) / (1 - alpha)) ** 0.5
             c2 = ((1 - alpha_next) - c1 ** 2) ** 0.5
             if c1 != 0.0:
-                x = _lincomb(x_start, float(self.sqrt_alphas_hat[time_next]), torch.randn_like(x), c1, pred_noise, c2)
+                x = _lincomb(x_start, float(self.sqrt_alphas_hat[time_next]), self._step_noise(x, key, step + 1), c1, pred_noise, c2)
             else:  # eta = 0 (the shipped config): deterministic, no RNG launch
                 x = _lincomb(x_start, float(self.sqrt_alphas_hat[time_next]), pred_noise, c2)
         return x
 
     # ---- DPM-Solver (the path the reference intended, with D1-D4 fixed) ----
     @torch.no_grad()
-    def sample_dpm_solver(self, x: Tensor, img=None, audio_cond: Optional[Tensor] = None) -> Tensor:
+    def sample_dpm_solver(self, x: Optional[Tensor], img=None, audio_cond: Optional[Tensor] = None, clip_ids=None) -> Tensor:
+        """Deterministic: ``clip_ids`` only matter for ``x=None`` (x_T from the device generator, noise_source="device")."""
+        x, _ = self._start(x, clip_ids, img)
         if self.step_invariant_shortcut and audio_cond is None:
             return self._shortcut(x, img, audio_cond)
-        if self._use_graph(x):
-            return self._graphed(self._sample_dpm_solver, x, img, audio_cond)
-        return self._sample_dpm_solver(x, img, audio_cond)
+        with self._passes():
+            if self._use_graph(x):
+                return self._graphed(self._sample_dpm_solver, x, img, audio_cond)
+            return self._sample_dpm_solver(x, img, audio_cond)
 
     def _fusable(self, x) -> bool:
         """The fused step tail (SalUNet.forward_fused_update) applies when the denoiser is ours in eval mode, predicts x0,
@@ -358,8 +507,9 @@ class DiffusionSampler:
                              solver_type=self.dpm_solver_type)
 
     @torch.no_grad()
-    def sample_image(self, x: Tensor, img: Optional[Tensor] = None, audio: Optional[Tensor] = None) -> Tensor:
-        """Encoders once per clip, then the per-step loop (R/diffusion_trainer.py:546-640)."""
+    def sample_image(self, x: Optional[Tensor], img: Optional[Tensor] = None, audio: Optional[Tensor] = None, clip_ids=None) -> Tensor:
+        """Encoders once per clip, then the per-step loop (R/diffusion_trainer.py:546-640).  noise_source="device":
+        ``clip_ids`` name the clips and ``x=None`` starts from their x_T."""
         m = self.model
         audio_embed = None
         if getattr(m, "audio_net", None):
@@ -367,15 +517,18 @@ class DiffusionSampler:
         if getattr(m, "visual_net", None):
             vis_list = m.visual_net(img)
         else:  # same synthetic fall-back shapes as the reference (:564-569)
+            if x is None:
+                x = self.initial_noise(clip_ids)
             b, dev = x.shape[0], x.device
             vis_list = [torch.randn((b, c, 8, h, w), device=dev)
                         for c, h, w in ((768, 7, 12), (384, 14, 24), (192, 28, 48), (96, 56, 96))]
+        kw = {} if clip_ids is None else {"clip_ids": clip_ids}
         if self.sample_type == "ddim":
-            return self.sample_ddim(x, vis_list, audio_embed)
+            return self.sample_ddim(x, vis_list, audio_embed, **kw)
         if self.sample_type in ("dpmsolver", "dpmsolver++"):
-            return self.sample_dpm_solver(x, vis_list, audio_embed)
+            return self.sample_dpm_solver(x, vis_list, audio_embed, **kw)
         if self.sample_type == "ddpm":
-            return self.sample_ddpm(x, vis_list, audio_embed)
+            return self.sample_ddpm(x, vis_list, audio_embed, **kw)
         raise NotImplementedError(self.sample_type)
 
 

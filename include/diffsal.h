@@ -771,6 +771,39 @@ int diffsal_resize_update(const float* s_low, const float* x, const float* m_pre
                           int N, int h, int w, int H, int W, float ex, float e0, float A, float c0, float c1,
                           diffsal_stream_t stream);
 
+/* ---- sampler noise from a counter-based generator (Philox4x32-10; beyond the reference, which draws x_T and the per-step
+ * noise of its stochastic samplers from torch's stateful generator: R/diffusion_trainer.py:476 randn_like in sample_ddim,
+ * :521 in p_sample, :119 x_T in prepare_data).  The value for (seed, clip id, draw, element) is a pure function, so a clip's noise
+ * does not depend on the batch it sits in, its position there or the number of devices of a sweep:
+ *   key     = (seed & 0xffffffff, seed >> 32)
+ *   counter = (q, draw, id & 0xffffffff, id >> 32)      q = e / 4, e = element index inside the clip's `per` elements;
+ *                                                       draw = 0 for x_T, s + 1 for the noise of step s
+ *   multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, ten rounds -> r0..r3 = elements 4q..4q+3
+ *   normals: u1 = ((r0 >> 8) + 1) * 2^-24, u2 = (r1 >> 8) * 2^-24, z0 = sqrt(-2 ln u1) cos(2 pi u2), z1 = sqrt(-2 ln u1) sin(2 pi u2);
+ *            z2, z3 from (r2, r3) in the same way; |z| <= 5.77
+ * `seed` points to ONE 64-bit word and `ids` to N 64-bit clip ids IN DEVICE MEMORY: a captured graph is replayed for other
+ * clips or another seed by rewriting those two buffers.  An id is used as its 64-bit pattern; callers keep ids non-negative
+ * (the library cannot read them before the launch; the Python binding checks host-side ids).  1 <= per <= 2^34.
+ *   philox_bits    out[N][per] raw 32-bit words (a test aid)
+ *   philox_normal  out[N][per] = scale * z */
+int diffsal_philox_bits(unsigned int* out, int N, long per, const long long* ids, const unsigned long long* seed,
+                        unsigned int draw, diffsal_stream_t stream);
+int diffsal_philox_normal(float* out, int N, long per, const long long* ids, const unsigned long long* seed,
+                          unsigned int draw, float scale, diffsal_stream_t stream);
+/* resize_update with a direct x0 term and in-kernel noise: the whole tail of a DDIM (eta >= 0) or DDPM ancestral step
+ * (R/diffusion_trainer.py:459-478, :508-527) in the denoiser's last kernel.
+ *   x0 = bilinear(s_low);  m = ex * x + e0 * x0;  x_next = b0 * x0 + A * x + cz * z + c0 * m + c1 * m_prev
+ * summed in that order, a term whose coefficient is 0 left out, the first product rounded and every further term one fma;
+ * z = the normals of (seed, ids[n], draw) for per = H * W, generated in place when cz != 0 (ids / seed may be NULL otherwise).
+ * With b0 = cz = 0 this is diffsal_resize_update's A * x + c0 * m [+ c1 * m_prev], bit for bit; with cz != 0 it equals
+ * diffsal_resize_update(x_next = NULL), diffsal_philox_normal(scale = 1) and diffsal_axpbypcz calls in the order above.
+ *   DDIM: ex = r/rm1, e0 = -1/rm1, A = 0, b0 = sqrt(abar_next), cz = c1(eta), c0 = c2;  DDPM: ex = 0, e0 = 1, A = coef2,
+ *   b0 = coef1, cz = exp(0.5 logvar) (0 at t = 0), c0 = 0. */
+int diffsal_resize_update_noise(const float* s_low, const float* x, const float* m_prev, float* x0_out, float* m_out,
+                                float* x_next, int N, int h, int w, int H, int W, float ex, float e0, float A, float b0,
+                                float c0, float c1, float cz, const long long* ids, const unsigned long long* seed,
+                                unsigned int draw, diffsal_stream_t stream);
+
 /* ---- K16 tail: loss, gradient clipping and the optimizer, on flat fp32 buffers -------------
  * diffsal_reduce_blocks(): number of doubles the `part` scratch of the two reductions below must hold.
  *
