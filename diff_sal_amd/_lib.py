@@ -34,7 +34,7 @@ class Wino4Ext(C.Structure):
 
 # must equal diffsal_version() of the loaded binary: bumped whenever a signature or struct in include/diffsal.h changes,
 # so that a stale libdiffsal_hip.so is rejected instead of being called with the wrong argument lists
-ABI_VERSION = 45
+ABI_VERSION = 46
 
 
 SIGNATURES = {
@@ -158,6 +158,9 @@ SIGNATURES = {
     "diffsal_philox_bits": (c_i, [c_f, c_i, C.c_long, c_f, c_f, C.c_uint, c_f]),
     "diffsal_philox_normal": (c_i, [c_f, c_i, C.c_long, c_f, c_f, C.c_uint, c_fl, c_f]),
     "diffsal_resize_update_noise": (c_i, [c_f] * 6 + [c_i] * 5 + [c_fl] * 7 + [c_f, c_f, C.c_uint, c_f]),
+    "diffsal_train_prepare": (c_i, [c_f] * 5 + [C.c_long, c_fl, c_i, C.c_long] + [c_f] * 4 + [c_i, C.c_long, c_f]),
+    "diffsal_dropout_keyed": (c_i, [c_f, c_f, c_i, C.c_long, c_fl, c_f, c_f, c_i, c_f]),
+    "diffsal_train_key_advance": (c_i, [c_f, c_f]),
     "diffsal_saliency_metrics_ws_bytes": (c_sz, [c_i]),
     "diffsal_saliency_metrics_bwd": (c_i, [c_f, c_f, c_i, C.c_long, c_f, c_sz, c_f, c_f, c_f]),
     "diffsal_saliency_metrics": (c_i, [c_f, c_f, c_i, C.c_long, c_f, c_sz, c_f, c_f, c_f]),

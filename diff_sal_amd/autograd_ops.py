@@ -309,6 +309,24 @@ def dropout(x, p, seed):
     return DropoutFn.apply(x, p, seed) if p > 0 else x
 
 
+class DropoutKeyedFn(torch.autograd.Function):
+    """Dropout with the mask of (train key, sample ids, site): the backward reads the SAME device step word as the forward, so
+    the key's step is advanced only after backward (DiffusionTrainStep.optimizer_step)."""
+
+    @staticmethod
+    def forward(ctx, x, p, ids, key, site):
+        ctx.p, ctx.ids, ctx.key, ctx.site = p, ids, key, site
+        return ops.dropout_keyed(x, p, ids, key, site)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.dropout_keyed(dy.contiguous(), ctx.p, ctx.ids, ctx.key, ctx.site), None, None, None, None
+
+
+def dropout_keyed(x, p, ids, key, site):
+    return DropoutKeyedFn.apply(x, p, ids, key, site) if p > 0 else x
+
+
 class GeluFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

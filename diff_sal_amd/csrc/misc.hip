@@ -1100,6 +1100,96 @@ __global__ __launch_bounds__(256) void resize_update_noise_kernel(
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Training stream of the same generator (include/diffsal.h, "training noise"): the draw word is formed from the step count
+// in DEVICE memory, key = {seed, step}, so that a step needs nothing from the host.
+// ------------------------------------------------------------------------------------------------
+enum { TRAIN_DEQUANT = 0, TRAIN_NOISE = 1, TRAIN_TIMESTEP = 2, TRAIN_DROPOUT0 = 3 };
+enum { T_PER_SAMPLE = 0, T_BATCH = 1, T_FIXED = 2 };
+
+__device__ __forceinline__ uint32_t train_draw(const unsigned long long* __restrict__ key, uint32_t purpose) {
+  return 0x80000000u | (static_cast<uint32_t>(key[1]) << 4) | purpose;
+}
+
+// prepare_data in one launch: x0 = sal + dq z0, x_t = a[t] x0 + b[t] z1 with lincomb3's rounding sequence (bit-equal to
+// philox_kernel<true> + axpbypcz_kernel twice).  One thread = one quad of a sample; every thread of a sample derives the sample's
+// timestep itself (one more Philox call, no second launch and nothing to wait for) and the thread of quad 0 stores it.
+__global__ __launch_bounds__(256) void train_prepare_kernel(
+    const float* __restrict__ sal, const long long* __restrict__ ids, const unsigned long long* __restrict__ key,
+    const float* __restrict__ tab_a, const float* __restrict__ tab_b, uint32_t T, float dq, int t_mode, long long t_fixed,
+    float* __restrict__ x0_out, float* __restrict__ xt_out, long long* __restrict__ t_out, float* __restrict__ noise_out, long per,
+    long nq, long total, int vec) {
+  const uint32_t d_dq = train_draw(key, TRAIN_DEQUANT), d_nz = train_draw(key, TRAIN_NOISE), d_t = train_draw(key, TRAIN_TIMESTEP);
+  for (long i = static_cast<long>(blockIdx.x) * 256 + threadIdx.x; i < total; i += static_cast<long>(gridDim.x) * 256) {
+    const long n = i / nq;
+    const uint32_t q = static_cast<uint32_t>(i - n * nq);
+    long long t = t_fixed;
+    if (t_mode != T_FIXED) {
+      uint32_t r[4];
+      philox_quad(ids, key, t_mode == T_BATCH ? 0 : n, 0u, d_t, r);
+      t = static_cast<long long>((static_cast<unsigned long long>(r[0]) * T) >> 32);
+    }
+    if (q == 0) t_out[n] = t;
+    const float a = tab_a[t], b = tab_b[t];
+    const long e_first = static_cast<long>(q) * 4, base = n * per + e_first;
+    const int cnt = per - e_first < 4 ? static_cast<int>(per - e_first) : 4;
+    float s[4], z0[4] = {0.f, 0.f, 0.f, 0.f}, z1[4], x0[4], xt[4];
+    if (vec) {
+      const float4 v = ld4(sal + base);
+      s[0] = v.x; s[1] = v.y; s[2] = v.z; s[3] = v.w;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[j] = j < cnt ? sal[base + j] : 0.f;
+    }
+    if (dq != 0.f) philox_normal4(ids, key, n, q, d_dq, z0);
+    philox_normal4(ids, key, n, q, d_nz, z1);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      x0[j] = dq != 0.f ? lincomb3(1.f, s[j], dq, z0[j], true, 0.f, 0.f, false) : s[j];
+      xt[j] = lincomb3(a, x0[j], b, z1[j], true, 0.f, 0.f, false);
+    }
+    if (vec) {
+      st4(x0_out + base, make_float4(x0[0], x0[1], x0[2], x0[3]));
+      st4(xt_out + base, make_float4(xt[0], xt[1], xt[2], xt[3]));
+      if (noise_out) st4(noise_out + base, make_float4(z1[0], z1[1], z1[2], z1[3]));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j < cnt) {
+          x0_out[base + j] = x0[j];
+          xt_out[base + j] = xt[j];
+          if (noise_out) noise_out[base + j] = z1[j];
+        }
+    }
+  }
+}
+
+// Dropout whose mask is a function of (seed, step, sample id, site, element inside the sample): word e % 4 of the call
+// (e / 4, purpose 3 + site, id) against dropout_kernel's threshold.  The same call on dy is the backward.
+__global__ __launch_bounds__(256) void dropout_keyed_kernel(const float* __restrict__ x, float* __restrict__ out,
+                                                            const long long* __restrict__ ids,
+                                                            const unsigned long long* __restrict__ key, uint32_t site, float p,
+                                                            long per, long nq, long total) {
+  const float scale = 1.0f / (1.0f - p);
+  const unsigned thr = static_cast<unsigned>(p * 4294967296.0);
+  const uint32_t draw = train_draw(key, TRAIN_DROPOUT0 + site);
+  for (long i = static_cast<long>(blockIdx.x) * 256 + threadIdx.x; i < total; i += static_cast<long>(gridDim.x) * 256) {
+    const long n = i / nq;
+    const uint32_t q = static_cast<uint32_t>(i - n * nq);
+    uint32_t r[4];
+    philox_quad(ids, key, n, q, draw, r);
+    const long base = n * per + static_cast<long>(q) * 4;
+    const float4 v = ld4(x + base);
+    st4(out + base, make_float4(r[0] >= thr ? v.x * scale : 0.f, r[1] >= thr ? v.y * scale : 0.f,
+                                r[2] >= thr ? v.z * scale : 0.f, r[3] >= thr ? v.w * scale : 0.f));
+  }
+}
+
+// The step word of the train key, advanced in stream order after everything that read the old value.
+__global__ void train_key_advance_kernel(unsigned long long* __restrict__ key) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) key[1] = key[1] + 1ull;
+}
+
 // storage-type conversion (weights once per parameter version; fp32 <-> bf16 / fp16), round to nearest even
 template <typename S, typename D>
 __global__ __launch_bounds__(256) void cast_kernel(const S* __restrict__ src, D* __restrict__ dst, long n) {
@@ -1160,7 +1250,7 @@ extern "C" size_t diffsal_workspace_bytes(int op, const diffsal_conv_desc* d, co
   }
 }
 
-extern "C" int diffsal_version(void) { return 45; }  // = _lib.ABI_VERSION
+extern "C" int diffsal_version(void) { return 46; }  // = _lib.ABI_VERSION
 extern "C" const char* diffsal_last_error(void) { return g_err; }
 extern "C" const char* diffsal_last_gemm_kernel(void) { return g_kernel; }
 
@@ -1788,4 +1878,44 @@ extern "C" int diffsal_resize_update_noise(const float* s_low, const float* x, c
                      m_prev, x0_out, m_out, x_next, h, w, H, W, static_cast<float>(h) / static_cast<float>(H),
                      static_cast<float>(w) / static_cast<float>(W), ex, e0, A, b0, c0, c1, cz, ids, seed, draw, per, nq, total, vec);
   return check_launch("resize_update_noise");
+}
+
+extern "C" int diffsal_train_prepare(const float* sal, const long long* ids, const unsigned long long* key,
+                                     const float* sqrt_alphas_hat, const float* sqrt_one_minus_alphas_hat, long T, float dq_scale,
+                                     int t_mode, long t_fixed, float* x0, float* x_t, long long* t, float* noise, int B, long per,
+                                     diffsal_stream_t stream) {
+  DS_REQUIRE(sal && ids && key && sqrt_alphas_hat && sqrt_one_minus_alphas_hat && x0 && x_t && t, DIFFSAL_E_ARG,
+             "train_prepare: null argument");
+  DS_REQUIRE(B > 0 && per > 0 && per <= (1L << 34), DIFFSAL_E_SHAPE, "train_prepare: bad shape (B = %d, per = %ld; 1 <= per <= 2^34)",
+             B, per);
+  DS_REQUIRE(T > 0 && T <= (1L << 31), DIFFSAL_E_SHAPE, "train_prepare: T = %ld out of [1, 2^31]", T);
+  DS_REQUIRE(t_mode == T_PER_SAMPLE || t_mode == T_BATCH || t_mode == T_FIXED, DIFFSAL_E_ARG, "train_prepare: t_mode %d", t_mode);
+  DS_REQUIRE(t_mode != T_FIXED || (t_fixed >= 0 && t_fixed < T), DIFFSAL_E_SHAPE, "train_prepare: fixed timestep %ld out of [0, %ld)",
+             t_fixed, T);
+  const long nq = (per + 3) / 4, total = static_cast<long>(B) * nq;
+  const int vec = per % 4 == 0 && aligned16(sal) && aligned16(x0) && aligned16(x_t) && (!noise || aligned16(noise));
+  hipLaunchKernelGGL(train_prepare_kernel, dim3(ew_grid(total)), dim3(256), 0, static_cast<hipStream_t>(stream), sal, ids, key,
+                     sqrt_alphas_hat, sqrt_one_minus_alphas_hat, static_cast<uint32_t>(T), dq_scale, t_mode,
+                     static_cast<long long>(t_fixed), x0, x_t, t, noise, per, nq, total, vec);
+  return check_launch("train_prepare");
+}
+
+extern "C" int diffsal_dropout_keyed(const float* x, float* out, int B, long per, float p, const long long* ids,
+                                     const unsigned long long* key, int site, diffsal_stream_t stream) {
+  DS_REQUIRE(x && out && ids && key, DIFFSAL_E_ARG, "dropout_keyed: null argument");
+  DS_REQUIRE(B > 0 && per > 0 && per % 4 == 0 && per <= (1L << 34), DIFFSAL_E_SHAPE,
+             "dropout_keyed: bad shape (B = %d, per = %ld; per a multiple of 4, at most 2^34)", B, per);
+  DS_REQUIRE(p >= 0.f && p < 1.f, DIFFSAL_E_SHAPE, "dropout_keyed: p=%f out of [0,1)", p);
+  DS_REQUIRE(site >= 0 && site < 13, DIFFSAL_E_ARG, "dropout_keyed: site %d out of [0, 13)", site);
+  DS_REQUIRE(aligned16(x) && aligned16(out), DIFFSAL_E_ALIGN, "dropout_keyed: misaligned pointer");
+  const long nq = per / 4, total = static_cast<long>(B) * nq;
+  hipLaunchKernelGGL(dropout_keyed_kernel, dim3(ew_grid(total)), dim3(256), 0, static_cast<hipStream_t>(stream), x, out, ids, key,
+                     static_cast<uint32_t>(site), p, per, nq, total);
+  return check_launch("dropout_keyed");
+}
+
+extern "C" int diffsal_train_key_advance(unsigned long long* key, diffsal_stream_t stream) {
+  DS_REQUIRE(key, DIFFSAL_E_ARG, "train_key_advance: null argument");
+  hipLaunchKernelGGL(train_key_advance_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), key);
+  return check_launch("train_key_advance");
 }

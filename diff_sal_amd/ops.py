@@ -1999,6 +1999,18 @@ def resize_update(s_low: Tensor, x: Tensor, m_prev: Optional[Tensor], ex: float,
 
 
 # ---- sampler noise from the counter-based generator (include/diffsal.h, "sampler noise") ----
+def _host_ids(ids, what: str):
+    """The ids as a checked host list, or None for a device tensor (taken as it is: reading it back would synchronise)."""
+    if isinstance(ids, Tensor) and ids.is_cuda:
+        if ids.dtype != torch.int64 or ids.dim() != 1:
+            raise ValueError(f"{what} ids must be a 1-D int64 tensor, got {ids.dtype} {tuple(ids.shape)}")
+        return None
+    host = [int(v) for v in (ids.reshape(-1).tolist() if isinstance(ids, Tensor) else ids)]
+    if any(v < 0 or v >= 1 << 63 for v in host):
+        raise ValueError(f"{what} ids must be non-negative int64 values, got {host}")
+    return host
+
+
 def noise_key(ids, seed, device) -> Tuple[Tensor, Tensor]:
     """(ids int64 [N], seed int64 [1]) on ``device``, the two buffers the noise kernels read.  Host-side ids (a sequence or a
     CPU tensor) are checked to be non-negative before they are uploaded; a device tensor is taken as it is (reading it back
@@ -2007,14 +2019,7 @@ def noise_key(ids, seed, device) -> Tuple[Tensor, Tensor]:
     if device.type != "cuda":
         raise RuntimeError("diff_sal_amd device noise runs on the GPU only (no CPU fallback); got device " + str(device))
     # everything is checked before anything is uploaded
-    host = None
-    if isinstance(ids, Tensor) and ids.is_cuda:
-        if ids.dtype != torch.int64 or ids.dim() != 1:
-            raise ValueError(f"clip ids must be a 1-D int64 tensor, got {ids.dtype} {tuple(ids.shape)}")
-    else:
-        host = [int(v) for v in (ids.reshape(-1).tolist() if isinstance(ids, Tensor) else ids)]
-        if any(v < 0 or v >= 1 << 63 for v in host):
-            raise ValueError(f"clip ids must be non-negative int64 values, got {host}")
+    host = _host_ids(ids, "clip")
     if isinstance(seed, Tensor):
         if not seed.is_cuda or seed.dtype != torch.int64 or seed.numel() != 1:
             raise ValueError("a seed tensor must be one int64 element on the GPU")
@@ -2094,6 +2099,117 @@ def resize_update_noise(s_low: Tensor, x: Tensor, m_prev: Optional[Tensor], ex: 
                                                    float(e0), float(A), float(b0), float(c0), float(c1), float(cz), ids_p, seed_p,
                                                    _draw(draw), _stream()), "resize_update_noise")
     return m, xn, x0
+
+
+# ---- training noise from the same generator (include/diffsal.h, "training noise") ----
+TRAIN_DEQUANT, TRAIN_NOISE, TRAIN_TIMESTEP, TRAIN_DROPOUT0 = 0, 1, 2, 3
+TRAIN_DROPOUT_SITES = 13
+_T_MODES = {"per_sample": 0, "batch": 1, "fixed": 2}
+
+
+def train_draw(step: int, purpose: int) -> int:
+    """Host mirror of the draw word the training kernels form on the device: 0x80000000 | (step << 4) | purpose."""
+    step, purpose = int(step), int(purpose)
+    if not 0 <= step < 1 << 27:
+        raise ValueError(f"training step must be in [0, 2^27) (the draw word holds 27 bits of it), got {step}")
+    if not 0 <= purpose < 16:
+        raise ValueError(f"purpose must be in [0, 16), got {purpose}")
+    return 0x80000000 | (step << 4) | purpose
+
+
+def _u64_pattern(v: int) -> int:
+    return v - (1 << 64) if v >= 1 << 63 else v
+
+
+def train_key(seed: int, step: int, device) -> Tensor:
+    """The train key {seed, step}: two int64 words on ``device`` that the training kernels read (written from the host here:
+    construction and checkpoint loading only; inside a step the step word is advanced by ``train_key_advance``)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("diff_sal_amd device noise runs on the GPU only (no CPU fallback); got device " + str(device))
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError(f"seed must be in [0, 2^64), got {seed}")
+    train_draw(step, 0)
+    return torch.tensor([_u64_pattern(seed), int(step)], dtype=torch.int64).to(device)
+
+
+def sample_ids(ids, device, count: Optional[int] = None) -> Tensor:
+    """Sample ids as the int64 device tensor the training kernels read: a host sequence is checked to be non-negative and
+    uploaded, an int64 GPU tensor is taken as it is."""
+    host = _host_ids(ids, "sample")
+    n = ids.numel() if host is None else len(host)
+    if count is not None and n != count:
+        raise ValueError(f"sample ids: {n} given for {count} samples (one id per sample)")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("diff_sal_amd device noise runs on the GPU only (no CPU fallback); got device " + str(device))
+    return ids.contiguous() if host is None else torch.tensor(host, dtype=torch.int64).to(device)
+
+
+def _check_key(what: str, ids: Tensor, key: Tensor, B: int) -> None:
+    if not (isinstance(ids, Tensor) and ids.is_cuda and ids.dtype == torch.int64 and ids.is_contiguous() and ids.numel() == B):
+        raise ValueError(f"{what}: ids must be a contiguous int64 GPU tensor with one id per sample ({B})")
+    if not (isinstance(key, Tensor) and key.is_cuda and key.dtype == torch.int64 and key.is_contiguous() and key.numel() == 2):
+        raise ValueError(f"{what}: key must be the two-word int64 GPU tensor of train_key()")
+
+
+def train_prepare(sal: Tensor, ids: Tensor, key: Tensor, sqrt_alphas_hat: Tensor, sqrt_one_minus_alphas_hat: Tensor, *,
+                  dq_scale: float = 0.01, t_mode: str = "per_sample", t0: Optional[int] = None, want_noise: bool = True):
+    """prepare_data in one launch (include/diffsal.h: diffsal_train_prepare): sal [B, ...] fp32 -> (x0, x_t, t [B] int64, noise)
+    with x0 = sal + dq_scale z0, x_t = a[t] x0 + b[t] z1.  ``t_mode``: "per_sample", "batch" (every sample takes the draw of
+    ids[0]) or "fixed" (t = t0).  The two tables are fp32 GPU tensors of T entries."""
+    lib = _lib.load()
+    if t_mode not in _T_MODES:
+        raise ValueError(f"train_prepare: t_mode={t_mode!r} ({', '.join(_T_MODES)})")
+    if not sal.is_cuda:
+        raise RuntimeError("diff_sal_amd device noise runs on the GPU only (no CPU fallback); got a CPU tensor")
+    if sal.dtype != torch.float32 or not sal.is_contiguous() or sal.dim() < 1 or sal.numel() == 0:
+        raise ValueError("train_prepare: sal must be a non-empty contiguous fp32 tensor [B, ...]")
+    B = sal.shape[0]
+    per = sal.numel() // B
+    _check_key("train_prepare", ids, key, B)
+    T = sqrt_alphas_hat.numel()
+    for tab in (sqrt_alphas_hat, sqrt_one_minus_alphas_hat):
+        if not (tab.is_cuda and tab.dtype == torch.float32 and tab.is_contiguous() and tab.numel() == T):
+            raise ValueError("train_prepare: the coefficient tables must be contiguous fp32 GPU tensors of equal length")
+    if (t_mode == "fixed") != (t0 is not None):
+        raise ValueError("train_prepare: t0 goes with t_mode='fixed' and only with it")
+    if t0 is not None and not 0 <= int(t0) < T:
+        raise ValueError(f"train_prepare: t0={t0} out of [0, {T})")
+    x0, x_t = torch.empty_like(sal), torch.empty_like(sal)
+    noise = torch.empty_like(sal) if want_noise else None
+    t = torch.empty((B,), device=sal.device, dtype=torch.int64)
+    with _prof("K15", 0.0, _nb(sal, x0, x_t, noise)):
+        _lib.check(lib.diffsal_train_prepare(_p(sal), ids.data_ptr(), key.data_ptr(), _p(sqrt_alphas_hat), _p(sqrt_one_minus_alphas_hat),
+                                             T, float(dq_scale), _T_MODES[t_mode], 0 if t0 is None else int(t0), _p(x0), _p(x_t),
+                                             t.data_ptr(), _p(noise), B, per, _stream()), "train_prepare")
+    return x0, x_t, t, noise
+
+
+def dropout_keyed(x: Tensor, p: float, ids: Tensor, key: Tensor, site: int) -> Tensor:
+    """x [B, ...] -> x * keep / (1 - p) with the mask of (key, ids[n], dropout site, element inside the sample); the same call
+    on the output gradient is the backward (include/diffsal.h: diffsal_dropout_keyed)."""
+    lib = _lib.load()
+    if not x.is_cuda:
+        raise RuntimeError("diff_sal_amd device noise runs on the GPU only (no CPU fallback); got a CPU tensor")
+    if not 0 <= int(site) < TRAIN_DROPOUT_SITES:
+        raise ValueError(f"dropout_keyed: site {site} out of [0, {TRAIN_DROPOUT_SITES})")
+    x = x.contiguous()
+    B = x.shape[0]
+    _check_key("dropout_keyed", ids, key, B)
+    out = torch.empty_like(x)
+    with _prof("dropout", 0.0, _nb(x, out)):
+        _lib.check(lib.diffsal_dropout_keyed(_p(x), _p(out), B, x.numel() // max(B, 1), float(p), ids.data_ptr(), key.data_ptr(),
+                                             int(site), _stream()), "dropout_keyed")
+    return out
+
+
+def train_key_advance(key: Tensor) -> None:
+    """key[1] += 1 on the device, in stream order (after the backward that re-applied the masks of the old step)."""
+    if not (key.is_cuda and key.dtype == torch.int64 and key.is_contiguous() and key.numel() == 2):
+        raise ValueError("train_key_advance: key must be the two-word int64 GPU tensor of train_key()")
+    _lib.check(_lib.load().diffsal_train_key_advance(key.data_ptr(), _stream()), "train_key_advance")
 
 
 # ---- training of the encoders: forward variants that keep what the backward needs, and the backward kernels ----

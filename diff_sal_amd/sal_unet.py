@@ -17,6 +17,7 @@ Unlike the reference, ``forward`` never mutates ``feat_list`` (reference defect 
 """
 from __future__ import annotations
 
+import contextlib
 import math
 from typing import Dict, List, Optional, Sequence
 
@@ -922,15 +923,35 @@ class SalUNet(nn.Module):
     # ------------------------------------------------------------------ training forward
     dropout_p = 0.1          # ResnetBlock dropout (sal_unet.py:229); set to 0 for gradient-parity tests
     _dropout_calls = 0
+    _dropout_key = None      # (ids, key) for the duration of one forward: how the key reaches a SalUNet nested in another module
+
+    @contextlib.contextmanager
+    def dropout_key_scope(self, dropout_key):
+        """``forward`` calls inside take their dropout masks from ``dropout_key = (ids, key)`` (see ``forward_train``); used by
+        DiffusionTrainStep, whose model may be a VideoSaliencyModel that calls this module as ``decoder_net(x, t, ...)``."""
+        prev, self._dropout_key = self._dropout_key, dropout_key
+        try:
+            yield
+        finally:
+            self._dropout_key = prev
 
     def forward_train(self, x: Tensor, t: Tensor, feat_list: Sequence[Tensor], audio_feat_list: Optional[Tensor] = None,
-                      dropout_seed: Optional[int] = None) -> Tensor:
+                      dropout_seed: Optional[int] = None, dropout_key=None) -> Tensor:
         """Train-mode forward on the autograd tape: BatchNorm uses (per-rank) batch statistics and updates its
         running buffers, ResnetBlock dropout is active, every op is a torch.autograd.Function whose forward AND
         backward are HIP kernels (autograd_ops.py).  Same graph as ``forward``; less epilogue fusion because the
-        backward needs the pre-activation tensors."""
+        backward needs the pre-activation tensors.
+
+        Dropout masks.  Default: hashed from ``torch.initial_seed()``, a process-wide call counter and the flat element index
+        (``dropout_seed`` replaces the first two).  ``dropout_key = (ids [B] int64, key)`` with ``key = ops.train_key(seed, step)``
+        instead makes the mask of a sample a function of (seed, step, its id, ResnetBlock index, element inside the sample):
+        independent of the batch layout and replayable from a checkpoint (include/diffsal.h, "training noise")."""
         from . import autograd_ops as ag
 
+        if dropout_key is None:
+            dropout_key = self._dropout_key
+        if dropout_key is not None and dropout_seed is not None:
+            raise ValueError("SalUNet.forward_train: give dropout_seed or dropout_key, not both (two different mask streams)")
         if not x.is_cuda:
             raise RuntimeError("diff_sal_amd.SalUNet runs on the GPU only (no CPU fallback); got a CPU tensor")
         if self.compute_dtype != torch.float32:
@@ -942,7 +963,10 @@ class SalUNet(nn.Module):
             raise RuntimeError("SalUNet.forward_train: empty batch (BatchNorm batch statistics are undefined); "
                                "nn.BatchNorm2d raises for it too")
         ns, dec = self.num_stages, self.invpt_decoder
-        if dropout_seed is None:
+        if dropout_key is not None:
+            if len(self.res_encoder) > ops.TRAIN_DROPOUT_SITES:
+                raise RuntimeError(f"SalUNet.forward_train: the train key has room for {ops.TRAIN_DROPOUT_SITES} dropout sites")
+        elif dropout_seed is None:
             SalUNet._dropout_calls += 1
             dropout_seed = (torch.initial_seed() * 1000003 + SalUNet._dropout_calls) & (2 ** 63 - 1)
         pw = ops.pack_conv_weight_diff
@@ -978,7 +1002,10 @@ class SalUNet(nn.Module):
                         rowvec=tproj[:, off:off + co], w_raw=rb.conv1.weight)
             off += co
             h = ag.groupnorm_swish(h, rb.norm2.weight, rb.norm2.bias, 32, rb.norm2.eps)
-            h = ag.dropout(h, self.dropout_p, dropout_seed + 7919 * i)
+            if dropout_key is not None:
+                h = ag.dropout_keyed(h, self.dropout_p, dropout_key[0], dropout_key[1], i)
+            else:
+                h = ag.dropout(h, self.dropout_p, dropout_seed + 7919 * i)
             sc = f
             if hasattr(rb, "nin_shortcut"):
                 sc = ag.conv(f, pw(rb.nin_shortcut.weight), bias=rb.nin_shortcut.bias, w_dgrad=dgw(rb.nin_shortcut.weight))

@@ -22,11 +22,14 @@ is per-link bound, so few large messages beat DDP's 25 MB x many) and each bucke
 launched asynchronously from a post-accumulate hook as soon as its last gradient lands, overlapping the rest of
 backward.  Only parameters that can receive a gradient are exchanged (the reference buckets 72 M dead ones).
 The DDP mean is not a separate pass: 1/world is folded into the norm and Adam kernels.
+``noise_source="device"`` takes the step's random inputs -- both noises, the timestep, the dropout masks -- from the counter-based
+generator the sampler uses (include/diffsal.h, "training noise"): a pure function of (seed, step, sample id), drawn on the device.
 BatchNorm running statistics follow DDP's ``broadcast_buffers=True``: rank 0's buffers are broadcast (one flat
 message) at the start of each step.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
@@ -339,7 +342,23 @@ class DiffusionTrainStep:
 
     ``model`` is a ``diff_sal_amd.SalUNet`` (called as ``model(x_t, t, feat_list, audio)``) or a
     ``VideoSaliencyModel`` (called as ``model({"img", "input", "audio"}, t)``, R/diffusion_trainer.py:212-218).
-    Keyword names follow the YAML fields the reference trainer reads (R/cfgs/diffusion.yml:24-28, 39-60)."""
+    Keyword names follow the YAML fields the reference trainer reads (R/cfgs/diffusion.yml:24-28, 39-60).
+
+    ``training_target``: "x0" (default) or "noise" -- what the loss regresses the prediction onto, the reference's
+    ``train_obj = x if training_target == "x0" else noise`` (R/diffusion_trainer.py:215); ``DiffusionSampler`` has the same switch.
+
+    ``noise_source``: "torch" (default) is the reference's behaviour, bit for bit: ``torch.randn_like`` for the two noises, numpy's
+    global generator for the one ``t0`` of the rank batch, dropout hashed from ``torch.initial_seed()`` and a call counter.
+    "device" draws all of them from Philox4x32-10 keyed by ``seed`` and counted by (step, purpose, sample id) -- include/diffsal.h,
+    "training noise" -- in one fused prepare launch and keyed dropout kernels; ``step(..., sample_ids=...)`` then names each sample
+    (a host sequence, checked to be non-negative, or an int64 GPU tensor, which saves the upload), e.g. by its dataset index.
+    What a sample sees no longer depends on its position in the batch, the batch size, the rank count or the loader's order, and
+    a run continued from ``state_dict()`` by a fresh object built with the same ``seed`` sees what the uninterrupted run saw:
+    seed and step live in two 64-bit device words (``train_key``), the step word is advanced on the device after backward and
+    rewritten by ``load_state_dict``; no value travels from the host inside a step.
+    ``t_mode``: "batch" (default) keeps the reference's ONE timestep per rank batch (R/diffusion_trainer.py:111); with device
+    noise it is the draw of the FIRST sample id of the call, so it depends on the batch layout by nature.  "per_sample" -- the
+    ordinary DDPM recipe, device noise only -- gives every sample the timestep of its own id."""
 
     def __init__(self, model: nn.Module, *, lr: float = 1e-4, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
                  weight_decay: float = 0.0, grad_clip: float = 1.0, mse_weight: float = 1.0,
@@ -347,7 +366,21 @@ class DiffusionTrainStep:
                  num_diffusion_timesteps: int = 1000, gaussian_dequantization: bool = True,
                  bucket_mb: float = 32.0, process_group=None, broadcast_buffers: bool = True,
                  store_clipped_grad: bool = False, exchange_single_rank: bool = False,
-                 loss_fn: Optional[Callable] = None, loss_config=None, exchange: str = "allreduce"):
+                 loss_fn: Optional[Callable] = None, loss_config=None, exchange: str = "allreduce",
+                 noise_source: str = "torch", seed: int = 0, t_mode: str = "batch", training_target: str = "x0"):
+        if noise_source not in ("torch", "device"):
+            raise ValueError(f"DiffusionTrainStep: noise_source={noise_source!r} (torch or device)")
+        if t_mode not in ("batch", "per_sample"):
+            raise ValueError(f"DiffusionTrainStep: t_mode={t_mode!r} (batch or per_sample)")
+        if training_target not in ("x0", "noise"):
+            raise ValueError(f"DiffusionTrainStep: training_target={training_target!r} (x0 or noise)")
+        if t_mode == "per_sample" and noise_source != "device":
+            raise ValueError("DiffusionTrainStep: t_mode='per_sample' needs noise_source='device': the torch path draws ONE t0 "
+                             "per rank batch from numpy's global generator, as the reference does, and has no per-sample draw")
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"DiffusionTrainStep: seed must be in [0, 2^64), got {seed}")
+        self.noise_source, self.seed, self.t_mode, self.training_target = noise_source, seed, t_mode, training_target
         self.model = model
         self.grad_clip, self.mse_weight = float(grad_clip), float(mse_weight)
         if loss_fn is not None and loss_config is not None:
@@ -376,6 +409,16 @@ class DiffusionTrainStep:
         self.step_count = 0
         self.last_norm: Optional[Tensor] = None
         self._rng = np.random  # the reference draws t0 from numpy's global generator (diffusion_trainer.py:111)
+        # device noise: the train key {seed, step} and the two coefficient tables, uploaded once (the tables are the very fp32
+        # tensors the torch path reads its by-value coefficients from, so both paths multiply by the same bits)
+        self.train_key: Optional[Tensor] = None
+        dev = self.flat.flat_p.device
+        if noise_source == "device" and dev.type == "cuda":
+            from . import ops
+
+            self.train_key = ops.train_key(seed, 0, dev)
+            self._tab_a = self.sqrt_alphas_hat.to(torch.float32).contiguous().to(dev)
+            self._tab_b = self.sqrt_one_minus_alphas_hat.to(torch.float32).contiguous().to(dev)
 
     # hyper-parameters live in the optimizer face's single parameter group (what a scheduler rewrites)
     def _hp(self, key):
@@ -393,11 +436,34 @@ class DiffusionTrainStep:
         return self.optimizer.param_groups
 
     # ---- R/diffusion_trainer.py:78-120 (training branch) ----
-    def prepare_data(self, sal_maps: Tensor, *, t0: Optional[int] = None, noise: Optional[Tensor] = None,
-                     dequant_noise: Optional[Tensor] = None):
-        """sal_maps [B,1,H,W] in [0,1] -> (x0, x_t, t [B] int64, noise)."""
+    def _sample_ids(self, sample_ids, sal_maps: Tensor) -> Tensor:
+        """Argument rules of the device-noise path, then the ids as an int64 tensor next to ``sal_maps``."""
         from . import ops
 
+        if sample_ids is None:
+            raise ValueError("DiffusionTrainStep: noise_source='device' needs sample_ids (one non-negative id per sample)")
+        ids = ops.sample_ids(sample_ids, sal_maps.device, sal_maps.shape[0])       # raises for a CPU tensor, after the id checks
+        if self.train_key is None:
+            raise RuntimeError("diff_sal_amd device noise runs on the GPU only (no CPU fallback); the model is on the CPU")
+        return ids
+
+    def prepare_data(self, sal_maps: Tensor, *, t0: Optional[int] = None, noise: Optional[Tensor] = None,
+                     dequant_noise: Optional[Tensor] = None, sample_ids=None):
+        """sal_maps [B,1,H,W] in [0,1] -> (x0, x_t, t [B] int64, noise).  With device noise: ``sample_ids`` names the samples,
+        ``noise`` / ``dequant_noise`` cannot be given, ``t0`` fixes the timestep of all samples, and the call is a pure function
+        of (seed, step_count, ids) -- calling it twice before a step returns the same tensors."""
+        from . import ops
+
+        if self.noise_source == "device":
+            if noise is not None or dequant_noise is not None:
+                raise ValueError("DiffusionTrainStep: noise= / dequant_noise= cannot be given with noise_source='device' "
+                                 "(the noise is drawn on the device from seed, step and sample_ids)")
+            ids = self._sample_ids(sample_ids, sal_maps)
+            mode = "fixed" if t0 is not None else self.t_mode
+            return ops.train_prepare(sal_maps.contiguous().float(), ids, self.train_key, self._tab_a, self._tab_b,
+                                     dq_scale=0.01 if self.gaussian_dequantization else 0.0, t_mode=mode, t0=t0)
+        if sample_ids is not None:
+            raise ValueError("DiffusionTrainStep: sample_ids mean nothing to torch's generator; use noise_source='device'")
         x = sal_maps.contiguous().float()
         if self.gaussian_dequantization:
             dq = torch.randn_like(x) if dequant_noise is None else dequant_noise
@@ -410,14 +476,19 @@ class DiffusionTrainStep:
         x_t = ops.axpbypcz(x, float(self.sqrt_alphas_hat[t0]), noise, float(self.sqrt_one_minus_alphas_hat[t0]))
         return x, x_t, t, noise
 
-    def _forward(self, x_t: Tensor, t: Tensor, cond: Dict) -> Tensor:
+    def _forward(self, x_t: Tensor, t: Tensor, cond: Dict, dropout_key=None) -> Tensor:
         from .sal_unet import SalUNet
 
-        if isinstance(self.model, SalUNet):
-            return self.model(x_t, t, cond["feat_list"], cond.get("audio_feat"))
-        data = dict(cond)
-        data["input"] = x_t
-        return self.model(data, t)
+        with contextlib.ExitStack() as scope:
+            if dropout_key is not None:      # every denoiser in the module tree, the one nested in a VideoSaliencyModel included
+                for m in self.model.modules():
+                    if isinstance(m, SalUNet):
+                        scope.enter_context(m.dropout_key_scope(dropout_key))
+            if isinstance(self.model, SalUNet):
+                return self.model(x_t, t, cond["feat_list"], cond.get("audio_feat"))
+            data = dict(cond)
+            data["input"] = x_t
+            return self.model(data, t)
 
     def _flatten_buffers(self) -> None:
         """Floating-point buffers (BatchNorm running statistics) become views into ONE flat tensor, once: the per-step broadcast
@@ -454,9 +525,18 @@ class DiffusionTrainStep:
         for b in others:           # none in the reference's model; kept exact for foreign modules
             dist.broadcast(b, src=src, group=self.group)
 
-    def loss_and_backward(self, x0: Tensor, x_t: Tensor, t: Tensor, cond: Dict) -> Tensor:
-        """Forward + loss + backward + gradient exchange; leaves the rank-SUMMED gradient in ``flat.flat_g``."""
+    def loss_and_backward(self, x0: Tensor, x_t: Tensor, t: Tensor, cond: Dict, sample_ids=None) -> Tensor:
+        """Forward + loss + backward + gradient exchange; leaves the rank-SUMMED gradient in ``flat.flat_g``.  ``x0`` is the
+        regression target (the forward-process noise when ``training_target="noise"``).  With device noise ``sample_ids`` key
+        the dropout masks (required then); the masks of forward and backward both read the device step word, which
+        ``optimizer_step`` advances afterwards."""
         from . import autograd_ops as ag
+
+        dropout_key = None
+        if self.noise_source == "device":
+            dropout_key = (self._sample_ids(sample_ids, x_t), self.train_key)
+        elif sample_ids is not None:
+            raise ValueError("DiffusionTrainStep: sample_ids mean nothing to torch's generator; use noise_source='device'")
 
         self.model.train()
         if self.broadcast_buffers:
@@ -466,7 +546,7 @@ class DiffusionTrainStep:
         from . import ops
 
         with ops.batched_packs():        # every parameter's kernel layouts (forward, data-gradient) rebuilt by one launch
-            pred = self._forward(x_t, t, cond)
+            pred = self._forward(x_t, t, cond, dropout_key)
             if self.loss_fn is None:
                 loss = ag.mse_loss(pred, x0, self.mse_weight / x0.shape[0])
                 self.last_losses = None
@@ -487,6 +567,9 @@ class DiffusionTrainStep:
     def optimizer_step(self) -> None:
         from . import ops
 
+        if self.train_key is not None:
+            ops.train_draw(self.step_count + 1, 0)     # the host mirror of the draw word's 27-bit step field
+            ops.train_key_advance(self.train_key)      # same stream as backward, so after the last reader of the old step
         self.step_count += 1
         gscale = 1.0 / self.world
         norm = ops.grad_norm(self.flat.flat_g, gscale) if self.grad_clip > 0 else None
@@ -502,10 +585,13 @@ class DiffusionTrainStep:
                 m.parameters_updated()
 
     def step(self, sal_maps: Tensor, cond: Dict, *, t0: Optional[int] = None, noise: Optional[Tensor] = None,
-             dequant_noise: Optional[Tensor] = None) -> Tensor:
-        """One training step on this rank's clips; returns the (detached, device-resident) loss."""
-        x0, x_t, t, _ = self.prepare_data(sal_maps, t0=t0, noise=noise, dequant_noise=dequant_noise)
-        loss = self.loss_and_backward(x0, x_t, t, cond)
+             dequant_noise: Optional[Tensor] = None, sample_ids=None) -> Tensor:
+        """One training step on this rank's clips; returns the (detached, device-resident) loss.  ``sample_ids``: one id per
+        sample, required with (and only with) ``noise_source="device"``."""
+        if self.noise_source == "device" and noise is None and dequant_noise is None:
+            sample_ids = self._sample_ids(sample_ids, sal_maps)        # checked and uploaded once for prepare and dropout
+        x0, x_t, t, nz = self.prepare_data(sal_maps, t0=t0, noise=noise, dequant_noise=dequant_noise, sample_ids=sample_ids)
+        loss = self.loss_and_backward(nz if self.training_target == "noise" else x0, x_t, t, cond, sample_ids=sample_ids)
         self.optimizer.step()          # the torch.optim.Optimizer face: step hooks and lr_scheduler bookkeeping see the step
         return loss
 
@@ -569,13 +655,21 @@ class DiffusionTrainStep:
             staged.append((k, p, st))
         if len(steps) > 1:
             raise ValueError(f"per-parameter step counts differ ({sorted(steps)}): the flat optimizer keeps one step count")
+        step_count = steps.pop() if steps else 0
+        new_key = None
+        if self.train_key is not None:
+            from . import ops
+
+            new_key = ops.train_key(self.seed, step_count, self.train_key.device)      # checks the step's range
         self.flat.exp_avg.zero_()
         self.flat.exp_avg_sq.zero_()
         for k, p, st in staged:
             o = self.flat.offsets[k]
             self.flat.exp_avg[o:o + p.numel()].view(p.shape).copy_(st["exp_avg"])
             self.flat.exp_avg_sq[o:o + p.numel()].view(p.shape).copy_(st["exp_avg_sq"])
-        self.step_count = steps.pop() if steps else 0
+        if new_key is not None:
+            self.train_key.copy_(new_key)          # the stream continues where the checkpointed run stopped
+        self.step_count = step_count
         g0 = groups[0]
         self.lr = float(g0.get("lr", self.lr))
         self.betas = tuple(float(b) for b in g0.get("betas", self.betas))

@@ -804,6 +804,40 @@ int diffsal_resize_update_noise(const float* s_low, const float* x, const float*
                                 float c0, float c1, float cz, const long long* ids, const unsigned long long* seed,
                                 unsigned int draw, diffsal_stream_t stream);
 
+/* ---- training noise: the training step's inputs from the same generator (K16; beyond the reference, which draws the two
+ * noises from torch's stateful generator, t0 from numpy's global one and the dropout masks from torch's:
+ * R/diffusion_trainer.py:106-117, 122-137, R/datasets/__init__.py:8-25, R/models/saliency_decoder/sal_unet.py:109,133).
+ * Philox4x32-10, key, counter and Box-Muller exactly as in "sampler noise" above; only the meaning of the words is new:
+ *   id    = a caller-supplied non-negative 64-bit SAMPLE id (e.g. the dataset index of the clip), not the position in the batch
+ *   draw  = 0x80000000 | (step << 4) | purpose     step = optimizer steps completed before this one, < 2^27; bit 31 keeps
+ *                                                  the stream apart from the sampler's draws 0, 1, 2, ... under one seed
+ *   purpose 0 dequantisation noise, 1 forward-process noise, 2 timestep, 3 + i dropout site i (i < 13)
+ *   timestep t = (uint64(r0) * T) >> 32, r0 = word 0 of the call (q = 0, purpose 2); T <= 2^31
+ * `key` points to TWO consecutive 64-bit words IN DEVICE MEMORY, {seed, step}: the kernels form `draw` from the device step,
+ * so a step takes no value from the host.  What a sample sees is a pure function of (seed, step, id): independent of the
+ * batch it sits in, its position there and the rank count, and a run resumed from (seed, step) continues the stream.
+ *
+ * train_prepare: the whole of prepare_data in one launch.  sal [B][per], ids [B]; the two tables hold T floats each.
+ *     x0 = sal + dq_scale * z0   (dq_scale = 0: x0 = sal, no draw)      z0 = normals of purpose 0
+ *     x_t = a[t] * x0 + b[t] * z1                                        z1 = normals of purpose 1 (also written to `noise`,
+ *                                                                        which may be NULL), a / b = the two tables
+ *   t_mode 0: every sample draws its own t from its id; 1: every sample uses the draw of ids[0] (the reference's one t0 per
+ *   rank batch -- by nature a function of the batch layout); 2: t = t_fixed for all.  t [B] int64 is written once per sample.
+ *   Rounded as diffsal_axpbypcz rounds (first product, then one fma): bit-equal to diffsal_philox_normal(scale = 1) for the
+ *   two draws followed by diffsal_axpbypcz(sal, 1, z0, dq_scale) and diffsal_axpbypcz(x0, a[t], z1, b[t]).  1 <= per <= 2^34;
+ *   16-byte accesses when per % 4 == 0 and the pointers are aligned, element-wise otherwise.
+ * dropout_keyed: out = x * keep / (1 - p) on x [B][per], per % 4 == 0 (DIFFSAL_E_SHAPE otherwise), 16-byte aligned.
+ *   Element e of sample n is kept iff word e % 4 of the call (q = e / 4, purpose 3 + site, ids[n]) >= (unsigned)(p * 2^32),
+ *   diffsal_dropout's threshold rule.  The same call on dy is the backward.
+ * train_key_advance: key[1] += 1, one thread, in stream order: enqueue it after the last reader of the old step (the
+ *   backward re-applies the dropout masks). */
+int diffsal_train_prepare(const float* sal, const long long* ids, const unsigned long long* key, const float* sqrt_alphas_hat,
+                          const float* sqrt_one_minus_alphas_hat, long T, float dq_scale, int t_mode, long t_fixed, float* x0,
+                          float* x_t, long long* t, float* noise, int B, long per, diffsal_stream_t stream);
+int diffsal_dropout_keyed(const float* x, float* out, int B, long per, float p, const long long* ids,
+                          const unsigned long long* key, int site, diffsal_stream_t stream);
+int diffsal_train_key_advance(unsigned long long* key, diffsal_stream_t stream);
+
 /* ---- K16 tail: loss, gradient clipping and the optimizer, on flat fp32 buffers -------------
  * diffsal_reduce_blocks(): number of doubles the `part` scratch of the two reductions below must hold.
  *
