@@ -407,4 +407,27 @@ __device__ __forceinline__ void epi_gelu_grad(float (&v)[4], float4 r) {
   v[0] *= gelu_erf_grad(r.x); v[1] *= gelu_erf_grad(r.y); v[2] *= gelu_erf_grad(r.z); v[3] *= gelu_erf_grad(r.w);
 }
 
+
+// Philox4x32-10 of include/diffsal.h ("sampler noise"): key = the seed's two halves, counter = (quad, draw, id lo, id hi).  The
+// seed and the ids are read from device memory so that a captured graph can be replayed for other clips.
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
+                                              uint32_t (&r)[4]) {
+#pragma unroll
+  for (int i = 0; i < 10; ++i) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
+}
+
+__device__ __forceinline__ void philox_quad(const long long* __restrict__ ids, const unsigned long long* __restrict__ seed,
+                                            long n, uint32_t q, uint32_t draw, uint32_t (&r)[4]) {
+  const unsigned long long sd = seed[0], id = static_cast<unsigned long long>(ids[n]);
+  philox4x32_10(q, draw, static_cast<uint32_t>(id), static_cast<uint32_t>(id >> 32), static_cast<uint32_t>(sd),
+                static_cast<uint32_t>(sd >> 32), r);
+}
+
 }  // namespace diffsal

@@ -960,26 +960,6 @@ __global__ __launch_bounds__(256) void resize_update_kernel(const float* __restr
 // by (quad, draw, clip id).  One thread = one quad of four consecutive elements of a clip; the seed and the ids are read from
 // device memory so that a captured graph can be replayed for other clips.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&r)[4]) {
-#pragma unroll
-  for (int i = 0; i < 10; ++i) {
-    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  r[0] = c0; r[1] = c1; r[2] = c2; r[3] = c3;
-}
-
-__device__ __forceinline__ void philox_quad(const long long* __restrict__ ids, const unsigned long long* __restrict__ seed,
-                                            long n, uint32_t q, uint32_t draw, uint32_t (&r)[4]) {
-  const unsigned long long sd = seed[0], id = static_cast<unsigned long long>(ids[n]);
-  philox4x32_10(q, draw, static_cast<uint32_t>(id), static_cast<uint32_t>(id >> 32), static_cast<uint32_t>(sd),
-                static_cast<uint32_t>(sd >> 32), r);
-}
-
 // Box-Muller on two words: both uniforms are exact in fp32 (24 bits; u1 in (0, 1], u2 in [0, 1)) and the angle goes to
 // sincospi as 2 u2, exact as well, so the only roundings are those of log, sqrt, sincospi and the final products.
 __device__ __forceinline__ void box_muller(uint32_t ra, uint32_t rb, float& za, float& zb) {
@@ -1250,7 +1230,7 @@ extern "C" size_t diffsal_workspace_bytes(int op, const diffsal_conv_desc* d, co
   }
 }
 
-extern "C" int diffsal_version(void) { return 46; }  // = _lib.ABI_VERSION
+extern "C" int diffsal_version(void) { return 47; }  // = _lib.ABI_VERSION
 extern "C" const char* diffsal_last_error(void) { return g_err; }
 extern "C" const char* diffsal_last_gemm_kernel(void) { return g_kernel; }
 

@@ -1971,6 +1971,60 @@ def saliency_metrics(pred: Tensor, gt: Tensor, keep_ws: bool = False):
     return mean, per
 
 
+EVAL_JUDD, EVAL_BORJI, EVAL_SAUC, EVAL_CC, EVAL_NSS, EVAL_SIM, EVAL_JITTER = 1, 2, 4, 8, 16, 32, 64      # DIFFSAL_EVAL_*
+EVAL_ROWS = ("auc_judd", "auc_borji", "auc_shuffled", "cc", "nss", "sim")      # rows of diffsal_eval_metrics' output
+
+
+def _u8(t: Optional[Tensor], what: str, shape):
+    if t is None:
+        return None
+    if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous() or tuple(t.shape) != tuple(shape):
+        raise ValueError(f"eval_metrics: {what} must be a contiguous uint8 GPU tensor of shape {tuple(shape)}, got {t.dtype} "
+                         f"{t.device} {tuple(t.shape)}")
+    return t.data_ptr()
+
+
+def eval_metrics(pred: Tensor, fix: Optional[Tensor], gt: Optional[Tensor], other: Optional[Tensor], terms: int, *, n_rep: int = 0,
+                 step: float = 0.1, rand_borji: Optional[Tensor] = None, rand_sauc: Optional[Tensor] = None,
+                 ids: Optional[Tensor] = None, seed: Optional[Tensor] = None) -> Tensor:
+    """``diffsal_eval_metrics`` (include/diffsal.h, "benchmark metrics") on pred [B, n] fp32, fix / other [B, n] uint8, gt [B, n]
+    fp32 -> [6, B] float64 in the order of EVAL_ROWS; rows whose EVAL_* bit is not in ``terms`` hold NaN.  rand_* are int32
+    [B, n_rep, cap] location tables (-1 = unused); ids / seed the int64 device buffers of ``noise_key``."""
+    lib = _lib.load()
+    if pred.dim() != 2:
+        raise ValueError(f"eval_metrics: pred must be [B, n], got {tuple(pred.shape)}")
+    B, n = pred.shape
+    if gt is not None and gt.shape != pred.shape:
+        raise ValueError(f"eval_metrics: gt {tuple(gt.shape)} vs pred {tuple(pred.shape)}")
+    cap = 0
+    for r in (rand_borji, rand_sauc):
+        if r is None:
+            continue
+        if not r.is_cuda or r.dtype != torch.int32 or not r.is_contiguous() or r.dim() != 3 or r.shape[:2] != (B, int(n_rep)):
+            raise ValueError(f"eval_metrics: rand_index must be a contiguous int32 GPU tensor [B={B}, n_rep={n_rep}, cap], got "
+                             f"{r.dtype} {r.device} {tuple(r.shape)}")
+        if cap and r.shape[2] != cap:
+            raise ValueError("eval_metrics: the two rand_index tables must share cap")
+        cap = r.shape[2]
+    for t, what in ((ids, "ids"), (seed, "seed")):
+        if t is not None and not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous()):
+            raise ValueError(f"eval_metrics: {what} must be a contiguous int64 GPU tensor")
+    if ids is not None and ids.numel() != B:
+        raise ValueError(f"eval_metrics: {ids.numel()} ids for {B} images")
+    sweeps = bool(terms & (EVAL_BORJI | EVAL_SAUC))
+    nws = lib.diffsal_eval_metrics_ws_bytes(B, n, int(terms), int(n_rep) if sweeps else 0)
+    ws = torch.empty((max(nws, 16) // 8,), device=pred.device, dtype=torch.float64)
+    out = torch.full((6, B), float("nan"), device=pred.device, dtype=torch.float64)
+    with _prof("metrics", 0.0, _nb(pred, fix, gt, other)):
+        _lib.check(lib.diffsal_eval_metrics(_p(pred), _u8(fix, "fix", pred.shape), _p(gt), _u8(other, "other", pred.shape), B, n,
+                                            int(terms), int(n_rep), float(step),
+                                            None if rand_borji is None else rand_borji.data_ptr(),
+                                            None if rand_sauc is None else rand_sauc.data_ptr(), cap,
+                                            None if ids is None else ids.data_ptr(), None if seed is None else seed.data_ptr(),
+                                            ws.data_ptr(), nws, out.data_ptr(), _stream()), "eval_metrics")
+    return out
+
+
 def maxpool2d(x: Tensor, k: int = 2, stride: int = 2) -> Tensor:
     """MaxPool2d(k, stride) on NHWC (no padding)."""
     lib = _lib.load()

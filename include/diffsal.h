@@ -755,6 +755,57 @@ int diffsal_saliency_metrics_bwd(const float* pred, const float* gt, int B, long
 int diffsal_saliency_metrics(const float* pred, const float* gt, int B, long n, void* ws, size_t ws_bytes,
                              float* per_image, float* mean_out, diffsal_stream_t stream);
 
+/* ---- benchmark metrics on the device: AUC-Judd, AUC-Borji, shuffled AUC, CC, NSS, SIM per image -----------
+ * R/metrics/metrics.py:7-252 (same-shape case; resizing a prediction to the fixation map's resolution is not done here), which
+ * R/compute_metrics.py runs on PNG files in a pool of numpy processes.  pred [B][n] fp32 (n = H*W), fix [B][n] bytes (a pixel is
+ * fixated iff its byte is non-zero), gt [B][n] fp32 (CC, SIM), other [B][n] bytes (sAUC: fixations of other images).
+ * terms = sum of DIFFSAL_EVAL_*; out [6][B] fp64, row r = (judd, borji, sauc, cc, nss, sim)[r]; rows not asked for are left alone.
+ *   S = (s - min) / (max - min) in fp32, one subtraction and one IEEE division (R/metrics/utils.py:47 on a float32 map, bit for
+ *   bit); values that collapse to one float are ties.
+ *   judd   above_i = #{j : S_j >= S_i} per fixated pixel i; k = i's position in the descending order of the fixation values
+ *          (equal values consecutive); ROC points (0,0), ((above - k - 1) / (n - n_fix), (k + 1) / n_fix), (1,1); fp64 trapezoids
+ *   borji  n_rep repetitions; thresholds k * step (fp64, k < ceil(max / step), max over the fixation values and the repetition's
+ *          sampled values: numpy's arange length rule), compared in fp64; tp over the fixation values, fp over the sampled
+ *          values, both / n_fix; one trapezoid sum per repetition, their mean in index order.  ceil(1 / step) <= 1024
+ *   sauc   the same with the sampled locations taken from the fixated pixels of `other`
+ *   cc     Pearson coefficient of pred and gt;  nss  mean over fixated pixels of (s - mean) / std, population std;
+ *   sim    sum of min of the two maps after range, then sum normalisation -- all three in fp64 from the fp32 inputs
+ * Sampled locations: rand_borji / rand_sauc [B][n_rep][cap] int32, -1 = unused slot (out-of-range entries are ignored), or NULL
+ * for the device generator: Philox4x32-10, key and counter exactly as in "sampler noise" below, with
+ *   id    = a caller-supplied non-negative 64-bit IMAGE id (ids [B], seed [1]: device memory, as there)
+ *   draw  = 0x40000000 | purpose      bit 30 keeps evaluation apart from the sampler's draws 0, 1, 2, ... and the trainer's
+ *                                     bit-31 draws under one seed
+ *   purpose 0 jitter (DIFFSAL_EVAL_JITTER, metrics.py:44-45): element p (pixel index): s' = float(double(s) + u * 1e-7),
+ *             u = (word >> 8) * 2^-24; the range normalisation then uses min / max of s'.  Judd only: a call with the jitter
+ *             bit may not ask for borji / sauc (the reference does not jitter them)
+ *   purpose 1 borji: element p * n_rep + rep, p = linear index of a fixated pixel -> location (uint64(word) * n) >> 32
+ *   purpose 2 sauc:  element p * n_rep + rep, p = a fixated pixel of `other`, is that pixel's key for the repetition; the
+ *             repetition uses the min(n_fix, n_other) pixels with the smallest (word, p) pairs (sampling without replacement,
+ *             as the reference's permutation prefix)
+ *   element e is word e % 4 of the call with q = e / 4; n * n_rep <= 2^34.
+ * Deliberate definitions where the reference returns NaN or divides by zero: an image with no fixation, with every pixel
+ * fixated or with a flat map (max == min) gets NaN in judd, borji, sauc and nss (sauc also when `other` has no fixation); cc
+ * and sim are set to NaN for a flat pred or gt (the reference's 0 / 0; the kernel writes the NaN itself, since the fmin of the
+ * SIM sum would drop it).  Such an image does not disturb the others of the batch.
+ * Cost: judd makes n_fix * n compares and n_fix^2 rank compares per image; it is meant for eye-tracking maps with n_fix from a
+ * few to a few thousand.  Denser maps give correct results at a cost that grows to O(n^2) per image (seconds at 360 x 640).
+ * Integer counts and fixed-order fp64 sums: results are bit-reproducible.  ws >= diffsal_eval_metrics_ws_bytes(B, n, terms,
+ * n_rep) bytes for the same terms (n_rep is ignored without borji / sauc), 16-byte aligned: cc / nss / sim need a few KB; judd,
+ * borji and sauc need [B][n] 4-byte arrays (the normalised map, the fixation lists, the counts: 4, 3, 3 of them, 6 when all
+ * three are asked for, i.e. 24 B n bytes, 354 MB at B = 64, 360 x 640).  No allocation, no synchronisation, graph-safe. */
+#define DIFFSAL_EVAL_JUDD 1u
+#define DIFFSAL_EVAL_BORJI 2u
+#define DIFFSAL_EVAL_SAUC 4u
+#define DIFFSAL_EVAL_CC 8u
+#define DIFFSAL_EVAL_NSS 16u
+#define DIFFSAL_EVAL_SIM 32u
+#define DIFFSAL_EVAL_JITTER 64u
+size_t diffsal_eval_metrics_ws_bytes(int B, long n, unsigned int terms, int n_rep);
+int diffsal_eval_metrics(const float* pred, const unsigned char* fix, const float* gt, const unsigned char* other, int B, long n,
+                         unsigned int terms, int n_rep, double step, const int* rand_borji, const int* rand_sauc, int cap,
+                         const long long* ids, const unsigned long long* seed, void* ws, size_t ws_bytes, double* out,
+                         diffsal_stream_t stream);
+
 /* ---- K15: sampler elementwise update  out = a*x + b*y + c*z  (y, z may be NULL) -----------
  * scalar-coefficient axpys of R/diffusion_trainer.py:459-478 and R/models/dpm_solver/sampler.py:548-593,816-853. */
 int diffsal_axpbypcz(const float* x, const float* y, const float* z, float a, float b, float c, float* out,
