@@ -5,8 +5,9 @@ include/diffsal.h "benchmark metrics") scores a batch per call, per image, in fl
 
 Shapes and types: ``pred`` is ``[B, 1, H, W]`` or ``[B, H, W]`` (any floating type; computed from its fp32 values); fixation
 maps are bool, uint8 (fixated iff non-zero) or floating (fixated iff ``> 0.5``, the reference's rule); ``gt`` is a floating map.
-Every map must have ``pred``'s resolution: resizing a prediction to the fixation map's resolution (the reference's skimage
-bicubic ``resize``) is out of scope here and a shape mismatch raises.  There is no CPU path: CPU tensors raise.
+Every map must have ``pred``'s resolution: a shape mismatch raises here.  Quantising a prediction to 8 bits and resizing it to
+the fixation map's resolution (the reference's PNG export and skimage ``resize``) is ``postprocess.protocol_metrics``, which
+then calls this module.  There is no CPU path: CPU tensors raise.
 
 Random locations of AUC-Borji / sAUC come either from an explicit ``rand_index`` table (``[B, n_rep, cap]`` int32 pixel
 indices, -1 = unused: what parity with the reference uses) or from the device generator keyed by ``seed`` and a caller-supplied
@@ -52,7 +53,8 @@ def _flat_map(t: Optional[Tensor], hw, what: str, binary: bool):
     if t.dim() == 4 and t.shape[1] == 1:
         t = t[:, 0]
     if tuple(t.shape) != tuple(hw):
-        raise ValueError(f"eval_metrics: {what} {tuple(t.shape)} does not match pred {tuple(hw)} (resizing is out of scope)")
+        raise ValueError(f"eval_metrics: {what} {tuple(t.shape)} does not match pred {tuple(hw)} (resizing is out of scope "
+                         "here: postprocess.protocol_metrics resizes the prediction first)")
     t = t.reshape(hw[0], -1)
     if not binary:
         if not t.is_floating_point():

@@ -2025,6 +2025,50 @@ def eval_metrics(pred: Tensor, fix: Optional[Tensor], gt: Optional[Tensor], othe
     return out
 
 
+def map_to_u8(pred: Tensor, *, want_u8: bool = True, want_float: bool = False):
+    """``diffsal_map_to_u8`` (include/diffsal.h, "benchmark post-processing") on pred [B, n] fp32 -> (u8 [B, n] uint8 or None,
+    f [B, n] fp32 = byte / 255 or None)."""
+    lib = _lib.load()
+    if pred.dim() != 2 or not (want_u8 or want_float):
+        raise ValueError(f"map_to_u8: pred must be [B, n] and one output asked for, got {tuple(pred.shape)}")
+    B, n = pred.shape
+    u8 = torch.empty((B, n), device=pred.device, dtype=torch.uint8) if want_u8 else None
+    f = torch.empty((B, n), device=pred.device, dtype=torch.float32) if want_float else None
+    nws = lib.diffsal_map_to_u8_ws_bytes(B, n)
+    ws = torch.empty((max(nws, 16) // 8,), device=pred.device, dtype=torch.float64)
+    with _prof("metrics", 0.0, 2 * _nb(pred) + _nb(u8, f)):
+        _lib.check(lib.diffsal_map_to_u8(_p(pred), B, n, None if u8 is None else u8.data_ptr(), _p(f), ws.data_ptr(), nws, _stream()),
+                   "map_to_u8")
+    return u8, f
+
+
+def map_from_u8(u8: Tensor) -> Tensor:
+    """``diffsal_map_from_u8``: fp32 byte / 255 (one IEEE division per element) of a contiguous uint8 GPU tensor, same shape."""
+    lib = _lib.load()
+    if not u8.is_cuda or u8.dtype != torch.uint8 or not u8.is_contiguous() or u8.numel() == 0:
+        raise ValueError(f"map_from_u8: expected a non-empty contiguous uint8 GPU tensor, got {u8.dtype} {u8.device} {tuple(u8.shape)}")
+    f = torch.empty(u8.shape, device=u8.device, dtype=torch.float32)
+    with _prof("metrics", 0.0, _nb(u8, f)):
+        _lib.check(lib.diffsal_map_from_u8(u8.data_ptr(), u8.numel(), _p(f), _stream()), "map_from_u8")
+    return f
+
+
+def map_resize(x: Tensor, H: int, W: int, *, order: int = 3, clip: bool = True, out_f64: bool = False) -> Tensor:
+    """``diffsal_map_resize`` on x [B, h, w] fp32 -> [B, H, W] fp32 (fp64 with ``out_f64``: the value before the last rounding)."""
+    lib = _lib.load()
+    if x.dim() != 3:
+        raise ValueError(f"map_resize: x must be [B, h, w], got {tuple(x.shape)}")
+    B, h, w = x.shape
+    H, W, order, clip = int(H), int(W), int(order), 1 if clip else 0
+    out = torch.empty((B, H, W) if H > 0 and W > 0 else (0,), device=x.device, dtype=torch.float64 if out_f64 else torch.float32)
+    nws = lib.diffsal_map_resize_ws_bytes(B, h, w, order, clip)
+    ws = torch.empty((max(nws, 16) // 8,), device=x.device, dtype=torch.float64)
+    with _prof("metrics", 0.0, _nb(x, out)):
+        _lib.check(lib.diffsal_map_resize(_p(x), B, h, w, H, W, order, clip, 1 if out_f64 else 0, out.data_ptr(), ws.data_ptr(), nws,
+                                          _stream()), "map_resize")
+    return out
+
+
 def maxpool2d(x: Tensor, k: int = 2, stride: int = 2) -> Tensor:
     """MaxPool2d(k, stride) on NHWC (no padding)."""
     lib = _lib.load()

@@ -1,0 +1,157 @@
+"""From the sampler's map to the map the benchmark scores, on the device: the 8-bit export, the float map read back from it and
+the spline resize to the annotation's resolution (csrc/postprocess.hip, arithmetic in include/diffsal.h "benchmark
+post-processing").  The reference scores what it wrote to disk, not the tensor the sampler returned:
+
+* R/diffusion_trainer.py:898-935 quantises each prediction with ``normalize_data`` (R/util/utils.py:11-16) and writes a PNG:
+  ``to_uint8`` gives those bytes, ``save_predictions`` the files;
+* R/compute_metrics.py:9-26 reads the PNG back with ``plt.imread``, float32 = byte / 255: ``from_uint8``;
+* R/metrics/metrics.py:41-42,102-103,195-196,218-219,243-244 resizes that map to the annotation's shape with skimage
+  ``resize``, ``order=3, mode='reflect'`` for the AUCs, CC and SIM and the default ``order=1`` for NSS: ``resize``;
+* ``protocol_metrics`` chains the three in front of ``eval_metrics.benchmark_metrics`` without a host copy or a synchronisation.
+
+``resize`` computes ``scipy.ndimage.zoom(map, (H / h, W / w), order=order, mode='mirror', grid_mode=True)`` in float64 from the
+float32 input, clamps to the input's range (``clip``) and rounds once to float32; the tests hold it to scipy 1.15 to 1e-12
+before that rounding.  Two things could not be run where this module was written and rest on reading the sources:
+
+* skimage itself.  The claim is that skimage (>= 0.19) executes exactly that zoom call for an upscale and then clips.  A
+  downscale (where skimage adds an anti-aliasing Gaussian first) is not built and raises.
+* the reference's JPEG path.  For the audio-visual sets it writes ``pred_sal_%06d.jpg``; JPEG is lossy and depends on the
+  encoder, so it is not offered: ``save_predictions`` writes PNG only, in the file layout of the visual sets.
+
+Deliberate definition: a flat prediction (max == min; ``normalize_data`` divides by zero there) quantises to all zeros.
+GPU only: CPU tensors raise.
+"""
+from __future__ import annotations
+
+import os
+from typing import Dict, Optional, Sequence, Tuple
+
+import torch
+
+from . import eval_metrics as _em
+from . import ops
+
+Tensor = torch.Tensor
+
+
+def _map3(t: Tensor, what: str, floating: bool = True) -> Tensor:
+    """[B, 1, H, W] or [B, H, W] GPU tensor -> [B, H, W]"""
+    if not isinstance(t, Tensor) or not t.is_cuda:
+        raise RuntimeError(f"diff_sal_amd postprocess runs on the GPU only (no CPU fallback); {what} is on "
+                           f"{getattr(t, 'device', type(t).__name__)}")
+    if floating and not t.is_floating_point():
+        raise ValueError(f"postprocess: {what} must be a floating map, got {t.dtype}")
+    if t.dim() == 4 and t.shape[1] == 1:
+        t = t[:, 0]
+    if t.dim() != 3 or t.numel() == 0:
+        raise ValueError(f"postprocess: {what} must be a non-empty [B, 1, H, W] or [B, H, W], got {tuple(t.shape)}")
+    return t
+
+
+def to_uint8(pred: Tensor) -> Tensor:
+    """``normalize_data`` per image, bit for bit in float32: uint8 ``[B, H, W]``."""
+    p = _map3(pred, "pred")
+    B, H, W = p.shape
+    u8, _ = ops.map_to_u8(p.reshape(B, -1).float().contiguous())
+    return u8.view(B, H, W)
+
+
+def from_uint8(u8: Tensor) -> Tensor:
+    """What ``plt.imread`` returns for the 8-bit PNG: float32 byte / 255, ``[B, H, W]``."""
+    q = _map3(u8, "u8", floating=False)
+    if q.dtype != torch.uint8:
+        raise ValueError(f"postprocess: u8 must be uint8, got {q.dtype}")
+    return ops.map_from_u8(q.contiguous())
+
+
+def _size(size) -> Tuple[int, int]:
+    try:
+        H, W = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"postprocess: size must be (H, W), got {size!r}") from None
+    return H, W
+
+
+def resize(map: Tensor, size, *, order: int = 3, clip: bool = True, dtype: torch.dtype = torch.float32) -> Tensor:
+    """Spline resize of ``[B, H, W]`` maps to ``size = (H', W')`` (neither axis shorter than the input's): ``order`` 3 (cubic
+    B-spline) or 1 (linear), mirror boundary, ``clip`` to each image's input range.  float32; ``dtype=torch.float64`` returns the
+    value before the last rounding (what the tests compare with scipy)."""
+    m = _map3(map, "map")
+    if dtype not in (torch.float32, torch.float64):
+        raise ValueError(f"postprocess: dtype must be float32 or float64, got {dtype}")
+    H, W = _size(size)
+    if H < m.shape[1] or W < m.shape[2]:
+        raise ValueError(f"postprocess: resize {tuple(m.shape[1:])} -> {(H, W)} shrinks an axis; a downscale (skimage's anti-aliasing "
+                         "path) is not built")
+    return ops.map_resize(m.float().contiguous(), H, W, order=order, clip=clip, out_f64=dtype == torch.float64)
+
+
+def protocol_metrics(pred: Tensor, fix: Optional[Tensor], gt: Optional[Tensor] = None, other: Optional[Tensor] = None, *,
+                     quantize: bool = True, **benchmark_metrics_kwargs) -> Dict[str, Tensor]:
+    """The benchmark's numbers for the sampler's maps: quantise -> / 255 -> resize to the annotations' resolution when it differs
+    -> ``eval_metrics.benchmark_metrics`` (whose keyword arguments pass through).  ``fix``, ``gt`` and ``other`` share one
+    resolution, at least the prediction's on both axes.  As in the reference, the map NSS scores is resized with order 1 and the
+    map of the other metrics with order 3: when both kinds are asked for and the shapes differ, ``benchmark_metrics`` runs twice.
+    ``quantize=False`` scores the float map as it is.  ``{name: [B] float64}``; no host copy, no synchronisation: capturable."""
+    p = _map3(pred, "pred")
+    B, h, w = p.shape
+    if quantize:
+        _, f = ops.map_to_u8(p.reshape(B, -1).float().contiguous(), want_u8=False, want_float=True)
+        p = f.view(B, h, w)
+    target = None
+    for t, what in ((fix, "fix"), (gt, "gt"), (other, "other")):
+        if t is None:
+            continue
+        s = tuple(_map3(t, what, floating=False).shape)
+        if target is not None and s != target:
+            raise ValueError(f"postprocess: {what} {s} does not share the resolution of the other annotations {target}")
+        target = s
+    if target is None:
+        raise ValueError("postprocess: protocol_metrics needs at least one annotation map")
+    kw = dict(benchmark_metrics_kwargs)
+    if target == (B, h, w):
+        return _em.benchmark_metrics(p, fix, gt, other, **kw)
+    if target[0] != B:
+        raise ValueError(f"postprocess: {target[0]} annotation maps for {B} predictions")
+    want = set(_em.METRICS if kw.get("metrics") is None else kw.pop("metrics"))
+    kw.pop("metrics", None)
+    if not want <= set(_em.METRICS):
+        raise ValueError(f"postprocess: unknown metric(s) {sorted(want - set(_em.METRICS))}; choose from {_em.METRICS}")
+    if fix is None:
+        want -= {"auc_judd", "auc_borji", "auc_shuffled", "nss"}
+    if gt is None:
+        want -= {"cc", "sim"}
+    if other is None:
+        want -= {"auc_shuffled"}
+    if not want:
+        raise ValueError("postprocess: the inputs given allow none of the metrics asked for")
+    res: Dict[str, Tensor] = {}
+    cubic = tuple(k for k in _em.METRICS if k in want and k != "nss")
+    if cubic:
+        res.update(_em.benchmark_metrics(resize(p, target[1:], order=3), fix, gt, other, metrics=cubic, **kw))
+    if "nss" in want:
+        res.update(_em.benchmark_metrics(resize(p, target[1:], order=1), fix, metrics=("nss",)))
+    return {k: res[k] for k in _em.METRICS if k in res}
+
+
+def save_predictions(pred: Tensor, video_ids: Sequence, frame_ids: Sequence, root: str, *, fmt: str = "png"):
+    """The reference's ``save_img`` for the visual sets: ``<root>/<video id>/<frame id>.png`` holding ``to_uint8``'s bytes as an
+    8-bit greyscale PNG.  Only the bytes travel to the host.  Returns the paths written."""
+    if fmt != "png":
+        raise ValueError(f"postprocess: fmt {fmt!r} is not offered (the reference's JPEG for the audio-visual sets is lossy); use 'png'")
+    from PIL import Image
+
+    u8 = to_uint8(pred)
+    frame_ids = [int(f) for f in (frame_ids.reshape(-1).tolist() if isinstance(frame_ids, Tensor) else frame_ids)]
+    video_ids = list(video_ids)
+    if not (u8.shape[0] == len(video_ids) == len(frame_ids)):
+        raise ValueError(f"postprocess: {u8.shape[0]} predictions, {len(video_ids)} video ids, {len(frame_ids)} frame ids")
+    host = u8.cpu().numpy()
+    paths = []
+    for img, vid, fid in zip(host, video_ids, frame_ids):
+        d = os.path.join(root, str(vid))
+        os.makedirs(d, exist_ok=True)
+        path = os.path.join(d, f"{fid}.png")
+        Image.fromarray(img).save(path, format="PNG")      # 2-D uint8: mode "L"
+        paths.append(path)
+    return paths

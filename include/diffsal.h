@@ -756,7 +756,7 @@ int diffsal_saliency_metrics(const float* pred, const float* gt, int B, long n, 
                              float* per_image, float* mean_out, diffsal_stream_t stream);
 
 /* ---- benchmark metrics on the device: AUC-Judd, AUC-Borji, shuffled AUC, CC, NSS, SIM per image -----------
- * R/metrics/metrics.py:7-252 (same-shape case; resizing a prediction to the fixation map's resolution is not done here), which
+ * R/metrics/metrics.py:7-252 (same-shape case; resizing a prediction to the fixation map's resolution is diffsal_map_resize's, below), which
  * R/compute_metrics.py runs on PNG files in a pool of numpy processes.  pred [B][n] fp32 (n = H*W), fix [B][n] bytes (a pixel is
  * fixated iff its byte is non-zero), gt [B][n] fp32 (CC, SIM), other [B][n] bytes (sAUC: fixations of other images).
  * terms = sum of DIFFSAL_EVAL_*; out [6][B] fp64, row r = (judd, borji, sauc, cc, nss, sim)[r]; rows not asked for are left alone.
@@ -806,7 +806,50 @@ int diffsal_eval_metrics(const float* pred, const unsigned char* fix, const floa
                          const long long* ids, const unsigned long long* seed, void* ws, size_t ws_bytes, double* out,
                          diffsal_stream_t stream);
 
-/* ---- K15: sampler elementwise update  out = a*x + b*y + c*z  (y, z may be NULL) -----------
+/* ---- benchmark post-processing: the 8-bit export and the spline resize to the annotation's resolution -----------
+ * What stands between the sampler's fp32 map and the map R/metrics/metrics.py scores: R/diffusion_trainer.py:898-935 quantises
+ * each prediction with normalize_data (R/util/utils.py:11-16) and writes a PNG; R/compute_metrics.py:9-26 reads it back with
+ * plt.imread (float32 = byte / 255); R/metrics/metrics.py:41-42,102-103,195-196,218-219,243-244 resizes that map to the
+ * annotation's shape with skimage `resize`: order=3, mode='reflect' for the AUCs, CC and SIM, the default order=1 for NSS.
+ *
+ * diffsal_map_to_u8: pred [B][n] fp32 (n = h*w) -> u8 [B][n] bytes and / or f [B][n] fp32 (either may be NULL, not both).  Per
+ * image, in fp32, normalize_data bit for bit:
+ *   mn, mx = min, max of the image;  s = fl32(255 / fl32(mx - mn))  (one IEEE division)
+ *   q = (uint8) trunc(clamp(fl32(fl32(x - mn) * s), 0, 255));  f = fl32(q / 255)  (one IEEE division: imread of an 8-bit PNG)
+ * Deliberate definition: a flat image (mx == mn; the reference divides by zero there) gives q = 0 everywhere.  A NaN in the
+ * input is the caller's error and the result is then undefined.  ws >= diffsal_map_to_u8_ws_bytes(B, n) bytes, 16-byte aligned.
+ * diffsal_map_from_u8: f[i] = fl32(u8[i] / 255) for `total` elements.
+ *
+ * diffsal_map_resize: in [B][h][w] fp32 -> out [B][H][W], fp32 (out_f64 = 0) or fp64 (out_f64 = 1: the same arithmetic before
+ * its last rounding, for tests).  All arithmetic is fp64 from the fp32 inputs; the fp32 store is a single round-to-nearest.
+ *   position per axis  x = (o + 0.5) * (n / N) - 0.5                      scipy.ndimage.zoom's grid_mode=True
+ *   boundary           whole-sample mirror extension, period 2(n - 1):    j %= 2(n-1); if j > n-1: j = 2(n-1) - j
+ *                      (scipy mode='mirror' = numpy.pad 'reflect' = what skimage's mode='reflect' means)
+ *   order 1            linear between floor(x) and floor(x) + 1, separable
+ *   order 3            interpolating cubic B-spline: coefficients c with (c[i-1] + 4 c[i] + c[i+1]) / 6 = s[i] per axis under
+ *                      the same boundary, computed as c[i] = sqrt(3) * sum_{|k| <= 34} z^|k| s[mirror(i + k)], z = sqrt(3) - 2
+ *                      (|z|^34 < 2^-64), x axis first; then out = sum_{k = f-1 .. f+2} beta3(x - k) c[mirror(k)] per axis,
+ *                      f = floor(x), beta3(t) = (4 - 6 t^2 + 3 |t|^3) / 6 for |t| < 1, (2 - |t|)^3 / 6 for |t| < 2, else 0
+ *                      (evaluated as 6 beta3 per axis and one division of the pixel's sum by 36)
+ *   clip = 1           each output image is clamped to [min, max] of its own input image (skimage's clip=True default; the
+ *                      cubic overshoots)
+ * This is scipy.ndimage.zoom(in, (H/h, W/w), order=order, mode='mirror', grid_mode=True), which skimage (>= 0.19) runs for an
+ * upscale before it clips.  An output axis shorter than the input is DIFFSAL_E_SHAPE (skimage adds an anti-aliasing Gaussian
+ * there; not built), so is an input axis shorter than 2 or any axis above 32768; equal length is allowed (the same formula).
+ * order other than 1 or 3: DIFFSAL_E_ARG.  All argument checks precede the first launch.
+ * ws >= diffsal_map_resize_ws_bytes(B, h, w, order, clip) bytes, 16-byte aligned: order 3 keeps two [B][h][w] fp64 arrays
+ * (88 MB at B = 64, 224 x 384), clip a few KB; order 1 without clip needs none (ws may be NULL).
+ * min / max are exact and every sum has a fixed order: results are bit-reproducible and an image's result does not depend on
+ * the batch it is in.  No floating-point atomics, no allocation, no synchronisation, graph-safe. */
+size_t diffsal_map_to_u8_ws_bytes(int B, long n);
+int diffsal_map_to_u8(const float* pred, int B, long n, unsigned char* u8, float* f, void* ws, size_t ws_bytes,
+                      diffsal_stream_t stream);
+int diffsal_map_from_u8(const unsigned char* u8, long total, float* f, diffsal_stream_t stream);
+size_t diffsal_map_resize_ws_bytes(int B, int h, int w, int order, int clip);
+int diffsal_map_resize(const float* in, int B, int h, int w, int H, int W, int order, int clip, int out_f64, void* out, void* ws,
+                       size_t ws_bytes, diffsal_stream_t stream);
+
+/* ---- K15: sampler elementwise update out = a*x + b*y + c*z  (y, z may be NULL) -----------
  * scalar-coefficient axpys of R/diffusion_trainer.py:459-478 and R/models/dpm_solver/sampler.py:548-593,816-853. */
 int diffsal_axpbypcz(const float* x, const float* y, const float* z, float a, float b, float c, float* out,
                      size_t n, diffsal_stream_t stream);
