@@ -34,7 +34,7 @@ class Wino4Ext(C.Structure):
 
 # must equal diffsal_version() of the loaded binary: bumped whenever a signature or struct in include/diffsal.h changes,
 # so that a stale libdiffsal_hip.so is rejected instead of being called with the wrong argument lists
-ABI_VERSION = 48
+ABI_VERSION = 49
 
 
 SIGNATURES = {
@@ -171,6 +171,9 @@ SIGNATURES = {
     "diffsal_map_from_u8": (c_i, [c_f, C.c_long, c_f, c_f]),
     "diffsal_map_resize_ws_bytes": (c_sz, [c_i] * 5),
     "diffsal_map_resize": (c_i, [c_f] + [c_i] * 8 + [c_f, c_f, c_sz, c_f]),
+    "diffsal_logmel_table_doubles": (C.c_long, []),
+    "diffsal_logmel": (c_i, [c_f, c_i, c_i, C.c_long, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_f]),
+    "diffsal_audio_examples": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
     "diffsal_reduce_partials": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     "diffsal_norm_finalize_fwd": (c_i, [c_f] * 7 + [c_i, c_i, c_i, C.c_double, C.c_double] + [c_f] * 4 + [c_fl, c_fl, c_f]),
     "diffsal_norm_finalize_bwd": (c_i, [c_f] * 8 + [c_i, c_i, c_i, C.c_double, c_f]),

@@ -2069,6 +2069,32 @@ def map_resize(x: Tensor, H: int, W: int, *, order: int = 3, clip: bool = True, 
     return out
 
 
+def logmel(wav: Tensor, wav_dtype: int, wav_len: Optional[Tensor], video: Optional[Tensor], starts: Tensor, ends: Tensor, B: int,
+           window: int, n_frames: int, tables: Tensor, *, out_f64: bool = False, sample_rate: int = 16000) -> Tensor:
+    """``diffsal_logmel`` (include/diffsal.h, "audio front end") on wav [V, Lmax] -> log-mel [B, n_frames, 64] fp32 (fp64 with
+    ``out_f64``).  starts / ends / video are int32 [B], wav_len int64 [V], tables the fp64 table of ``audio_input.device_tables``."""
+    lib = _lib.load()
+    V, Lmax = wav.shape
+    out = torch.empty((B, max(int(n_frames), 0), 64), device=wav.device, dtype=torch.float64 if out_f64 else torch.float32)
+    with _prof("audio_input", 2.0 * 2 * 235 * 400 * B * n_frames, _nb(wav, out)):
+        _lib.check(lib.diffsal_logmel(wav.data_ptr(), wav_dtype, V, Lmax, None if wav_len is None else wav_len.data_ptr(),
+                                      None if video is None else video.data_ptr(), starts.data_ptr(), ends.data_ptr(), B, int(sample_rate),
+                                      int(window), int(n_frames), tables.data_ptr(), 1 if out_f64 else 0, out.data_ptr(), _stream()),
+                   "logmel")
+    return out
+
+
+def audio_examples(lm: Tensor, exists: Optional[Tensor], n_examples: int, h: int, w: int) -> Tensor:
+    """``diffsal_audio_examples`` on log-mel [B, F, 64] fp32 -> [B, 1, 9, h, w] fp32: the nine examples, bilinearly resized."""
+    lib = _lib.load()
+    B, F, _ = lm.shape
+    out = torch.empty((B, 1, 9, h, w) if h > 0 and w > 0 else (0,), device=lm.device, dtype=torch.float32)
+    with _prof("audio_input", 0.0, _nb(lm, out)):
+        _lib.check(lib.diffsal_audio_examples(_p(lm), None if exists is None else exists.data_ptr(), B, F, int(n_examples), h, w, _p(out),
+                                              _stream()), "audio_examples")
+    return out
+
+
 def maxpool2d(x: Tensor, k: int = 2, stride: int = 2) -> Tensor:
     """MaxPool2d(k, stride) on NHWC (no padding)."""
     lib = _lib.load()

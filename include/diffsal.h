@@ -849,6 +849,54 @@ size_t diffsal_map_resize_ws_bytes(int B, int h, int w, int order, int clip);
 int diffsal_map_resize(const float* in, int B, int h, int w, int H, int W, int order, int clip, int out_f64, void* out, void* ws,
                        size_t ws_bytes, diffsal_stream_t stream);
 
+/* ---- audio front end: PCM samples in device memory -> the audio tensor [B][1][9][h][w] forward_vggish reads -----------
+ * What the reference does per clip on the host in numpy: R/datasets/saliency_db.py:449-497 (get_mel_feature) cuts
+ * wav[starts[a] : ends[b] + 1] out of the video's waveform (the table of R/datasets/saliency_db.py:208-222), centres it in a
+ * zero buffer of `window` samples and calls R/datasets/torchvggish/vggish_input.py:30-82 (waveform_to_examples), which frames
+ * the log-mel spectrogram of R/datasets/torchvggish/mel_features.py:71-223 into examples; get_mel_feature repeats them to nine
+ * and R/datasets/saliency_db.py:303-305,351-354 resizes each to half the frame size and stacks them.
+ * Input at 16000 Hz only: the reference's resampy step is not built and any other sample_rate is DIFFSAL_E_ARG.
+ *
+ * diffsal_logmel: wav [V][Lmax] of wav_dtype (int16 is divided by 32768, exactly; fp32; fp64), wav_len [V] valid samples per
+ * video (NULL: Lmax), video [B] the video of each clip (NULL: 0), starts / ends [B] -> out [B][n_frames][64], fp32 (out_f64 = 0)
+ * or fp64 (out_f64 = 1: the value before the rounding, for tests).  All arithmetic is fp64.  Per clip, with n = wav_len[video]:
+ *   lo = min(starts, n), hi = min(ends + 1, n), v = max(hi - lo, 0)              numpy's slice clamping
+ *   x[p] = wav[lo + p - off] for off <= p < off + v, else 0;  off = window/2 - v/2 (integer divisions; both parities of v)
+ *   frame f, bin k:  X = sum_{i < 400} x[160 f + i] * hann[i] * exp(-2 pi j i k / 512),  hann[i] = 0.5 - 0.5 cos(2 pi i / 400)
+ *   mel[f][m] = sum_k |X[f][k]| * M[k][m]        M: the 257 x 64 HTK mel matrix, 16 kHz, 125-7500 Hz (only bins 5..239 carry
+ *                                                weight, a band at most 17 of them), summed in ascending k
+ *   out[f][m] = log(mel[f][m] + 0.01)            frames 0 .. n_frames - 1 <= (window - 400) / 160
+ * The transform is a direct DFT in ascending i (no FFT); the caller checks v <= window (the reference fails there); an
+ * unchecked longer excerpt is centre-cropped, never read out of bounds.  `tables`: diffsal_logmel_table_doubles() fp64 values
+ * on the device, 16-byte aligned, built once by the caller:
+ *   [400][256][2]  hann[i] * (cos, sin)(2 pi i k / 512) for k = 5 + column, columns 235..255 zero
+ *   [64][17]       M[first[m] + 5 + j][m], j = 0..16 (zero past the band's last bin)
+ *   [64]           first[m]: the column of band m's first non-zero bin
+ *
+ * diffsal_audio_examples: logmel [B][n_frames][64] fp32, exists [B] bytes (NULL: all present) -> out [B][1][9][h][w] fp32.
+ *   n_examples = 1 + ((window - 400) / 160 + 1 - 64) / 11 of the window the log-mel came from; < 1 is DIFFSAL_E_SHAPE
+ *   output example j reads source example e = j if n_examples >= 9; otherwise, with r = 9 / n_examples,
+ *   e = j / r for j < n_examples * r, else (j - n_examples * r) / r      (repeat_interleave, then cat with the head of the
+ *                                                                         repeated list, then [:9])
+ *   example e is log-mel frames 11 e .. 11 e + 63 (rows) x 64 bands (columns); n_frames >= 64 + 11 (min(n_examples, 9) - 1)
+ *   resize 64 x 64 -> h x w as F.interpolate(mode="bilinear", align_corners=False) on the CPU computes it in fp32, per axis
+ *     s = max(fma(fl32(64 / N), o + 0.5, -0.5), 0);  i0 = min(trunc(s), 63);  i1 = min(i0 + 1, 63);  w1 = s - i0;  w0 = 1 - w1
+ *     value = fma(w0, a, fl32(w1 * b)), columns first, then rows           (h = w = 64 returns the examples unchanged)
+ *     the plain form, with no anti-aliasing filter, for every h and w: for an upscale that is also what the antialiased form
+ *     computes; for h or w below 64 a torchvision whose tensor Resize defaults to antialias=True gives other values
+ *   a clip with exists[b] == 0 is zeros (the reference returns zeros, not log(0.01), for a video without audio)
+ * Both calls: every sum has a fixed order, results are bit-reproducible and a clip's result does not depend on the batch it is
+ * in.  No atomics, no allocation, no synchronisation, graph-safe.  All argument checks precede the launch. */
+#define DIFFSAL_WAV_I16 0
+#define DIFFSAL_WAV_F32 1
+#define DIFFSAL_WAV_F64 2
+long diffsal_logmel_table_doubles(void);
+int diffsal_logmel(const void* wav, int wav_dtype, int V, long Lmax, const long* wav_len, const int* video, const int* starts,
+                   const int* ends, int B, int sample_rate, int window, int n_frames, const double* tables, int out_f64, void* out,
+                   diffsal_stream_t stream);
+int diffsal_audio_examples(const float* logmel, const unsigned char* exists, int B, int n_frames, int n_examples, int h, int w,
+                           float* out, diffsal_stream_t stream);
+
 /* ---- K15: sampler elementwise update out = a*x + b*y + c*z  (y, z may be NULL) -----------
  * scalar-coefficient axpys of R/diffusion_trainer.py:459-478 and R/models/dpm_solver/sampler.py:548-593,816-853. */
 int diffsal_axpbypcz(const float* x, const float* y, const float* z, float a, float b, float c, float* out,
