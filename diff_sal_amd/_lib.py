@@ -34,7 +34,7 @@ class Wino4Ext(C.Structure):
 
 # must equal diffsal_version() of the loaded binary: bumped whenever a signature or struct in include/diffsal.h changes,
 # so that a stale libdiffsal_hip.so is rejected instead of being called with the wrong argument lists
-ABI_VERSION = 49
+ABI_VERSION = 50
 
 
 SIGNATURES = {
@@ -174,6 +174,11 @@ SIGNATURES = {
     "diffsal_logmel_table_doubles": (C.c_long, []),
     "diffsal_logmel": (c_i, [c_f, c_i, c_i, C.c_long, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_f]),
     "diffsal_audio_examples": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),
+    "diffsal_resample_ksize": (c_i, [c_i, c_i, c_i]),
+    "diffsal_resample_u8_band_rows": (c_i, [c_i] * 6),
+    "diffsal_resample_u8_ws_bytes": (c_sz, [c_i] * 8),
+    "diffsal_resample_u8": (c_i, [c_f] + [c_i] * 7 + [c_f, c_f, c_i, c_f, c_f, c_i, c_i, c_i, c_f, c_f, c_sz, c_f]),
+    "diffsal_clip_gather_u8": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_i, c_f, c_f, c_f]),
     "diffsal_reduce_partials": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_f]),
     "diffsal_norm_finalize_fwd": (c_i, [c_f] * 7 + [c_i, c_i, c_i, C.c_double, C.c_double] + [c_f] * 4 + [c_fl, c_fl, c_f]),
     "diffsal_norm_finalize_bwd": (c_i, [c_f] * 8 + [c_i, c_i, c_i, C.c_double, c_f]),

@@ -2095,6 +2095,68 @@ def audio_examples(lm: Tensor, exists: Optional[Tensor], n_examples: int, h: int
     return out
 
 
+FILTER_BILINEAR, FILTER_BICUBIC = 0, 1                      # DIFFSAL_FILTER_* of include/diffsal.h
+RESAMPLE_AUTO, RESAMPLE_FUSED, RESAMPLE_TWO_PASS = 0, 1, 2  # DIFFSAL_RESAMPLE_*
+
+
+def _u8_frames(t: Tensor, what: str) -> Tensor:
+    if not isinstance(t, Tensor) or not t.is_cuda:
+        raise RuntimeError(f"diff_sal_amd video_input runs on the GPU only (no CPU fallback); {what} is on "
+                           f"{getattr(t, 'device', type(t).__name__)}")
+    if t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] not in (1, 3) or t.numel() == 0:
+        raise ValueError(f"video_input: {what} must be a non-empty uint8 tensor [N, H, W, C] with C = 1 or 3, got {t.dtype} {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def resample_u8(frames: Tensor, H1: int, W1: int, filter_id: int, xtab, ytab, *, form: int = RESAMPLE_AUTO, band_rows: int = 0) -> Tensor:
+    """``diffsal_resample_u8`` (include/diffsal.h, "video front end") on frames [N, H0, W0, C] uint8 -> [N, H1, W1, C] uint8: one
+    Pillow ``Image.resize``.  xtab / ytab are (bounds int32 [n_out, 2], kk int32 [n_out, ksize]) on the device, or None for an
+    axis whose size does not change (``video_input.device_table``)."""
+    lib = _lib.load()
+    frames = _u8_frames(frames, "frames")
+    N, H0, W0, Cc = frames.shape
+    H1, W1 = int(H1), int(W1)
+    ptrs = []
+    for tab, n_out in ((xtab, W1), (ytab, H1)):
+        if tab is None:
+            ptrs += [None, None, 0]
+            continue
+        b, k = tab
+        for t in (b, k):
+            if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 2 or t.shape[0] != n_out:
+                raise ValueError(f"resample_u8: a table must be contiguous int32 GPU tensors with {n_out} rows, got {t.dtype} {t.device} "
+                                 f"{tuple(t.shape)}")
+        if b.shape[1] != 2:
+            raise ValueError(f"resample_u8: bounds must be [n_out, 2], got {tuple(b.shape)}")
+        ptrs += [b.data_ptr(), k.data_ptr(), k.shape[1]]
+    out = torch.empty((N, H1, W1, Cc) if H1 > 0 and W1 > 0 else (0,), device=frames.device, dtype=torch.uint8)
+    nws = lib.diffsal_resample_u8_ws_bytes(N, H0, W0, Cc, H1, W1, int(filter_id), int(form))
+    ws = torch.empty((nws,), device=frames.device, dtype=torch.uint8) if nws else None
+    with _prof("video_input", 0.0, _nb(frames, out) + 2 * nws):
+        _lib.check(lib.diffsal_resample_u8(frames.data_ptr(), N, H0, W0, Cc, H1, W1, int(filter_id), *ptrs, int(form), int(band_rows),
+                                           out.data_ptr(), None if ws is None else ws.data_ptr(), nws, _stream()), "resample_u8")
+    return out
+
+
+def clip_gather_u8(frames: Tensor, indices: Optional[Tensor], B: int, T: int, table: Tensor) -> Tensor:
+    """``diffsal_clip_gather_u8`` on frames [N, h, w, C] uint8, indices int32 [B, T] (None: frame b * T + t), table fp32 [C, 256]
+    -> fp32 [B, C, T, h, w] = table[c, frames[indices[b, t], y, x, c]]."""
+    lib = _lib.load()
+    frames = _u8_frames(frames, "frames")
+    N, h, w, Cc = frames.shape
+    if indices is not None and (not indices.is_cuda or indices.dtype != torch.int32 or not indices.is_contiguous()
+                                or indices.numel() != int(B) * int(T)):
+        raise ValueError(f"clip_gather_u8: indices must be a contiguous int32 GPU tensor of {B} x {T} entries, got {indices.dtype} "
+                         f"{indices.device} {tuple(indices.shape)}")
+    if tuple(table.shape) != (Cc, 256):
+        raise ValueError(f"clip_gather_u8: table must be [{Cc}, 256], got {tuple(table.shape)}")
+    out = torch.empty((B, Cc, T, h, w) if B > 0 and T > 0 else (0,), device=frames.device, dtype=torch.float32)
+    with _prof("video_input", 0.0, B * T * h * w * Cc + _nb(out)):
+        _lib.check(lib.diffsal_clip_gather_u8(frames.data_ptr(), N, h, w, Cc, None if indices is None else indices.data_ptr(), int(B), int(T),
+                                              _p(table), _p(out), _stream()), "clip_gather_u8")
+    return out
+
+
 def maxpool2d(x: Tensor, k: int = 2, stride: int = 2) -> Tensor:
     """MaxPool2d(k, stride) on NHWC (no padding)."""
     lib = _lib.load()

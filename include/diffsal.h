@@ -897,6 +897,56 @@ int diffsal_logmel(const void* wav, int wav_dtype, int V, long Lmax, const long*
 int diffsal_audio_examples(const float* logmel, const unsigned char* exists, int B, int n_frames, int n_examples, int h, int w,
                            float* out, diffsal_stream_t stream);
 
+/* ---- video front end: decoded uint8 frames in device memory -> the clip tensor [B][3][T][h][w] MViT reads -----------
+ * What the reference does per clip on the host with Pillow: R/datasets/saliency_db.py:29-36 (pil_loader) resizes every frame to
+ * 320 x 240 with Image.resize's default filter (bicubic); :292-296 applies Scale(sample_size) (bilinear), ToTensor(norm_value)
+ * and Normalize(mean, std); :382-394 stacks and permutes the frames.  R/datasets/meta_data.py:27-35 and
+ * R/datasets/dhf1k_data.py:72-81 run transforms.Resize on the PIL image (bilinear), ToTensor and Normalize.  The targets
+ * (saliency_db.py:298-301 target_transform, meta_data.py:32-35 sal_transform) are the same resize of an 'L' image and / 255.
+ * Decoding and convert('RGB' | 'L') stay with the caller.
+ *
+ * diffsal_resample_u8: in [N][H0][W0][C] bytes, C = 1 or 3 -> out [N][H1][W1][C] bytes: one Image.resize of Pillow's 8-bit path
+ * (ImagingResample), bit for bit.  The coefficients are the caller's, built in float64 as precompute_coeffs builds them, per
+ * axis (n_in -> n_out, filter support s0 = 1 bilinear, 2 bicubic with a = -0.5):
+ *   scale = n_in / n_out;  fs = max(scale, 1);  s = s0 * fs;  ksize = 2 * ceil(s) + 1  (= diffsal_resample_ksize)
+ *   output o:  c = (o + 0.5) * scale;  xmin = max(trunc(c - s + 0.5), 0);  count = min(trunc(c + s + 0.5), n_in) - xmin
+ *              w[t] = filter((t + xmin - c + 0.5) / fs) for t < count, divided by their sum (if it is not zero)
+ *   kk[o][t] = trunc(w[t] * 2^22 + 0.5)  (- 0.5 for a negative w[t]);  0 for count <= t < ksize
+ *   bounds [n_out][2] = (xmin, count),  kk [n_out][ksize], both int32, in device memory
+ * The kernels do integer work only.  Horizontal pass first, every channel alike:
+ *   mid[y][o] = clip8((2^21 + sum_{t < count} in[y][xmin + t] * kk[o][t]) >> 22)      int32 sum, arithmetic shift, clip to 0..255
+ * then the vertical pass the same way on the uint8 image `mid`.  An axis whose size does not change runs no pass (its tables may
+ * be NULL); equal sizes make the call a copy.  All N frames share the source size.
+ * form: DIFFSAL_RESAMPLE_FUSED is one launch: a workgroup owns band_rows output rows over the full width, resamples the source
+ * rows they need horizontally into LDS and runs the vertical pass out of LDS (band_rows = 0: the library picks it from the LDS
+ * budget, diffsal_resample_u8_band_rows; at most 32; DIFFSAL_E_SHAPE if the band does not fit in 160 KB).
+ * DIFFSAL_RESAMPLE_TWO_PASS keeps `mid` [N][H0][W1][C] in ws (diffsal_resample_u8_ws_bytes).  DIFFSAL_RESAMPLE_AUTO is the fused
+ * form where a band fits and H0 * W0 >= 2 * H1 * W1 (where it measured faster), else two passes.  The forms agree bit for bit;
+ * with a single pass they are the same launch.
+ * The tables cannot be checked from the host: the kernels clamp xmin to the source, count to ksize and to the source, and a
+ * band's row span to its LDS image, so a wrong table gives wrong pixels, never an access outside the buffers.
+ *
+ * diffsal_clip_gather_u8: frames [N][h][w][C] bytes, indices [B][T] int32 (NULL: frame b * T + t, B * T = N), table [C][256]
+ * fp32 -> out [B][C][T][h][w] fp32 with out[b][c][t][y][x] = table[c][frames[indices[b][t]][y][x][c]].  The table is how
+ * ToTensor and Normalize are matched bit for bit: the caller evaluates the reference's own float32 operations on the 256 byte
+ * values per channel (x / norm_value, then - mean, then / std) and the kernel only indexes.  C = 1, T = 1, indices NULL and
+ * table[v] = v / 255 is the target path.  An index outside [0, N) is clamped (check it on the host where it is known there).
+ * All calls: no atomics, no allocation, no synchronisation, bit-reproducible, graph-safe; all argument checks precede the
+ * launch. */
+#define DIFFSAL_FILTER_BILINEAR 0
+#define DIFFSAL_FILTER_BICUBIC 1
+#define DIFFSAL_RESAMPLE_AUTO 0
+#define DIFFSAL_RESAMPLE_FUSED 1
+#define DIFFSAL_RESAMPLE_TWO_PASS 2
+int diffsal_resample_ksize(int in_size, int out_size, int filter);      /* 0: bad argument */
+int diffsal_resample_u8_band_rows(int H0, int W0, int C, int H1, int W1, int filter);      /* 0: no band fits, or a single pass */
+size_t diffsal_resample_u8_ws_bytes(int N, int H0, int W0, int C, int H1, int W1, int filter, int form);
+int diffsal_resample_u8(const unsigned char* in, int N, int H0, int W0, int C, int H1, int W1, int filter, const int* xbounds,
+                        const int* xkk, int xks, const int* ybounds, const int* ykk, int yks, int form, int band_rows,
+                        unsigned char* out, void* ws, size_t ws_bytes, diffsal_stream_t stream);
+int diffsal_clip_gather_u8(const unsigned char* frames, int N, int h, int w, int C, const int* indices, int B, int T,
+                           const float* table, float* out, diffsal_stream_t stream);
+
 /* ---- K15: sampler elementwise update out = a*x + b*y + c*z  (y, z may be NULL) -----------
  * scalar-coefficient axpys of R/diffusion_trainer.py:459-478 and R/models/dpm_solver/sampler.py:548-593,816-853. */
 int diffsal_axpbypcz(const float* x, const float* y, const float* z, float a, float b, float c, float* out,
