@@ -34,7 +34,7 @@ class Wino4Ext(C.Structure):
 
 # must equal diffsal_version() of the loaded binary: bumped whenever a signature or struct in include/diffsal.h changes,
 # so that a stale libdiffsal_hip.so is rejected instead of being called with the wrong argument lists
-ABI_VERSION = 50
+ABI_VERSION = 51
 
 
 SIGNATURES = {
@@ -171,6 +171,10 @@ SIGNATURES = {
     "diffsal_map_from_u8": (c_i, [c_f, C.c_long, c_f, c_f]),
     "diffsal_map_resize_ws_bytes": (c_sz, [c_i] * 5),
     "diffsal_map_resize": (c_i, [c_f] + [c_i] * 8 + [c_f, c_f, c_sz, c_f]),
+    "diffsal_jpeg_capacity": (C.c_long, [c_i, c_i]),
+    "diffsal_jpeg_encode_ws_bytes": (c_sz, [c_i, c_i, c_i]),
+    "diffsal_jpeg_encode": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, C.c_long, c_f, c_f, c_f, c_sz, c_f]),
+    "diffsal_jpeg_roundtrip": (c_i, [c_f, c_i, c_i, c_i, c_i, c_f, c_f]),
     "diffsal_logmel_table_doubles": (C.c_long, []),
     "diffsal_logmel": (c_i, [c_f, c_i, c_i, C.c_long, c_f, c_f, c_f, c_f, c_i, c_i, c_i, c_i, c_f, c_i, c_f, c_f]),
     "diffsal_audio_examples": (c_i, [c_f, c_f, c_i, c_i, c_i, c_i, c_i, c_f, c_f]),

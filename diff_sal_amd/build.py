@@ -6,7 +6,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdiffsal_hip.so")
-SOURCES = ["igemm.hip", "igemm16.hip", "lin_stream.hip", "wgrad.hip", "backward.hip", "optim.hip", "pack.hip", "norm.hip", "misc.hip", "metrics.hip", "eval_metrics.hip", "postprocess.hip", "audio_input.hip", "video_input.hip", "attention.hip", "attn_fold.hip", "mvit.hip", "mvit_pool.hip", "block16.hip", "conv16_halo.hip", "conv16_dma.hip", "gemm16_dma.hip", "attn16_mfma.hip", "tapsum.hip", "tblock.hip", "wino.hip", "gemm_dma.hip", "wino4.hip", "upconv.hip"]
+SOURCES = ["igemm.hip", "igemm16.hip", "lin_stream.hip", "wgrad.hip", "backward.hip", "optim.hip", "pack.hip", "norm.hip", "misc.hip", "metrics.hip", "eval_metrics.hip", "postprocess.hip", "jpeg_export.hip", "audio_input.hip", "video_input.hip", "attention.hip", "attn_fold.hip", "mvit.hip", "mvit_pool.hip", "block16.hip", "conv16_halo.hip", "conv16_dma.hip", "gemm16_dma.hip", "attn16_mfma.hip", "tapsum.hip", "tblock.hip", "wino.hip", "gemm_dma.hip", "wino4.hip", "upconv.hip"]
+# headers only one translation unit includes: a change rebuilds that unit alone
+OWN_HEADERS = {"jpeg_export.hip": ["jpeg_core.h"]}
 
 
 def _hipcc():
@@ -37,7 +39,7 @@ def needs_build():
     deps = [os.path.join(CSRC, s) for s in SOURCES] + [
         os.path.join(CSRC, "common.h"),
         os.path.join(os.path.dirname(HERE), "include", "diffsal.h"),
-    ]
+    ] + [os.path.join(CSRC, h) for hs in OWN_HEADERS.values() for h in hs]
     # an installed copy may ship the binary without its sources: nothing to compare against, nothing to rebuild
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
 
@@ -70,7 +72,7 @@ def build_library(force=False, verbose=False):
     for s in SOURCES:
         src, o = os.path.join(CSRC, s), os.path.join(CSRC, s.replace(".hip", ".o"))
         objs.append(o)
-        if force or _stale(src, o, common):
+        if force or _stale(src, o, common + [os.path.join(CSRC, h) for h in OWN_HEADERS.get(s, ())]):
             todo.append([_hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"] + extra + ["-c", src, "-o", o])
     running, failed, jobs = [], [], _jobs()
     while todo or running:

@@ -2069,6 +2069,47 @@ def map_resize(x: Tensor, H: int, W: int, *, order: int = 3, clip: bool = True, 
     return out
 
 
+def _jpeg_u8(u8: Tensor, what: str):
+    if not u8.is_cuda or u8.dtype != torch.uint8 or not u8.is_contiguous() or u8.dim() != 3 or u8.numel() == 0:
+        raise ValueError(f"{what}: expected a non-empty contiguous uint8 GPU tensor [B, h, w], got {u8.dtype} {u8.device} {tuple(u8.shape)}")
+    return u8.shape
+
+
+def jpeg_capacity(h: int, w: int) -> int:
+    """``diffsal_jpeg_capacity``: the bytes no JPEG file of an h x w image can exceed (host arithmetic)."""
+    cap = _lib.load().diffsal_jpeg_capacity(int(h), int(w))
+    if cap <= 0:
+        raise ValueError(f"jpeg_capacity: {h} x {w} (1..65535 per axis)")
+    return cap
+
+
+def jpeg_encode(u8: Tensor, quality: int = 95, *, want_recon: bool = False):
+    """``diffsal_jpeg_encode`` (include/diffsal.h, "JPEG export") on u8 [B, h, w] uint8 -> (data [B, cap] uint8, lengths [B] int32,
+    recon [B, h, w] uint8 or None): image b's file is ``data[b, :lengths[b]]``."""
+    lib = _lib.load()
+    B, h, w = _jpeg_u8(u8, "jpeg_encode")
+    cap = jpeg_capacity(h, w)
+    data = torch.empty((B, cap), device=u8.device, dtype=torch.uint8)
+    lengths = torch.empty((B,), device=u8.device, dtype=torch.int32)
+    recon = torch.empty((B, h, w), device=u8.device, dtype=torch.uint8) if want_recon else None
+    nws = lib.diffsal_jpeg_encode_ws_bytes(B, h, w)
+    ws = torch.empty((max(nws, 16) // 8,), device=u8.device, dtype=torch.float64)
+    with _prof("metrics", 0.0, _nb(u8, recon) + 2 * nws):
+        _lib.check(lib.diffsal_jpeg_encode(u8.data_ptr(), B, h, w, int(quality), data.data_ptr(), cap, lengths.data_ptr(),
+                                           None if recon is None else recon.data_ptr(), ws.data_ptr(), nws, _stream()), "jpeg_encode")
+    return data, lengths, recon
+
+
+def jpeg_roundtrip(u8: Tensor, quality: int = 95) -> Tensor:
+    """``diffsal_jpeg_roundtrip``: the pixels a libjpeg decoder reads back from the file of each image, uint8 [B, h, w], one launch."""
+    lib = _lib.load()
+    B, h, w = _jpeg_u8(u8, "jpeg_roundtrip")
+    recon = torch.empty((B, h, w), device=u8.device, dtype=torch.uint8)
+    with _prof("metrics", 0.0, _nb(u8, recon)):
+        _lib.check(lib.diffsal_jpeg_roundtrip(u8.data_ptr(), B, h, w, int(quality), recon.data_ptr(), _stream()), "jpeg_roundtrip")
+    return recon
+
+
 def logmel(wav: Tensor, wav_dtype: int, wav_len: Optional[Tensor], video: Optional[Tensor], starts: Tensor, ends: Tensor, B: int,
            window: int, n_frames: int, tables: Tensor, *, out_f64: bool = False, sample_rate: int = 16000) -> Tensor:
     """``diffsal_logmel`` (include/diffsal.h, "audio front end") on wav [V, Lmax] -> log-mel [B, n_frames, 64] fp32 (fp64 with

@@ -15,8 +15,10 @@ before that rounding.  Two things could not be run where this module was written
 
 * skimage itself.  The claim is that skimage (>= 0.19) executes exactly that zoom call for an upscale and then clips.  A
   downscale (where skimage adds an anti-aliasing Gaussian first) is not built and raises.
-* the reference's JPEG path.  For the audio-visual sets it writes ``pred_sal_%06d.jpg``; JPEG is lossy and depends on the
-  encoder, so it is not offered: ``save_predictions`` writes PNG only, in the file layout of the visual sets.
+* the reference's JPEG path.  For the audio-visual sets it writes ``pred_sal_%06d.jpg`` with ``cv2.imwrite``.  That export is integer
+  arithmetic throughout and lives in ``diff_sal_amd.jpeg`` (files and read-back pixels, held to Pillow byte for byte; its docstring
+  says what rests on reading OpenCV's sources): ``protocol_metrics(..., quantize="jpeg")`` scores the map a decoder reads back from
+  that file, ``jpeg.save_predictions`` writes the files.  ``save_predictions`` here writes PNG only, in the layout of the visual sets.
 
 Deliberate definition: a flat prediction (max == min; ``normalize_data`` divides by zero there) quantises to all zeros.
 GPU only: CPU tensors raise.
@@ -87,15 +89,22 @@ def resize(map: Tensor, size, *, order: int = 3, clip: bool = True, dtype: torch
 
 
 def protocol_metrics(pred: Tensor, fix: Optional[Tensor], gt: Optional[Tensor] = None, other: Optional[Tensor] = None, *,
-                     quantize: bool = True, **benchmark_metrics_kwargs) -> Dict[str, Tensor]:
+                     quantize=True, **benchmark_metrics_kwargs) -> Dict[str, Tensor]:
     """The benchmark's numbers for the sampler's maps: quantise -> / 255 -> resize to the annotations' resolution when it differs
-    -> ``eval_metrics.benchmark_metrics`` (whose keyword arguments pass through).  ``fix``, ``gt`` and ``other`` share one
-    resolution, at least the prediction's on both axes.  As in the reference, the map NSS scores is resized with order 1 and the
+    -> ``eval_metrics.benchmark_metrics`` (whose keyword arguments pass through).  ``quantize="jpeg"`` is the audio-visual sets'
+    protocol: quantise -> the pixels read back from the JPEG file of that map (``jpeg.roundtrip``, quality 95) -> / 255 -> the rest
+    alike.  ``fix``, ``gt`` and ``other`` share one resolution, at least the prediction's on both axes.  As in the reference, the map NSS scores is resized with order 1 and the
     map of the other metrics with order 3: when both kinds are asked for and the shapes differ, ``benchmark_metrics`` runs twice.
     ``quantize=False`` scores the float map as it is.  ``{name: [B] float64}``; no host copy, no synchronisation: capturable."""
     p = _map3(pred, "pred")
     B, h, w = p.shape
-    if quantize:
+    if isinstance(quantize, str) and quantize == "jpeg":
+        from . import jpeg
+
+        p = from_uint8(jpeg.roundtrip(to_uint8(p)))
+    elif isinstance(quantize, str) or quantize not in (True, False):
+        raise ValueError(f"postprocess: quantize must be True, False or 'jpeg', got {quantize!r}")
+    elif quantize:
         _, f = ops.map_to_u8(p.reshape(B, -1).float().contiguous(), want_u8=False, want_float=True)
         p = f.view(B, h, w)
     target = None
@@ -138,7 +147,8 @@ def save_predictions(pred: Tensor, video_ids: Sequence, frame_ids: Sequence, roo
     """The reference's ``save_img`` for the visual sets: ``<root>/<video id>/<frame id>.png`` holding ``to_uint8``'s bytes as an
     8-bit greyscale PNG.  Only the bytes travel to the host.  Returns the paths written."""
     if fmt != "png":
-        raise ValueError(f"postprocess: fmt {fmt!r} is not offered (the reference's JPEG for the audio-visual sets is lossy); use 'png'")
+        raise ValueError(f"postprocess: fmt {fmt!r} is not offered (the reference's JPEG for the audio-visual sets is lossy: "
+                         "a map written that way is not this one; diff_sal_amd.jpeg.save_predictions writes those files); use 'png'")
     from PIL import Image
 
     u8 = to_uint8(pred)

@@ -849,6 +849,48 @@ size_t diffsal_map_resize_ws_bytes(int B, int h, int w, int order, int clip);
 int diffsal_map_resize(const float* in, int B, int h, int w, int H, int W, int order, int clip, int out_f64, void* out, void* ws,
                        size_t ws_bytes, diffsal_stream_t stream);
 
+/* ---- JPEG export: the 8-bit maps of the audio-visual sets -> the files the reference writes, and what it reads back -----------
+ * For AVAD, Coutrot, DIEM, ETMD and SumMe R/diffusion_trainer.py:898-935 (save_img, av_data=True) writes pred_sal_%06d.jpg with
+ * cv2.imwrite: 8-bit greyscale, baseline, quality 95, libjpeg's default slow-integer DCT, the standard tables.  Every step is
+ * integer arithmetic; in = the bytes of diffsal_map_to_u8, [B][h][w], 1 <= h, w <= 65535, quality 1..100.
+ *   geometry     8 x 8 blocks in raster order; the image is padded to multiples of 8 by repeating its last column, then its last row
+ *   table        s = 5000 / q for q < 50, else 200 - 2 q;  t[k] = clamp((base[k] * s + 50) / 100, 1, 255), integer divisions;
+ *                base = ITU-T T.81 Annex K.1 (luminance).  Quality 95: first row 2 1 1 2 2 4 5 6
+ *   forward DCT  libjpeg's jfdctint on sample - 128: CONST_BITS = 13, PASS1_BITS = 2, rows (outputs 0 and 4 times 4, the others
+ *                descaled by 11) then columns (outputs 0 and 4 descaled by 2, the others by 15), 32-bit integers,
+ *                DESCALE(x, n) = (x + (1 << (n - 1))) >> n, constants 2446 3196 4433 6270 7373 9633 12299 15137 16069 16819 20995
+ *                25172 (FIX(0.298631336) .. FIX(3.072711026)); the result carries a factor 8
+ *   quantiser    d = 8 t[k];  |c| <- (|c| + d / 2) / d, the sign put back
+ *   entropy      zig-zag order; DC as the difference from the block before it in the same image (0 before the first); Annex K.3
+ *                luminance DC and AC codes; ZRL (F0) for every 16 zeros of a run, EOB (00) when the block ends in zeros; a value
+ *                of category n is its low n bits, v - 1 for a negative v
+ *   bit stream   MSB first; the last byte filled with 1-bits; 00 behind every FF byte, a filled last byte included
+ *   file         SOI; APP0 JFIF 1.01, units 0, density 1 x 1, no thumbnail; DQT (table 0, 8-bit, zig-zag); SOF0 precision 8, h, w,
+ *                one component 01 11 00; DHT class 0 id 0; DHT class 1 id 0; SOS 01 01 00 00 3F 00; the scan; EOI.  328 bytes
+ *                stand in front of the scan.  Byte for byte what Pillow's Image.fromarray(u8).save(f, "JPEG", quality=q) writes.
+ *   read-back    coefficient times t[k]; libjpeg's jidctint, columns (descale 11) then rows (descale 18); libjpeg's range limit:
+ *                x + 128 clamped to 0..255, taken from a table indexed by the low 10 bits of x (the plain clamp for
+ *                -512 <= x <= 511)
+ * diffsal_jpeg_roundtrip: recon [B][h][w] = the read-back pixels, one launch, no workspace and no entropy coder: what scoring needs.
+ * diffsal_jpeg_encode: out [B][cap] bytes, cap >= diffsal_jpeg_capacity(h, w); image b's file is out[b][0 .. lengths[b]), the
+ * bytes behind it are undefined; recon as above or NULL; ws >= diffsal_jpeg_encode_ws_bytes(B, h, w) bytes, 16-byte aligned.
+ * Capacity is a bound, not an estimate: a block codes to at most (9 + 11) + 63 * (16 + 10) = 1658 bits (the categories are capped
+ * at 11 and 10, which no 8-bit image reaches), so with nblk = ceil(h / 8) * ceil(w / 8) and m = ceil(1658 nblk / 8)
+ *   diffsal_jpeg_capacity(h, w) = 328 + 2 m + 2 + 2      (every scan byte stuffed, EOI, two spare)
+ * and the workspace holds int16 [B][64][nblk] coefficients, per block a 32-bit AC bit count and a 64-bit bit offset, the bit
+ * stream of ceil(m / 4) 32-bit words per image and two 32-bit counts per 2048 stream bytes.  No kernel writes outside out[b][0 .. cap)
+ * or the workspace for any input bytes.  An image whose capacity passes 2^31 - 1 is DIFFSAL_E_SHAPE for encode (lengths are int32).
+ * Launches of encode: a clear of the bit stream (hipMemsetAsync on `stream`, every call), block transform, bit offsets (exclusive
+ * scan per image), pack (integer atomicOr into the shared words: order-independent), FF count, frame (scan of the counts, header,
+ * EOI, length), stuff.  Results are bit-reproducible and an image's bytes do not depend on the batch it is in.  No allocation, no
+ * synchronisation, no host copy, graph-safe; all argument checks precede the first launch. */
+long diffsal_jpeg_capacity(int h, int w);      /* 0: bad argument */
+size_t diffsal_jpeg_encode_ws_bytes(int B, int h, int w);
+int diffsal_jpeg_encode(const unsigned char* u8, int B, int h, int w, int quality, unsigned char* out, long cap, int* lengths,
+                        unsigned char* recon, void* ws, size_t ws_bytes, diffsal_stream_t stream);
+int diffsal_jpeg_roundtrip(const unsigned char* u8, int B, int h, int w, int quality, unsigned char* recon,
+                           diffsal_stream_t stream);
+
 /* ---- audio front end: PCM samples in device memory -> the audio tensor [B][1][9][h][w] forward_vggish reads -----------
  * What the reference does per clip on the host in numpy: R/datasets/saliency_db.py:449-497 (get_mel_feature) cuts
  * wav[starts[a] : ends[b] + 1] out of the video's waveform (the table of R/datasets/saliency_db.py:208-222), centres it in a
