@@ -36,7 +36,7 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import ops
+from . import _lib, ops
 
 Tensor = torch.Tensor
 
@@ -181,7 +181,7 @@ def warm(device) -> None:
     _tables(torch.device(device))
 
 
-_WAV_DTYPES = {torch.int16: 0, torch.float32: 1, torch.float64: 2}
+_WAV_DTYPES = dict(zip((torch.int16, torch.float32, torch.float64), _lib.constants("WAV_", "I16 F32 F64")))
 
 
 def _wav2(wav, wav_len, video):

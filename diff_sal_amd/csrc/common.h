@@ -37,13 +37,17 @@ constexpr int kWave = 64;  // CDNA wavefront
 
 // Test / tuning switches ("Environment switches").  The environment is read ONCE, when the library is loaded; afterwards
 // a switch changes only through diffsal_set_tuning() -- no getenv on a launch path, and no way for an inherited variable to
-// reach a kernel argument.  tune(key) < 0 means "unset".
-enum TuneKey {
-  TUNE_NO_PERSIST = 0, TUNE_NO_XCD_ORDER, TUNE_NO_HALO, TUNE_FORCE_HALO, TUNE_IGEMM_CFG, TUNE_IGEMM16_CFG, TUNE_PLAN_DEBUG,
-  TUNE_WGRAD_CFG, TUNE_WGRAD_SPLITS, TUNE_WGRAD_VERBOSE, TUNE_NO_FUSED_BLOCK, TUNE_NO_WINOGRAD, TUNE_FORCE_WINOGRAD, TUNE_GN_CHUNKS,
-  TUNE_GN_APPLY_WGS, TUNE_GEMM_DMA, TUNE_CONV_DMA, TUNE_GROUP_GRID, TUNE_GEMM_DMA16, TUNE_WGRAD_DMA, TUNE_NO_GN_SLAB, TUNE_NO_WINOGRAD4, TUNE_BATCH_TILE, TUNE_BATCH_XCD, TUNE_NO_TAPSUM_ROWS, TUNE_TAPSUM_ROWS_FORM,
-  TUNE_NO_ATTN_BWD_DS, TUNE_NO_POOL_RUNS, TUNE_NO_ATTN_SLOTS, TUNE_NO_STREAM16, TUNE_CONV16_TILE, TUNE_BLOCK16_WAVES, TUNE_NO_ATTN16_MFMA, TUNE_CONV16_HALF, TUNE_FRONT_FOLD_WGS, TUNE_COUNT
-};
+// reach a kernel argument.  tune(key) < 0 means "unset".  The one list of switches: X(NAME) is the key TUNE_NAME here and the
+// variable / diffsal_set_tuning name "DIFFSAL_NAME" in misc.hip; append new ones at the end.
+#define DIFFSAL_TUNE_KEYS(X) \
+  X(NO_PERSIST) X(NO_XCD_ORDER) X(NO_HALO) X(FORCE_HALO) X(IGEMM_CFG) X(IGEMM16_CFG) X(PLAN_DEBUG) \
+  X(WGRAD_CFG) X(WGRAD_SPLITS) X(WGRAD_VERBOSE) X(NO_FUSED_BLOCK) X(NO_WINOGRAD) X(FORCE_WINOGRAD) X(GN_CHUNKS) \
+  X(GN_APPLY_WGS) X(GEMM_DMA) X(CONV_DMA) X(GROUP_GRID) X(GEMM_DMA16) X(WGRAD_DMA) X(NO_GN_SLAB) X(NO_WINOGRAD4) X(BATCH_TILE) \
+  X(BATCH_XCD) X(NO_TAPSUM_ROWS) X(TAPSUM_ROWS_FORM) X(NO_ATTN_BWD_DS) X(NO_POOL_RUNS) X(NO_ATTN_SLOTS) X(NO_STREAM16) \
+  X(CONV16_TILE) X(BLOCK16_WAVES) X(NO_ATTN16_MFMA) X(CONV16_HALF) X(FRONT_FOLD_WGS)
+#define DIFFSAL_TUNE_ENUM(name) TUNE_##name,
+enum TuneKey { DIFFSAL_TUNE_KEYS(DIFFSAL_TUNE_ENUM) TUNE_COUNT };
+#undef DIFFSAL_TUNE_ENUM
 int tune(int key);
 
 // Butterfly all-reduce over `width` (power of two <= 64) consecutive lanes, entirely on the VALU: quad permutes for the

@@ -23,12 +23,9 @@ void note_kernel(const char* fmt, ...) {
   va_end(ap);
 }
 
-static const char* const kTuneNames[TUNE_COUNT] = {
-    "DIFFSAL_NO_PERSIST", "DIFFSAL_NO_XCD_ORDER", "DIFFSAL_NO_HALO", "DIFFSAL_FORCE_HALO", "DIFFSAL_IGEMM_CFG",
-    "DIFFSAL_IGEMM16_CFG", "DIFFSAL_PLAN_DEBUG", "DIFFSAL_WGRAD_CFG", "DIFFSAL_WGRAD_SPLITS", "DIFFSAL_WGRAD_VERBOSE",
-    "DIFFSAL_NO_FUSED_BLOCK", "DIFFSAL_NO_WINOGRAD", "DIFFSAL_FORCE_WINOGRAD", "DIFFSAL_GN_CHUNKS", "DIFFSAL_GN_APPLY_WGS",
-    "DIFFSAL_GEMM_DMA", "DIFFSAL_CONV_DMA", "DIFFSAL_GROUP_GRID", "DIFFSAL_GEMM_DMA16", "DIFFSAL_WGRAD_DMA", "DIFFSAL_NO_GN_SLAB", "DIFFSAL_NO_WINOGRAD4", "DIFFSAL_BATCH_TILE", "DIFFSAL_BATCH_XCD", "DIFFSAL_NO_TAPSUM_ROWS", "DIFFSAL_TAPSUM_ROWS_FORM",
-    "DIFFSAL_NO_ATTN_BWD_DS", "DIFFSAL_NO_POOL_RUNS", "DIFFSAL_NO_ATTN_SLOTS", "DIFFSAL_NO_STREAM16", "DIFFSAL_CONV16_TILE", "DIFFSAL_BLOCK16_WAVES", "DIFFSAL_NO_ATTN16_MFMA", "DIFFSAL_CONV16_HALF", "DIFFSAL_FRONT_FOLD_WGS"};
+#define DIFFSAL_TUNE_NAME(name) "DIFFSAL_" #name,
+static const char* const kTuneNames[TUNE_COUNT] = {DIFFSAL_TUNE_KEYS(DIFFSAL_TUNE_NAME)};
+#undef DIFFSAL_TUNE_NAME
 static int g_tune[TUNE_COUNT];
 static const bool g_tune_init = [] {
   for (int k = 0; k < TUNE_COUNT; ++k) {
@@ -1230,7 +1227,7 @@ extern "C" size_t diffsal_workspace_bytes(int op, const diffsal_conv_desc* d, co
   }
 }
 
-extern "C" int diffsal_version(void) { return 51; }  // = _lib.ABI_VERSION
+extern "C" int diffsal_version(void) { return DIFFSAL_ABI_VERSION; }
 extern "C" const char* diffsal_last_error(void) { return g_err; }
 extern "C" const char* diffsal_last_gemm_kernel(void) { return g_kernel; }
 

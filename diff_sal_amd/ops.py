@@ -464,19 +464,15 @@ class _PackBatch:
         if not self.entries:
             return
         if self.dirty or self.table is None:
-            import numpy as np
-
-            dt = np.dtype([("src", "u8"), ("dst", "u8"), ("Cout", "i4"), ("Cin", "i4"), ("taps", "i4"), ("mode", "i4"),
-                           ("tile0", "i4"), ("reserved", "i4")])
-            jobs = np.zeros(len(self.entries), dtype=dt)
+            jobs = (_lib.PackJob * len(self.entries))()
             t0, mt, dev = 0, 1, None
             for i, (k, e) in enumerate(self.entries.items()):
                 _, out, co, ci, taps, mode = e
-                jobs[i] = (k[0], out.data_ptr(), co, ci, taps, mode, t0, 0)
+                jobs[i] = _lib.PackJob(k[0], out.data_ptr(), co, ci, taps, mode, t0, 0)
                 t0 += (ci // 32) * ((co + 31) // 32)
                 mt = max(mt, taps)
                 dev = out.device
-            self.table = torch.from_numpy(jobs.view(np.uint8).copy()).to(dev)
+            self.table = torch.frombuffer(jobs, dtype=torch.uint8).to(dev)
             self.tiles, self.max_taps, self.dirty = t0, mt, False
         with _prof("pack"):
             _lib.check(_lib.load().diffsal_pack_weight_many(self.table.data_ptr(), len(self.entries), self.tiles, self.max_taps,
@@ -1971,7 +1967,7 @@ def saliency_metrics(pred: Tensor, gt: Tensor, keep_ws: bool = False):
     return mean, per
 
 
-EVAL_JUDD, EVAL_BORJI, EVAL_SAUC, EVAL_CC, EVAL_NSS, EVAL_SIM, EVAL_JITTER = 1, 2, 4, 8, 16, 32, 64      # DIFFSAL_EVAL_*
+EVAL_JUDD, EVAL_BORJI, EVAL_SAUC, EVAL_CC, EVAL_NSS, EVAL_SIM, EVAL_JITTER = _lib.constants("EVAL_", "JUDD BORJI SAUC CC NSS SIM JITTER")
 EVAL_ROWS = ("auc_judd", "auc_borji", "auc_shuffled", "cc", "nss", "sim")      # rows of diffsal_eval_metrics' output
 
 
@@ -2136,8 +2132,8 @@ def audio_examples(lm: Tensor, exists: Optional[Tensor], n_examples: int, h: int
     return out
 
 
-FILTER_BILINEAR, FILTER_BICUBIC = 0, 1                      # DIFFSAL_FILTER_* of include/diffsal.h
-RESAMPLE_AUTO, RESAMPLE_FUSED, RESAMPLE_TWO_PASS = 0, 1, 2  # DIFFSAL_RESAMPLE_*
+FILTER_BILINEAR, FILTER_BICUBIC = _lib.constants("FILTER_", "BILINEAR BICUBIC")
+RESAMPLE_AUTO, RESAMPLE_FUSED, RESAMPLE_TWO_PASS = _lib.constants("RESAMPLE_", "AUTO FUSED TWO_PASS")
 
 
 def _u8_frames(t: Tensor, what: str) -> Tensor:

@@ -42,6 +42,10 @@ enum { DIFFSAL_ACT_NONE = 0, DIFFSAL_ACT_RELU = 1, DIFFSAL_ACT_GELU_ERF = 2, DIF
         * pre-activation of the erf-GELU in front of the layer whose data gradient this product is, and is NOT added */
        DIFFSAL_ACT_GELU_GRAD = 5 };
 
+/* Bumped whenever a signature or struct in this header changes.  diffsal_version() returns the value the binary was compiled
+ * with; a binding compares it with the header it reads, so a stale libdiffsal_hip.so is refused instead of being called with
+ * other argument lists. */
+#define DIFFSAL_ABI_VERSION 51
 int diffsal_version(void);
 const char* diffsal_last_error(void);
 /* Name and tile plan of the kernel the last diffsal_conv_igemm / diffsal_linear_pair / diffsal_conv_wino call of THIS thread
@@ -54,7 +58,7 @@ const char* diffsal_last_gemm_kernel(void);
  * summation order).  The DIFFSAL_* environment variables of the same names are read ONCE when the library is loaded; afterwards
  * only this call changes a switch (value < 0 = unset).  Names: DIFFSAL_NO_PERSIST, DIFFSAL_NO_XCD_ORDER, DIFFSAL_NO_HALO,
  * DIFFSAL_FORCE_HALO, DIFFSAL_IGEMM_CFG, DIFFSAL_IGEMM16_CFG, DIFFSAL_PLAN_DEBUG, DIFFSAL_WGRAD_CFG, DIFFSAL_WGRAD_SPLITS,
- * DIFFSAL_WGRAD_VERBOSE, DIFFSAL_NO_FUSED_BLOCK, ... (the full list: kTuneNames in csrc/misc.hip); round 6:
+ * DIFFSAL_WGRAD_VERBOSE, DIFFSAL_NO_FUSED_BLOCK, ... (the full list: DIFFSAL_TUNE_KEYS in csrc/common.h); round 6:
  * DIFFSAL_NO_STREAM16 = 1 routes 16-bit storage back to the 8-byte forms of the HBM-bound kernels and to the kernels the planner took before
  * conv16_dma / gemm16_dma2; DIFFSAL_FORCE_HALO = 2 and DIFFSAL_GEMM_DMA16 = 3 / 4 take those two (gemm16_dma2 with its 256 x 96 / 192 x 192
  * tile) on every shape they can run; DIFFSAL_CONV16_TILE = 0 / 1 keeps conv16_dma off / on its 8 x 24 x 192-channel tile, DIFFSAL_CONV16_HALF = 0 / 1 off / on its 128-pixel tiles; DIFFSAL_FRONT_FOLD_WGS = 1 runs diffsal_block_front_fold as one workgroup per CU with a next-tile look-ahead;
