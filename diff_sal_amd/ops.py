@@ -1506,6 +1506,8 @@ def attention_bwd(q: Tensor, k: Tensor, v: Tensor, dout: Tensor, heads: int, sca
     N, Lq, Cc = q.shape
     Lk = k.shape[1]
     d = Cc // heads
+    if Cc % 32:                                           # pass 2 is a matrix-core GEMM over C: refused before pass 1 is launched
+        raise RuntimeError(f"attention_bwd: C={Cc} must be a multiple of 32")
     ld = (heads * Lk + 3) // 4 * 4
     alloc = torch.empty if ld == heads * Lk else torch.zeros
     P = alloc((N * Lq, ld), device=q.device, dtype=torch.float32)
@@ -1513,8 +1515,6 @@ def attention_bwd(q: Tensor, k: Tensor, v: Tensor, dout: Tensor, heads: int, sca
     dq = torch.empty_like(q)
     _lib.check(lib.diffsal_attention_bwd(_p(q), _p(k), _p(v), _p(dout), _p(dq), _p(P), _p(dS), N, Lq, Lk, Cc, heads, ld,
                                          scale, _stream()), "attention_bwd")
-    if Cc % 32:
-        raise RuntimeError(f"attention_bwd: C={Cc} must be a multiple of 32")
     dk_full = wgrad_segmented(q.reshape(N * Lq, Cc), dS, N)       # [N, ld, C]: rows (head, t) x all channels
     dv_full = wgrad_segmented(dout.reshape(N * Lq, Cc), P, N)
     pick = lambda full: torch.cat([full[:, h * Lk:(h + 1) * Lk, h * d:(h + 1) * d] for h in range(heads)], dim=2)

@@ -545,7 +545,10 @@ int diffsal_block16(const void* o, const void* x, const void* wp, const float* b
 
 /* ---- K11: attention core ------------------------------------------------------------------
  * o[n,l,:] = concat_h softmax_t( q[n,l,h,:] . k[n,t,h,:] * scale ) v[n,t,h,:],  Lk <= 32.
- * R/.../attention.py:97-108 (scale = C^-0.5, quirk Q6). */
+ * R/.../attention.py:97-108 (scale = C^-0.5, quirk Q6).
+ * Accepted: any heads >= 1 with N * heads < 65536, head dim d = C / heads a multiple of 4, and K | V of one head in LDS as fp32 on
+ * every storage type: 2 * Lk * d * 4 <= 160 KiB (anything else is DIFFSAL_E_SHAPE before a launch).  Tiles above 64 KiB run with the
+ * kernel's dynamic LDS limit raised; the 160 KiB tile itself (Lk = 32, d = 640) launches on gfx950 (tests/test_gpu_instantiations.py). */
 int diffsal_attention(const void* q, const void* k, const void* v, void* o, int N, int Lq, int Lk,
                       int C, int heads, float scale, int dtype, diffsal_stream_t stream);
 
