@@ -442,23 +442,17 @@ class SalUNet(nn.Module):
                 else:
                     bias2 = pk[f"res{i}.bias2"]
                 f, _, _ = ops.conv3x3_wino4_ex(h, w2.f4, bias=bias2, residual=sc, gn_ab=ab2)
-                if taps is not None:
-                    taps[f"res{i}"] = f
-                hh, ww = f.shape[1:3]
-                f = ops.conv_igemm(f, pk[f"res{i}.down.w"], kh=3, kw=3, stride=(2, 2),
-                                   out_hw=((hh - 2) // 2 + 1, (ww - 2) // 2 + 1), bias=dn.conv.bias, tag="K5")
-                outs.append(f)
-                continue
-            h = ops.groupnorm_swish(f, rb.norm1.weight, rb.norm1.bias, 32, rb.norm1.eps)
-            h = ops.conv_igemm(h, pk[f"res{i}.conv1.w"], kh=3, kw=3, pad=(1, 1), bias=rb.conv1.bias,
-                               rowvec=tproj[:, off:off + co], tag="K4", wino=pk[f"res{i}.conv1.wino"])
-            off += co
-            h = ops.groupnorm_swish(h, rb.norm2.weight, rb.norm2.bias, 32, rb.norm2.eps)
-            sc = f
-            if hasattr(rb, "nin_shortcut"):
-                sc = ops.conv_igemm(f, pk[f"res{i}.nin.w"], bias=rb.nin_shortcut.bias, tag="K4")
-            f = ops.conv_igemm(h, pk[f"res{i}.conv2.w"], kh=3, kw=3, pad=(1, 1), bias=rb.conv2.bias, residual=sc, tag="K4",
-                               wino=pk[f"res{i}.conv2.wino"])
+            else:
+                h = ops.groupnorm_swish(f, rb.norm1.weight, rb.norm1.bias, 32, rb.norm1.eps)
+                h = ops.conv_igemm(h, pk[f"res{i}.conv1.w"], kh=3, kw=3, pad=(1, 1), bias=rb.conv1.bias,
+                                   rowvec=tproj[:, off:off + co], tag="K4", wino=w1)
+                off += co
+                h = ops.groupnorm_swish(h, rb.norm2.weight, rb.norm2.bias, 32, rb.norm2.eps)
+                sc = f
+                if hasattr(rb, "nin_shortcut"):
+                    sc = ops.conv_igemm(f, pk[f"res{i}.nin.w"], bias=rb.nin_shortcut.bias, tag="K4")
+                f = ops.conv_igemm(h, pk[f"res{i}.conv2.w"], kh=3, kw=3, pad=(1, 1), bias=rb.conv2.bias, residual=sc, tag="K4",
+                                   wino=w2)
             if taps is not None:
                 taps[f"res{i}"] = f
             hh, ww = f.shape[1:3]
@@ -473,7 +467,6 @@ class SalUNet(nn.Module):
         B, T, H, W, C = x.shape
         blk = self.invpt_decoder.mid_stages[i].blocks[0]
         a = blk.attn
-        n9 = B * T
         k_src = None                       # None: the key branch reads the same normalised frames as q and v
         if audio_tok is not None:
             if isinstance(audio_tok, tuple):     # (all stages' align products side by side, channel offsets): this stage's slice
@@ -482,123 +475,99 @@ class SalUNet(nn.Module):
             else:
                 a_small = ops.linear(audio_tok, pk[f"s{i}.align.w"], blk.align_conv.bias, tag="K7-align")  # [B*T, ha*wa, C]
             k_src = ops.audio_fuse(a_small, x, audio_hw[0], audio_hw[1])  # [B,C,T,H,W], read back as tokens (Q5)
-        xt = x.view(n9, H * W, C)
-        gh, gw = (H - self.kernel_kv[i]) // self.kernel_kv[i] + 1, (W - self.kernel_kv[i]) // self.kernel_kv[i] + 1
-        if (self.fused_front and ops.block_front_supported(C, self.heads[i], gh * gw, x.dtype)
-                and (x.dtype != torch.float32 or self._precision() == "fp32")
-                and not getattr(pk[f"s{i}.k.w"], "_diffsal_split", False)):
-            # [pooled k / v with the folded first LayerNorm] [their projections, one paired launch] [LayerNorm -> depthwise q -> LayerNorm -> proj_q ->
-            # attention (-> proj + residual on fp32)]: x_n, q_in, q and (fp32) o never reach HBM.  C = 96 continues with the
-            # fused second half (mlp_block / block16: 4 launches for the whole block, 3 with fold_kv_proj), C = 192 with the per-operator launches
-            xv_ = x.view(n9, H, W, C)
-            xk_ = xv_ if k_src is None else k_src.view(n9, H, W, C)
-            kvn = (a.conv_proj_k.bn.weight, a.conv_proj_k.bn.bias, a.conv_proj_v.bn.weight, a.conv_proj_v.bn.bias)
-            pre = (blk.norm.weight, blk.norm.bias, blk.norm.eps, k_src is None)
+        xt = x.view(B * T, H * W, C)
+        o, x1 = self._block_front(i, x, xt, k_src, pk)
+        # ---- the block's second half: proj + residual (where the front left them) -> norm2 -> MLP + residual
+        proj = (pk[f"s{i}.proj.w"], a.proj.bias)
+        norm2 = (blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
+        fc1, fc2 = (pk[f"s{i}.fc1.w"], blk.mlp.fc1.bias), (pk[f"s{i}.fc2.w"], blk.mlp.fc2.bias)
+        nz = None if norm_z is None else (norm_z.weight, norm_z.bias, norm_z.eps)
+        fused_c = C == 96 and blk.mlp.fc1.out_features == 192      # the finest stage's shape: both MLP weights live in LDS
+        z = None
+        if x1 is None and fused_c and x.dtype != torch.float32:
+            # 16-bit storage: proj + residual + norm2 + MLP + residual + norm_mts in ONE launch
+            x2, z = ops.block16(o, xt, proj, norm2, fc1, fc2, nz, (H * W, T, self.temporal_list[i]))
+        else:
+            if x1 is None:
+                x1 = ops.linear(o, *proj, residual=xt)
+            if fused_c and x1.dtype == torch.float32 and self._precision() == "fp32":
+                # norm2 -> fc1 -> GELU -> fc2 -> +x1 -> norm_mts in ONE launch
+                x2, z = ops.mlp_block(x1, norm2, fc1, fc2, nz, (H * W, T, self.temporal_list[i]))
+            else:
+                y = ops.layernorm(x1, *norm2)
+                y = ops.linear(y, *fc1, act=ACT_GELU)
+                x2 = ops.linear(y, *fc2, residual=x1)
+        return x2.view(B, T, H, W, C), (None if z is None else z.view(B, T, H, W, C))
+
+    def _block_front(self, i: int, x: Tensor, xt: Tensor, k_src: Optional[Tensor], pk):
+        """The first half of a TransformerBlock -> (o, None), the attention output [B*T, H*W, C] with proj + residual still to
+        apply, or (None, x1) where the launch that ran the attention applied them.  xt: x as tokens (the residual); k_src: what
+        the key branch reads (None: the same normalised frames as q and v)."""
+        B, T, H, W, C = x.shape
+        blk = self.invpt_decoder.mid_stages[i].blocks[0]
+        a = blk.attn
+        n9, kkv, heads, scale = B * T, self.kernel_kv[i], self.heads[i], float(C) ** -0.5  # scale uses full C (Q6)
+        norm1 = (blk.norm.weight, blk.norm.bias, blk.norm.eps)
+        normq = (a.conv_proj_q.bn.weight, a.conv_proj_q.bn.bias, a.conv_proj_q.bn.eps)
+        kvn = (a.conv_proj_k.bn.weight, a.conv_proj_k.bn.bias, a.conv_proj_v.bn.weight, a.conv_proj_v.bn.bias)
+        keps = a.conv_proj_k.bn.eps
+        wq9, wk, wv = pk[f"s{i}.wq9"], pk[f"s{i}.wk"], pk[f"s{i}.wv"]
+        split_w = getattr(pk[f"s{i}.k.w"], "_diffsal_split", False)
+        xv_ = x.view(n9, H, W, C)
+        gh, gw = (H - kkv) // kkv + 1, (W - kkv) // kkv + 1
+        if (self.fused_front and ops.block_front_supported(C, heads, gh * gw, x.dtype)
+                and (x.dtype != torch.float32 or self._precision() == "fp32") and not split_w):
+            # [pooled k / v with the folded first LayerNorm] [their projections, one paired launch] [LayerNorm -> depthwise q ->
+            # LayerNorm -> proj_q -> attention (-> proj + residual on fp32)]: x_n, q_in, q and (fp32) o never reach HBM
             f32 = x.dtype == torch.float32
-            fold = f32 and self._fold_front(i, gh * gw)
-            if fold:
+            kk, vv = ops.kv_prep(k_src.view(n9, H, W, C) if k_src is not None else xv_, xv_, wk, wv, *kvn, kkv, keps,
+                                 pre_ln=norm1 + (k_src is None,))
+            if f32 and self._fold_front(i, gh * gw):
                 # proj_q and proj on the key side: [pooled rows] [G | U = the pooled rows times the folded weights, one paired launch
                 # with N = 2 C] [block_front_fold]: the same three launches, q, k, v and o are never formed
-                kk, vv = ops.kv_prep(xk_, xv_, pk[f"s{i}.wk"], pk[f"s{i}.wv"], *kvn, self.kernel_kv[i], a.conv_proj_k.bn.eps, pre_ln=pre)
                 Gk, Uv = ops.linear_pair(kk, vv, pk[f"s{i}.kq.w"], pk[f"s{i}.vp.w"], None, None)
-                y = ops.block_front_fold(xv_, Gk, Uv, kk, pk[f"s{i}.ukq"], (blk.norm.weight, blk.norm.bias, blk.norm.eps),
-                                         pk[f"s{i}.wq9"], (a.conv_proj_q.bn.weight, a.conv_proj_q.bn.bias, a.conv_proj_q.bn.eps),
-                                         pk[f"s{i}.proj.bf"], self.heads[i], float(C) ** -0.5).view(n9, H * W, C)
-            elif self.fold_kv_proj and C == 96:
-                kk, vv = ops.kv_prep_proj(xk_, xv_, pk[f"s{i}.wk"], pk[f"s{i}.wv"], *kvn, self.kernel_kv[i], a.conv_proj_k.bn.eps, pre,
-                                          (pk[f"s{i}.k.w"], a.proj_k.bias), (pk[f"s{i}.v.w"], a.proj_v.bias))
+                y = ops.block_front_fold(xv_, Gk, Uv, kk, pk[f"s{i}.ukq"], norm1, wq9, normq, pk[f"s{i}.proj.bf"], heads, scale)
             else:
-                kk, vv = ops.kv_prep(xk_, xv_, pk[f"s{i}.wk"], pk[f"s{i}.wv"], *kvn, self.kernel_kv[i], a.conv_proj_k.bn.eps, pre_ln=pre)
                 kk, vv = ops.linear_pair(kk, vv, pk[f"s{i}.k.w"], pk[f"s{i}.v.w"], a.proj_k.bias, a.proj_v.bias)
-            if not fold:
-                y = ops.block_front(xv_, kk, vv, (blk.norm.weight, blk.norm.bias, blk.norm.eps), pk[f"s{i}.wq9"],
-                                    (a.conv_proj_q.bn.weight, a.conv_proj_q.bn.bias, a.conv_proj_q.bn.eps),
-                                    (pk[f"s{i}.q.w"], a.proj_q.bias), (pk[f"s{i}.proj.w"], a.proj.bias) if f32 else None,
-                                    self.heads[i], float(C) ** -0.5).view(n9, H * W, C)
-            nz = None if norm_z is None else (norm_z.weight, norm_z.bias, norm_z.eps)
-            if C == 96 and blk.mlp.fc1.out_features == 192:
-                if f32:
-                    x2, z = ops.mlp_block(y, (blk.norm2.weight, blk.norm2.bias, blk.norm2.eps), (pk[f"s{i}.fc1.w"], blk.mlp.fc1.bias),
-                                          (pk[f"s{i}.fc2.w"], blk.mlp.fc2.bias), nz, (H * W, T, self.temporal_list[i]))
-                else:
-                    x2, z = ops.block16(y, xt, (pk[f"s{i}.proj.w"], a.proj.bias), (blk.norm2.weight, blk.norm2.bias, blk.norm2.eps),
-                                        (pk[f"s{i}.fc1.w"], blk.mlp.fc1.bias), (pk[f"s{i}.fc2.w"], blk.mlp.fc2.bias), nz,
-                                        (H * W, T, self.temporal_list[i]))
-                return x2.view(B, T, H, W, C), (None if z is None else z.view(B, T, H, W, C))
-            x1 = y if f32 else ops.linear(y, pk[f"s{i}.proj.w"], a.proj.bias, residual=xt)
-            y2 = ops.layernorm(x1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
-            y2 = ops.linear(y2, pk[f"s{i}.fc1.w"], blk.mlp.fc1.bias, act=ACT_GELU)
-            x2 = ops.linear(y2, pk[f"s{i}.fc2.w"], blk.mlp.fc2.bias, residual=x1)
-            return x2.view(B, T, H, W, C), None
-        if self.merge_qkv_prep and self.fold_norm1 and a.conv_proj_q.bn.eps == a.conv_proj_k.bn.eps:
+                y = ops.block_front(xv_, kk, vv, norm1, wq9, normq, (pk[f"s{i}.q.w"], a.proj_q.bias),
+                                    (pk[f"s{i}.proj.w"], a.proj.bias) if f32 else None, heads, scale)
+            y = y.view(n9, H * W, C)
+            return (None, y) if f32 else (y, None)
+        if self.merge_qkv_prep and self.fold_norm1 and normq[2] == keps:
             # the block's `norm` is applied to the tokens as qkv_prep loads them: x_n = norm(x) is never written
-            xv_ = x.view(n9, H, W, C)
-            q, kk, vv = ops.qkv_prep(xv_, pk[f"s{i}.wq9"], a.conv_proj_q.bn.weight, a.conv_proj_q.bn.bias,
-                                     xv_ if k_src is None else k_src.view(n9, H, W, C), xv_, pk[f"s{i}.wk"], pk[f"s{i}.wv"],
-                                     a.conv_proj_k.bn.weight, a.conv_proj_k.bn.bias, a.conv_proj_v.bn.weight,
-                                     a.conv_proj_v.bn.bias, self.kernel_kv[i], a.conv_proj_k.bn.eps,
-                                     pre_ln=(blk.norm.weight, blk.norm.bias, blk.norm.eps, k_src is None))
+            q, kk, vv = ops.qkv_prep(xv_, wq9, *normq[:2], xv_ if k_src is None else k_src.view(n9, H, W, C), xv_, wk, wv, *kvn,
+                                     kkv, keps, pre_ln=norm1 + (k_src is None,))
         else:
-            xn = ops.layernorm(x, blk.norm.weight, blk.norm.bias, blk.norm.eps)
+            xn = ops.layernorm(x, *norm1)
             if k_src is None:
                 k_src = xn
-            if self.merge_qkv_prep and a.conv_proj_q.bn.eps == a.conv_proj_k.bn.eps and k_src.dtype == xn.dtype:
-                q, kk, vv = ops.qkv_prep(xn.view(n9, H, W, C), pk[f"s{i}.wq9"], a.conv_proj_q.bn.weight, a.conv_proj_q.bn.bias,
-                                         k_src.view(n9, H, W, C), xn.view(n9, H, W, C), pk[f"s{i}.wk"], pk[f"s{i}.wv"],
-                                         a.conv_proj_k.bn.weight, a.conv_proj_k.bn.bias, a.conv_proj_v.bn.weight,
-                                         a.conv_proj_v.bn.bias, self.kernel_kv[i], a.conv_proj_k.bn.eps)
+            xn_ = xn.view(n9, H, W, C)
+            if self.merge_qkv_prep and normq[2] == keps and k_src.dtype == xn.dtype:
+                q, kk, vv = ops.qkv_prep(xn_, wq9, *normq[:2], k_src.view(n9, H, W, C), xn_, wk, wv, *kvn, kkv, keps)
             else:
-                q = ops.dwconv3_ln(xn.view(n9, H, W, C), pk[f"s{i}.wq9"], a.conv_proj_q.bn.weight, a.conv_proj_q.bn.bias,
-                                   a.conv_proj_q.bn.eps)
-                kk, vv = ops.dwpool_ln_kv(k_src.view(n9, H, W, C), xn.view(n9, H, W, C), pk[f"s{i}.wk"], pk[f"s{i}.wv"],
-                                          a.conv_proj_k.bn.weight, a.conv_proj_k.bn.bias, a.conv_proj_v.bn.weight,
-                                          a.conv_proj_v.bn.bias, self.kernel_kv[i], a.conv_proj_k.bn.eps)
+                q = ops.dwconv3_ln(xn_, wq9, *normq)
+                kk, vv = ops.dwpool_ln_kv(k_src.view(n9, H, W, C), xn_, wk, wv, *kvn, kkv, keps)
         if self._fold_attn(i, kk.shape[1]):
             # proj_q and proj on the key side: q, k, v and o are never formed.  [G | U = the pooled rows times the folded weights, one
             # paired launch with N = 2 C] [scores, softmax, P U + bias + residual on the matrix cores, one launch]
             Gk, Uv = ops.linear_pair(kk, vv, pk[f"s{i}.kq.w"], pk[f"s{i}.vp.w"], None, None)
-            x1 = ops.attn_fold(q, Gk, Uv, kk, pk[f"s{i}.ukq"], xt, pk[f"s{i}.proj.bf"], self.heads[i], float(C) ** -0.5)
-            y = ops.layernorm(x1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
-            y = ops.linear(y, pk[f"s{i}.fc1.w"], blk.mlp.fc1.bias, act=ACT_GELU)
-            x2 = ops.linear(y, pk[f"s{i}.fc2.w"], blk.mlp.fc2.bias, residual=x1)
-            return x2.view(B, T, H, W, C), None
+            return None, ops.attn_fold(q, Gk, Uv, kk, pk[f"s{i}.ukq"], xt, pk[f"s{i}.proj.bf"], heads, scale)
         if (self.group_qkv and self.compute_dtype == torch.float32 and ops.get_gemm_precision() == "fp32"
-                and not getattr(pk[f"s{i}.k.w"], "_diffsal_split", False) and C % 96 == 0
-                and (self.group_qkv_all or -(-(q.numel() // C) // 96) * (C // 96) <= 256)):
+                and not split_w and C % 96 == 0 and -(-(q.numel() // C) // 96) * (C // 96) <= 256):
             # the three projections of the block in ONE launch when the query product alone leaves workgroup slots free (<= 256
             # tiles of 96 x 96: stage 0 at B = 4; the key / value products have 648 rows and would fill a quarter of the chip
             # for the length of a whole K walk).  Measured at B = 4: stage 0 64 us against 40 + 36; stages 1 / 2, whose query
             # products fill the chip, 60 / 65 us against 38 + 19 / 41 + 15 -- not grouped.
             q, kk, vv = ops.linear_group((q, kk, vv), (pk[f"s{i}.q.w"], pk[f"s{i}.k.w"], pk[f"s{i}.v.w"]),
                                          (a.proj_q.bias, a.proj_k.bias, a.proj_v.bias))
-        elif self.pair_kv and not getattr(pk[f"s{i}.k.w"], "_diffsal_split", False) and (
-                self.compute_dtype != torch.float32 or ops.get_gemm_precision() == "fp32"):
-            q = ops.linear(q, pk[f"s{i}.q.w"], a.proj_q.bias)
-            kk, vv = ops.linear_pair(kk, vv, pk[f"s{i}.k.w"], pk[f"s{i}.v.w"], a.proj_k.bias, a.proj_v.bias)   # one launch
         else:
             q = ops.linear(q, pk[f"s{i}.q.w"], a.proj_q.bias)
-            kk = ops.linear(kk, pk[f"s{i}.k.w"], a.proj_k.bias)
-            vv = ops.linear(vv, pk[f"s{i}.v.w"], a.proj_v.bias)
-        o = ops.attention(q, kk, vv, self.heads[i], float(C) ** -0.5)  # scale uses full C (Q6)
-        if C == 96 and blk.mlp.fc1.out_features == 192 and x.dtype != torch.float32:
-            # finest stage on 16-bit storage: proj + residual + norm2 + MLP + residual + norm_mts in ONE launch
-            x2, z = ops.block16(o, xt, (pk[f"s{i}.proj.w"], a.proj.bias), (blk.norm2.weight, blk.norm2.bias, blk.norm2.eps),
-                                (pk[f"s{i}.fc1.w"], blk.mlp.fc1.bias), (pk[f"s{i}.fc2.w"], blk.mlp.fc2.bias),
-                                None if norm_z is None else (norm_z.weight, norm_z.bias, norm_z.eps),
-                                (H * W, T, self.temporal_list[i]))
-            return x2.view(B, T, H, W, C), (None if z is None else z.view(B, T, H, W, C))
-        x1 = ops.linear(o, pk[f"s{i}.proj.w"], a.proj.bias, residual=xt)
-        if C == 96 and blk.mlp.fc1.out_features == 192 and x1.dtype == torch.float32 and self._precision() == "fp32":
-            # finest stage: norm2 -> fc1 -> GELU -> fc2 -> +x1 -> norm_mts in ONE launch (both MLP weights live in LDS)
-            x2, z = ops.mlp_block(x1, (blk.norm2.weight, blk.norm2.bias, blk.norm2.eps), (pk[f"s{i}.fc1.w"], blk.mlp.fc1.bias),
-                                  (pk[f"s{i}.fc2.w"], blk.mlp.fc2.bias),
-                                  None if norm_z is None else (norm_z.weight, norm_z.bias, norm_z.eps),
-                                  (H * W, T, self.temporal_list[i]))
-            return x2.view(B, T, H, W, C), (None if z is None else z.view(B, T, H, W, C))
-        y = ops.layernorm(x1, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps)
-        y = ops.linear(y, pk[f"s{i}.fc1.w"], blk.mlp.fc1.bias, act=ACT_GELU)
-        x2 = ops.linear(y, pk[f"s{i}.fc2.w"], blk.mlp.fc2.bias, residual=x1)
-        return x2.view(B, T, H, W, C), None
+            if self.pair_kv and not split_w and (self.compute_dtype != torch.float32 or ops.get_gemm_precision() == "fp32"):
+                kk, vv = ops.linear_pair(kk, vv, pk[f"s{i}.k.w"], pk[f"s{i}.v.w"], a.proj_k.bias, a.proj_v.bias)   # one launch
+            else:
+                kk = ops.linear(kk, pk[f"s{i}.k.w"], a.proj_k.bias)
+                vv = ops.linear(vv, pk[f"s{i}.v.w"], a.proj_v.bias)
+        return ops.attention(q, kk, vv, heads, scale), None
 
     # Largest batch evaluated in one pass.  The implicit-GEMM loader addresses each operand with 32-bit BYTE offsets (< 4 GiB) and
     # the row kernels count elements in 32-bit ints, so a pass is sized such that the largest tensor it touches stays inside
@@ -637,10 +606,6 @@ class SalUNet(nn.Module):
     fold_norm1 = False
     # finest stage (C = 96): the block's first half is ONE launch (csrc/tblock.hip).  Off: the per-operator launches below
     fused_front = True
-    # proj_k / proj_v inside the pooled launch (the whole C = 96 block is then 3 launches).  Measured: 45 us against 31 + 10 us for
-    # the pooled launch + the paired projection GEMM at stage 3 (every one of the 648 workgroups re-reads both weight matrices
-    # from L2), 43 against 30 us at C = 192: off.
-    fold_kv_proj = False
     # fp32 stages with C = 192 / 384 / 768 (stages 0-2): proj_q and proj re-associated onto the 2 x Lk pooled keys of a frame
     # (ops.attn_fold, csrc/attn_fold.hip): per token two [. x 2 Lk] contractions instead of two dense C x C products; exact algebra,
     # another summation order.  Off: the grouped / paired projections, ops.attention and the proj GEMM
@@ -670,7 +635,6 @@ class SalUNet(nn.Module):
     # source-resolution result itself (ops.conv3x3_wino4_ex(up2=...)); the first one's output exists only on its 3-pixel border ring
     fuse_up_pe2 = True
     group_qkv = True  # fp32: query, key and value projections of a block in one grouped launch (ops.linear_group)
-    group_qkv_all = False  # ... at every stage, not only where the query product alone leaves workgroup slots free (A/B aid)
     merge_align = True   # the stages' audio align convolutions as one product (eval)
     group_reduce_temp = True   # fp32 tap path: the stages' ReduceTemp products in one grouped launch after the last stage
     # uses of the tap form on 16-bit storage, from {"s1", "s2", "s3", "mt"}.  Off by default: ("s1", "s2") is +3.4 % on the bf16
@@ -741,6 +705,46 @@ class SalUNet(nn.Module):
                 xs.append(xn)
         return (ms[0], xs[0]) if len(ms) == 1 else (torch.cat(ms), torch.cat(xs))
 
+    def _up_embed(self, i: int, xcur: Tensor, skip: Optional[Tensor], pk, taps: Optional[dict]) -> Tensor:
+        """UpEmbed of stage i (common_block.py:196-216) on frames [B,T,h,w,Cp] -> [B,T,2h,2w,C]: bilinear x2, two dilated 3x3
+        convolutions + BN + ReLU, and the stage's encoder frames ``skip`` added by the second one's epilogue."""
+        Bn, T, h, w, Cp = xcur.shape
+        C, d = self.up_channels[i], self.dilation[i]
+        xs = xcur.view(Bn * T, h, w, Cp)
+        w1, wino1, tapw = pk[f"s{i}.pe1.w"], pk[f"s{i}.pe1.wino"], pk[f"s{i}.pe1.tapw"]
+        s1, b1, s2, b2 = pk[f"s{i}.pe1.scale"], pk[f"s{i}.pe1.shift"], pk[f"s{i}.pe2.scale"], pk[f"s{i}.pe2.shift"]
+        wino2 = pk[f"s{i}.pe2.wino"]
+        f32c = (self._use_tap_conv(taps, f"s{i}") and self.compute_dtype == torch.float32 and wino1 is not None
+                and h >= 12 and w >= 12)
+        lowc = (self.compute_dtype != torch.float32 and self.up_commute16 and not (taps is not None and self.taps_reference_forms)
+                and h >= 2 and w >= 2)
+        fuse_up = None
+        if self.up_commute and d == 2 and (f32c or lowc):
+            # the convolution at the source resolution + interpolation + border-ring corrections.  fp32: F(4x4) there, and only
+            # where the interior is most of the map (stages 2 and 3 at 224 x 384; the alternative is the tap path).  16-bit
+            # storage: every stage (the alternative is the convolution on the up-sampled map: 4x the products)
+            if (f32c and self.fuse_up_pe2 and wino2 is not None and wino2.f4 is not None
+                    and ops.wino4_supported(_ShapeOnly((Bn * T, 2 * h, 2 * w, C)), C, 2)):
+                # ... and UpEmbed's second convolution forms the interpolated interior itself as its input transform gathers
+                # it: only the border ring of the first convolution's output is ever written
+                u, c_ext = ops.up2_conv3x3_d2(xs, w1, wino1, tapw, scale=s1, shift=b1, act=ACT_RELU, tag="K12", ring_only=True)
+                fuse_up = (c_ext, s1, b1, ACT_RELU)
+            else:
+                u = ops.up2_conv3x3_d2(xs, w1, wino1, tapw, scale=s1, shift=b1, act=ACT_RELU, tag="K12")
+        elif self._use_tap_conv(taps, f"s{i}") and d in (1, 2) and h >= 2 and w >= 2:
+            y9 = ops.linear(xs, tapw, None, tag="K12")
+            u = ops.tapsum([y9], 2 * h, 2 * w, C, dil=d, scale=s1, shift=b1, act=ACT_RELU, tag="K12-tap")
+        else:
+            u = ops.resize_bilinear(xs, 2 * h, 2 * w)
+            u = ops.conv_igemm(u, w1, kh=3, kw=3, pad=(d, d), dil=(d, d), scale=s1, shift=b1, act=ACT_RELU, tag="K12")
+        res = None if skip is None else skip.view(Bn * T, 2 * h, 2 * w, C)
+        if fuse_up is not None:
+            u, _, _ = ops.conv3x3_wino4_ex(u, wino2.f4, scale=s2, shift=b2, act=ACT_RELU, residual=res, dil=2, up2=fuse_up, tag="K12")
+        else:
+            u = ops.conv_igemm(u, pk[f"s{i}.pe2.w"], kh=3, kw=3, pad=(d, d), dil=(d, d), scale=s2, shift=b2, act=ACT_RELU, tag="K12",
+                               residual=res, wino=wino2)
+        return u.view(Bn, T, 2 * h, 2 * w, C)
+
     def _forward_eval(self, x: Tensor, t: Tensor, feat_list: Sequence[Tensor], audio_feat_list: Optional[Tensor],
                       taps: Optional[dict], lowres: bool = False) -> Tensor:
         pk = self.packed()
@@ -806,48 +810,7 @@ class SalUNet(nn.Module):
         for i in range(ns):
             C = self.up_channels[i]
             if self.dilation[i] != 0:
-                Bn, T, h, w, Cp = xcur.shape
-                d = self.dilation[i]
-                f32c = (self._use_tap_conv(taps, f"s{i}") and self.compute_dtype == torch.float32 and pk[f"s{i}.pe1.wino"] is not None
-                        and h >= 12 and w >= 12)
-                lowc = (self.compute_dtype != torch.float32 and self.up_commute16 and not (taps is not None and self.taps_reference_forms)
-                        and h >= 2 and w >= 2)
-                fuse_up = None
-                if self.up_commute and d == 2 and (f32c or lowc):
-                    # the convolution at the source resolution + interpolation + border-ring corrections.  fp32: F(4x4) there, and only
-                    # where the interior is most of the map (stages 2 and 3 at 224 x 384; the alternative is the tap path).  16-bit
-                    # storage: every stage (the alternative is the convolution on the up-sampled map: 4x the products)
-                    w2 = pk[f"s{i}.pe2.wino"]
-                    if (f32c and self.fuse_up_pe2 and w2 is not None and w2.f4 is not None
-                            and ops.wino4_supported(_ShapeOnly((Bn * T, 2 * h, 2 * w, C)), C, 2)):
-                        # ... and UpEmbed's second convolution forms the interpolated interior itself as its input transform gathers
-                        # it: only the border ring of the first convolution's output is ever written
-                        u, c_ext = ops.up2_conv3x3_d2(xcur.view(Bn * T, h, w, Cp), pk[f"s{i}.pe1.w"], pk[f"s{i}.pe1.wino"], pk[f"s{i}.pe1.tapw"],
-                                                      scale=pk[f"s{i}.pe1.scale"], shift=pk[f"s{i}.pe1.shift"], act=ACT_RELU, tag="K12",
-                                                      ring_only=True)
-                        fuse_up = (c_ext, pk[f"s{i}.pe1.scale"], pk[f"s{i}.pe1.shift"], ACT_RELU)
-                    else:
-                        u = ops.up2_conv3x3_d2(xcur.view(Bn * T, h, w, Cp), pk[f"s{i}.pe1.w"], pk[f"s{i}.pe1.wino"], pk[f"s{i}.pe1.tapw"],
-                                               scale=pk[f"s{i}.pe1.scale"], shift=pk[f"s{i}.pe1.shift"], act=ACT_RELU, tag="K12")
-                elif self._use_tap_conv(taps, f"s{i}") and d in (1, 2) and h >= 2 and w >= 2:
-                    y9 = ops.linear(xcur.view(Bn * T, h, w, Cp), pk[f"s{i}.pe1.tapw"], None, tag="K12")
-                    u = ops.tapsum([y9], 2 * h, 2 * w, C, dil=d, scale=pk[f"s{i}.pe1.scale"], shift=pk[f"s{i}.pe1.shift"],
-                                   act=ACT_RELU, tag="K12-tap")
-                else:
-                    u = ops.resize_bilinear(xcur.view(Bn * T, h, w, Cp), 2 * h, 2 * w)
-                    u = ops.conv_igemm(u, pk[f"s{i}.pe1.w"], kh=3, kw=3, pad=(d, d), dil=(d, d),
-                                       scale=pk[f"s{i}.pe1.scale"], shift=pk[f"s{i}.pe1.shift"], act=ACT_RELU, tag="K12")
-                skip = frames[i] if i in (1, 2) else None  # transformer.py:265-270
-                if fuse_up is not None:
-                    u, _, _ = ops.conv3x3_wino4_ex(u, pk[f"s{i}.pe2.wino"].f4, scale=pk[f"s{i}.pe2.scale"], shift=pk[f"s{i}.pe2.shift"],
-                                                   act=ACT_RELU, residual=None if skip is None else skip.view(Bn * T, 2 * h, 2 * w, C),
-                                                   dil=2, up2=fuse_up, tag="K12")
-                else:
-                    u = ops.conv_igemm(u, pk[f"s{i}.pe2.w"], kh=3, kw=3, pad=(d, d), dil=(d, d),
-                                       scale=pk[f"s{i}.pe2.scale"], shift=pk[f"s{i}.pe2.shift"], act=ACT_RELU, tag="K12",
-                                       residual=None if skip is None else skip.view(Bn * T, 2 * h, 2 * w, C),
-                                       wino=pk[f"s{i}.pe2.wino"])
-                xcur = u.view(Bn, T, 2 * h, 2 * w, C)
+                xcur = self._up_embed(i, xcur, frames[i] if i in (1, 2) else None, pk, taps)  # skip: transformer.py:265-270
             kt = self.temporal_list[i]
             if (xcur.shape[1] - kt) // kt + 1 != 1:
                 raise RuntimeError(f"ReduceTemp: T={xcur.shape[1]}, kernel/stride {kt} must give exactly one frame")
@@ -888,6 +851,9 @@ class SalUNet(nn.Module):
                 ops.conv_igemm(pr["x"], pr["w"], kh=pr["kh"], kw=pr["kw"], stride=pr["stride"], act=pr["act"], out=pr["out"], tag="K13")
             ops.conv_igemm_group(redu, tag="K13")
         mt = dec.mt_proj
+        head = (pk["head.w"], self.logits.linear_pred.bias)
+        # MLPHead (1x1 to one channel + sigmoid) in the tap gather's epilogue: the [B,112,192,96] map never reaches HBM
+        in_gather = z_all is not None and self.fold_head and mt[0].out_channels <= 128 and mt[0].out_channels % 4 == 0
         if z_all is not None:
             # 16-bit storage: the tap products leave the matrix cores in fp32 and the gather adds them in fp32 (ops.linear(out_f32)):
             # nothing of mt_proj is rounded to 16 bits -- the 4-scale sum [B,112,192,768] (2.1 GB at 64 clips) does not exist either
@@ -898,23 +864,15 @@ class SalUNet(nn.Module):
                 m_ = z_.shape[0] * z_.shape[1] * z_.shape[2]
                 ys.append(y9[off:off + m_].view(z_.shape[0], z_.shape[1], z_.shape[2], y9.shape[-1]))
                 off += m_
-            if self.fold_head and mt[0].out_channels <= 128 and mt[0].out_channels % 4 == 0:
-                # MLPHead (1x1 to one channel + sigmoid) in the gather's epilogue: the [B,112,192,96] map never reaches HBM
-                s = ops.tapsum(ys, th, tw, mt[0].out_channels, dil=1, bias=mt[0].bias, scale=pk["mt.scale"], shift=pk["mt.shift"],
-                               act=ACT_RELU, tag="K14-tap", head=(pk["head.w"], self.logits.linear_pred.bias))
-                if lowres:
-                    return s
-                out = ops.resize_bilinear(s, self.img_size[0], self.img_size[1], tag="K14-head")
-                return out.view(B, 1, self.img_size[0], self.img_size[1])
             y = ops.tapsum(ys, th, tw, mt[0].out_channels, dil=1, bias=mt[0].bias, scale=pk["mt.scale"], shift=pk["mt.shift"],
-                           act=ACT_RELU, tag="K14-tap")
+                           act=ACT_RELU, tag="K14-tap", head=head if in_gather else None)
         else:
             acc = ops.resize_sum(zs, th, tw)
             if taps is not None:
                 taps["multi_scale"] = acc
             y = ops.conv_igemm(acc, pk["mt.w"], kh=3, kw=3, pad=(1, 1), bias=mt[0].bias, scale=pk["mt.scale"],
                                shift=pk["mt.shift"], act=ACT_RELU, tag="K14")
-        s = ops.head_sigmoid(y, pk["head.w"], self.logits.linear_pred.bias)
+        s = y if in_gather else ops.head_sigmoid(y, *head)
         if lowres:                       # the caller fuses the final resize with the solver update
             return s
         out = ops.resize_bilinear(s, self.img_size[0], self.img_size[1], tag="K14-head")

@@ -45,7 +45,7 @@ enum { DIFFSAL_ACT_NONE = 0, DIFFSAL_ACT_RELU = 1, DIFFSAL_ACT_GELU_ERF = 2, DIF
 /* Bumped whenever a signature or struct in this header changes.  diffsal_version() returns the value the binary was compiled
  * with; a binding compares it with the header it reads, so a stale libdiffsal_hip.so is refused instead of being called with
  * other argument lists. */
-#define DIFFSAL_ABI_VERSION 51
+#define DIFFSAL_ABI_VERSION 52
 int diffsal_version(void);
 const char* diffsal_last_error(void);
 /* Name and tile plan of the kernel the last diffsal_conv_igemm / diffsal_linear_pair / diffsal_conv_wino call of THIS thread
@@ -568,16 +568,6 @@ int diffsal_attn_fold(const float* q_in, const float* G, const float* U, const f
  * R/.../common_block.py:111-122. */
 int diffsal_head_sigmoid(const void* x, const float* w /*[C]*/, const float* bias /*[1]*/, float* out /*fp32*/,
                          int NHW, int C, int dtype, diffsal_stream_t stream);
-
-/* The pooled key / value branch of a TransformerBlock in ONE launch, projections included (C = 96 / 192; attention.py:49-76,
- * 79-80, 88-99): per pooled token  k = Linear_k(LN_k(pool_k(LN_1?(xk)))),  v = Linear_v(LN_v(pool_v(LN_1(xv)))),  pool = depthwise
- * k x k stride-k convolution (weights wk / wv [k*k, C] fp32), LN_1 = the block's first LayerNorm applied as the tokens are loaded
- * (to xv always, to xk when pre_ln_k), proj_w* [C, C] in the storage type.  out_k, out_v [N, gh*gw, C]. */
-int diffsal_kv_prep_proj(const void* xk, const void* xv, const float* wk, const float* wv, const float* gk, const float* bk,
-                         const float* gv, const float* bv, const void* proj_wk, const float* proj_bk, const void* proj_wv,
-                         const float* proj_bv, void* out_k, void* out_v, int N, int H, int W, int C, int k, float eps,
-                         const float* pre_gamma, const float* pre_beta, float pre_eps, int pre_ln_k, int dtype,
-                         diffsal_stream_t stream);
 
 /* ---- fused first half of a TransformerBlock (C = 96, 2 heads; csrc/tblock.hip) --------------------------------------------
  * R/models/saliency_decoder/transformer.py:150-152, attention.py:36-47,87-110:

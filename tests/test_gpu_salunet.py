@@ -156,6 +156,64 @@ def test_image_based_false_uses_eight_frames():
     assert (out.cpu() - ref).abs().max().item() < RTOL * ref.abs().max().item()
 
 
+def _launch_trace(net, args):
+    """(class, note) of every launch of one forward (ops.PROFILE), and its output.  An untraced forward goes first, so that the
+    launches that pack the weights (once per setting of the switches in SalUNet._cache_key) are not part of the trace."""
+    from diff_sal_amd import ops
+
+    with torch.no_grad():
+        net(*args)
+    ops.PROFILE = []
+    try:
+        with torch.no_grad():
+            out = net(*args)
+        torch.cuda.synchronize()
+        return [(p[3], p[5]) for p in ops.PROFILE], out
+    finally:
+        ops.PROFILE = None
+
+
+# (storage, fixture, switch under test, its non-default value, the other overrides)
+SWITCH_CASES = [
+    ("fp32", "small_av", "fused_front", False, {}),
+    ("fp32", "small_av", "merge_qkv_prep", False, {}),
+    ("fp32", "small_av", "group_qkv", False, {"fold_attn_proj": False}),
+    ("fp32", "small_av", "pair_kv", False, {"fold_attn_proj": False, "group_qkv": False}),
+    ("fp32", "small_av", "merge_align", False, {}),
+    ("fp32", "small_av", "group_reduce_temp", False, {}),
+    ("fp32", "small_av", "fold_head", False, {}),
+    ("fp32", "small_av", "fold_norm1", True, {}),
+    ("fp32", "full_av_b1", "up_commute", False, {}),
+    ("fp32", "full_av_b1", "fuse_up_pe2", False, {}),
+    ("fp32", "full_av_b1", "fuse_resblock", False, {}),
+] + [(d, "small_av", s, False, {}) for s in ("fused_front", "pair_kv", "up_commute16", "mt_tap16_f32") for d in ("bf16", "fp16")]
+
+
+@pytest.mark.parametrize("dname,name,switch,value,others", SWITCH_CASES,
+                         ids=[f"{c[0]}-{c[1]}-{c[2]}" for c in SWITCH_CASES])
+def test_switch_off_default_settings_stay_inside_the_bar(golden_dir, dname, name, switch, value, others):
+    """The class-level switches of SalUNet at the setting no other test runs: the output against the reference's fixture inside
+    the file's bar (fp32: RTOL relative to the fixture's maximum; 16-bit storage: tests/test_gpu_lowp.py::LOWP_ATOL), and the
+    launch trace differs from the one with the switch at its default, so the case did reach its branch."""
+    from tests import test_gpu_lowp as lowp
+
+    cfg, sd, x, t, feats, audio, g = load_case(golden_dir, name)
+    net = build(cfg, sd) if dname == "fp32" else lowp.build(cfg, sd, lowp.DTYPES[dname])
+    assert getattr(type(net), switch) == (not value)
+    for k, v in others.items():
+        setattr(net, k, v)
+    args = (x.to(DEV), t.to(DEV), [f.to(DEV) for f in feats], None if audio is None else audio.to(DEV))
+    base, _ = _launch_trace(net, args)
+    setattr(net, switch, value)
+    flipped, out = _launch_trace(net, args)
+    ref = torch.from_numpy(g["output"])
+    err = (out.cpu() - ref).abs().max().item()
+    bar = RTOL * ref.abs().max().item() if dname == "fp32" else lowp.LOWP_ATOL[dname]
+    print(f"SWITCH {dname} {name} {switch}={value}: max abs err {err:.3e} (bar {bar:.3e}); launches {len(base)} -> {len(flipped)}")
+    assert out.shape == ref.shape and err < bar
+    assert flipped != base
+
+
 @pytest.fixture
 def bf16x3():
     from diff_sal_amd import ops
