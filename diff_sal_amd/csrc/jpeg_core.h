@@ -133,6 +133,8 @@ constexpr int kC0298 = 2446, kC0390 = 3196, kC0541 = 4433, kC0765 = 6270, kC0899
               kC1847 = 15137, kC1961 = 16069, kC2053 = 16819, kC2562 = 20995, kC3072 = 25172;
 
 JPEG_HD int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
+// the same bits in wrap-around arithmetic: for the decoder, whose coefficients come from a file (jpeg_decode_core.h)
+JPEG_HD uint32_t descale(uint32_t x, int n) { return static_cast<uint32_t>(static_cast<int>(x + (1u << (n - 1))) >> n); }
 
 // one forward pass over eight values d[0], d[S], ..., d[7 S]
 template <int S, bool FIRST>
@@ -172,17 +174,18 @@ JPEG_HD void fdct_quantise(int (&d)[64], const QTab& q) {
   }
 }
 
-template <int S, int N>
-JPEG_HD void idct_pass(int* d) {
-  int z2 = d[2 * S], z3 = d[6 * S];
-  int z1 = (z2 + z3) * kC0541;
-  int t2 = z1 - z3 * kC1847, t3 = z1 + z2 * kC0765;
-  int t0 = (d[0] + d[4 * S]) * 8192, t1 = (d[0] - d[4 * S]) * 8192;
-  const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
+// T: int (the export: its own coefficients, no overflow) or uint32_t (the decoder: any coefficients, defined by wrap-around)
+template <int S, int N, class T>
+JPEG_HD void idct_pass(T* d) {
+  T z2 = d[2 * S], z3 = d[6 * S];
+  T z1 = (z2 + z3) * kC0541;
+  T t2 = z1 - z3 * kC1847, t3 = z1 + z2 * kC0765;
+  T t0 = (d[0] + d[4 * S]) * 8192, t1 = (d[0] - d[4 * S]) * 8192;
+  const T t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
   t0 = d[7 * S]; t1 = d[5 * S]; t2 = d[3 * S]; t3 = d[S];
   z1 = t0 + t3; z2 = t1 + t2; z3 = t0 + t2;
-  int z4 = t1 + t3;
-  const int z5 = (z3 + z4) * kC1175;
+  T z4 = t1 + t3;
+  const T z5 = (z3 + z4) * kC1175;
   t0 *= kC0298; t1 *= kC2053; t2 *= kC3072; t3 *= kC1501;
   z1 *= -kC0899; z2 *= -kC2562;
   z3 = z3 * -kC1961 + z5; z4 = z4 * -kC0390 + z5;
@@ -200,7 +203,8 @@ JPEG_HD int range_limit(int x) {
 }
 
 // d: the quantised coefficients in natural order -> the 64 pixels a libjpeg decoder returns, in raster order
-JPEG_HD void dequantise_idct(int (&d)[64], const QTab& q) {
+template <class T>
+JPEG_HD void dequantise_idct(T (&d)[64], const QTab& q) {
 #pragma unroll
   for (int i = 0; i < 64; ++i) d[i] *= q.t[i];
 #pragma unroll
@@ -208,7 +212,7 @@ JPEG_HD void dequantise_idct(int (&d)[64], const QTab& q) {
 #pragma unroll
   for (int r = 0; r < 8; ++r) idct_pass<1, 18>(d + 8 * r);
 #pragma unroll
-  for (int i = 0; i < 64; ++i) d[i] = range_limit(d[i]);
+  for (int i = 0; i < 64; ++i) d[i] = range_limit(static_cast<int>(d[i]));
 }
 
 // ---- entropy coding ------------------------------------------------------------------------------------------------------------------

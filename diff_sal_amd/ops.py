@@ -2087,6 +2087,29 @@ def jpeg_roundtrip(u8: Tensor, quality: int = 95) -> Tensor:
     return recon
 
 
+def jpeg_decode(packed: Tensor, files: Tensor, segments: Tensor, max_file_seg: int, N: int, H: int, W: int, ncomp: int, hs: int, vs: int,
+                mode_l: bool):
+    """``diffsal_jpeg_decode`` (include/diffsal.h, "JPEG decode"): packed uint8 [nbytes] (a multiple of 4), files uint8 [N, 1392],
+    segments int32 [nseg, 4] -> (frames uint8 [N, H, W, 3] or [N, H, W], status int32 [N])."""
+    lib = _lib.load()
+    for t, dt, what in ((packed, torch.uint8, "packed"), (files, torch.uint8, "files"), (segments, torch.int32, "segments")):
+        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"jpeg_decode: {what} must be a contiguous {dt} GPU tensor, got {t.dtype} {t.device}")
+    if files.shape != (N, 1392) or segments.dim() != 2 or segments.shape[1] != 4:
+        raise ValueError(f"jpeg_decode: files {tuple(files.shape)} (want [{N}, 1392]), segments {tuple(segments.shape)} (want [nseg, 4])")
+    nws = lib.diffsal_jpeg_decode_ws_bytes(N, H, W, ncomp, hs, vs)
+    if nws == 0:
+        raise ValueError(f"jpeg_decode: N={N}, {H} x {W}, {ncomp} components, luma sampling {hs} x {vs}: outside what the decode takes")
+    out = torch.empty((N, H, W) if mode_l else (N, H, W, 3), device=packed.device, dtype=torch.uint8)
+    status = torch.empty((N,), device=packed.device, dtype=torch.int32)
+    ws = torch.empty((nws // 8,), device=packed.device, dtype=torch.float64)
+    with _prof("metrics", 0.0, _nb(packed, out) + 2 * nws):
+        _lib.check(lib.diffsal_jpeg_decode(packed.data_ptr(), packed.numel(), files.data_ptr(), segments.data_ptr(), segments.shape[0],
+                                           int(max_file_seg), N, H, W, ncomp, hs, vs, 1 if mode_l else 0, out.data_ptr(), status.data_ptr(),
+                                           ws.data_ptr(), nws, _stream()), "jpeg_decode")
+    return out, status
+
+
 def logmel(wav: Tensor, wav_dtype: int, wav_len: Optional[Tensor], video: Optional[Tensor], starts: Tensor, ends: Tensor, B: int,
            window: int, n_frames: int, tables: Tensor, *, out_f64: bool = False, sample_rate: int = 16000) -> Tensor:
     """``diffsal_logmel`` (include/diffsal.h, "audio front end") on wav [V, Lmax] -> log-mel [B, n_frames, 64] fp32 (fp64 with

@@ -888,6 +888,59 @@ int diffsal_jpeg_encode(const unsigned char* u8, int B, int h, int w, int qualit
 int diffsal_jpeg_roundtrip(const unsigned char* u8, int B, int h, int w, int quality, unsigned char* recon,
                            diffsal_stream_t stream);
 
+/* ---- JPEG decode: the frame files of the audio-visual sets -> the uint8 frames Pillow returns -----------
+ * R/datasets/saliency_db.py:29-44 decodes img_%05d.jpg with Image.open(f).convert('RGB') (pil_loader) and eyeMap_%05d.jpg with
+ * .convert('L') (pil_loader_sal).  Pillow's decoder is libjpeg-turbo with its defaults; every step is integer arithmetic, and the
+ * result here is bit-equal.  Baseline sequential files only: 8-bit, one component or three read as YCbCr, luma sampling 1x1, 2x1
+ * or 2x2 with chroma 1x1, one interleaved scan; everything else is refused by the caller's parser before a launch.
+ *   (a) entropy   T.81 F.2: codes assigned in order of length (Annex C); DC is a difference from the previous block of the same
+ *                 component, the predictor 0 at the scan start and behind every restart marker; EXTEND(v, n) = v for
+ *                 v >= 2^(n-1), else v - 2^n + 1; AC symbol F0 (ZRL) skips 16 coefficients, 00 (EOB) ends the block; coefficient
+ *                 k of the zig-zag order is stored in natural order; FF 00 in the scan is the byte FF; MCUs in raster order, an
+ *                 MCU holds hs * vs luma blocks, rows first, then one block per chroma component; sizes are padded to whole MCUs
+ *   (b) dequantise   coefficient times table entry, natural order
+ *   (c) transform    the read-back of "JPEG export": libjpeg's jidctint (columns descale 11, rows descale 18) and range limit, in
+ *                    32-bit wrap-around arithmetic (the bits of the int arithmetic wherever that does not overflow)
+ *   (d) chroma    cw = ceil(W / hs), ch = ceil(H / vs): a chroma plane's real size; samples beyond it are never read.
+ *                 hs = 1: none.  cw <= 2: every sample replicated hs x vs times (libjpeg leaves the fancy filters out).
+ *                 2x1, cw > 2:  out[2i] = (3 x[i] + x[i-1] + 1) >> 2,  out[2i+1] = (3 x[i] + x[i+1] + 2) >> 2; the first output
+ *                 column is x[0], the last (2 cw - 1) is x[cw-1].
+ *                 2x2, cw > 2:  rows first, unrounded: r[2j] = 3 x[j] + x[j-1], r[2j+1] = 3 x[j] + x[j+1], the neighbour's row index
+ *                 clamped to 0 .. ch-1; then out[2i] = (3 r[i] + r[i-1] + 8) >> 4, out[2i+1] = (3 r[i] + r[i+1] + 7) >> 4; the
+ *                 first output column is (4 r[0] + 8) >> 4, the last (4 r[cw-1] + 7) >> 4.  The output is cropped to H x W.
+ *   (e) colour    with cb, cr minus 128 and arithmetic shifts:  R = y + ((91881 cr + 32768) >> 16),
+ *                 G = y + ((-22554 cb - 46802 cr + 32768) >> 16),  B = y + ((116130 cb + 32768) >> 16), each clamped to 0..255;
+ *                 one component: R = G = B = y
+ *   (f) L         one component: y.  Three: (19595 R + 38470 G + 7471 B + 32768) >> 16 of (e)'s RGB (Pillow's convert; not Y)
+ * diffsal_jpeg_decode: N files of one size H x W, component count ncomp and luma sampling hs x vs, all in device memory:
+ *   bytes     the files packed back to back, padded with zeros to nbytes, a multiple of 4 below 2^31; 4-byte aligned
+ *   files     N records of 1392 bytes: uint32 scan_off, scan_len (the entropy-coded bytes in `bytes`; informative), restart (MCUs
+ *             per interval, 0: none), seg0, nseg (the file's rows of `segments`), 3 unused; uint8 comp[4][4]: per component its
+ *             quantisation table, DC table, AC table, 0; uint8 qt[4][64]: quantisation tables 0..3 in natural order;
+ *             uint8 hbits[4][16], hvals[4][256]: Huffman tables DC 0, DC 1, AC 0, AC 1 as DHT carries them (counts per length, symbols)
+ *   segments  nseg rows of int32 (file, begin, end, first_mcu): one restart interval each, bytes [begin, end) of `bytes` without the
+ *             RSTn marker; the whole scan when the file has no restart interval.  max_file_seg: the most rows any file has
+ *   out       [N][H][W][3] bytes (mode_l = 0) or [N][H][W] (mode_l = 1), indexed in 64 bits
+ *   status    int32 [N]: 0 clean, else the OR of DIFFSAL_JPEG_BAD_CODE (no Huffman code matches), DIFFSAL_JPEG_BAD_INDEX (a run past
+ *             coefficient 63) and DIFFSAL_JPEG_NO_BITS (a segment ended before its MCUs).  The pixels of such a file are
+ *             unspecified; they lie inside its frame, and the other files of the call are unaffected.  libjpeg's error recovery is
+ *             not reproduced
+ *   ws        >= diffsal_jpeg_decode_ws_bytes(N, H, W, ncomp, hs, vs) bytes, 16-byte aligned: int32 [N] status, int16
+ *             [N][blocks][64] coefficients, uint8 component planes at component resolution (MCU padding included)
+ * For any contents of bytes, files and segments no kernel reads outside them or writes outside out, status and ws: byte ranges
+ * and MCU counts are clamped, selectors masked, every loop bound is a constant or comes from N, H, W, hs, vs.
+ * Launches: a clear of status and coefficients (hipMemsetAsync on `stream`, every call); entropy (a lane per segment, the file's
+ * Huffman tables built in LDS per workgroup; a file without restart markers is decoded by one lane); transform (a lane per
+ * block); colour (up-sampling, RGB, L).  Bit-reproducible; a file's pixels do not depend on the batch it is in.  No allocation, no
+ * synchronisation, no host copy, graph-safe; all argument checks precede the first launch.  ws_bytes: 0 for a bad argument. */
+#define DIFFSAL_JPEG_BAD_CODE 1
+#define DIFFSAL_JPEG_BAD_INDEX 2
+#define DIFFSAL_JPEG_NO_BITS 4
+size_t diffsal_jpeg_decode_ws_bytes(int N, int H, int W, int ncomp, int hs, int vs);
+int diffsal_jpeg_decode(const unsigned char* bytes, long nbytes, const void* files, const int* segments, int nseg, int max_file_seg,
+                        int N, int H, int W, int ncomp, int hs, int vs, int mode_l, unsigned char* out, int* status, void* ws,
+                        size_t ws_bytes, diffsal_stream_t stream);
+
 /* ---- audio front end: PCM samples in device memory -> the audio tensor [B][1][9][h][w] forward_vggish reads -----------
  * What the reference does per clip on the host in numpy: R/datasets/saliency_db.py:449-497 (get_mel_feature) cuts
  * wav[starts[a] : ends[b] + 1] out of the video's waveform (the table of R/datasets/saliency_db.py:208-222), centres it in a
@@ -942,7 +995,7 @@ int diffsal_audio_examples(const float* logmel, const unsigned char* exists, int
  * and Normalize(mean, std); :382-394 stacks and permutes the frames.  R/datasets/meta_data.py:27-35 and
  * R/datasets/dhf1k_data.py:72-81 run transforms.Resize on the PIL image (bilinear), ToTensor and Normalize.  The targets
  * (saliency_db.py:298-301 target_transform, meta_data.py:32-35 sal_transform) are the same resize of an 'L' image and / 255.
- * Decoding and convert('RGB' | 'L') stay with the caller.
+ * JPEG decoding with convert('RGB' | 'L') is diffsal_jpeg_decode ("JPEG decode"); PNG decoding stays with the caller.
  *
  * diffsal_resample_u8: in [N][H0][W0][C] bytes, C = 1 or 3 -> out [N][H1][W1][C] bytes: one Image.resize of Pillow's 8-bit path
  * (ImagingResample), bit for bit.  The coefficients are the caller's, built in float64 as precompute_coeffs builds them, per
