@@ -8,6 +8,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdiffsal_hip.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "diffsal.h")      # the C ABI: compiled into the library, read by _lib.py
 SOURCES = ["igemm.hip", "igemm16.hip", "lin_stream.hip", "wgrad.hip", "backward.hip", "optim.hip", "pack.hip", "norm.hip", "misc.hip", "metrics.hip", "eval_metrics.hip", "postprocess.hip", "jpeg_export.hip", "jpeg_decode.hip", "audio_input.hip", "video_input.hip", "attention.hip", "attn_fold.hip", "mvit.hip", "mvit_pool.hip", "block16.hip", "conv16_halo.hip", "conv16_dma.hip", "gemm16_dma.hip", "attn16_mfma.hip", "tapsum.hip", "tblock.hip", "wino.hip", "gemm_dma.hip", "wino4.hip", "upconv.hip"]
+# headers every translation unit may include: a change rebuilds them all
+SHARED_HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_family.h"), HEADER]
 # headers only one translation unit includes: a change rebuilds that unit alone
 OWN_HEADERS = {"jpeg_export.hip": ["jpeg_core.h"], "jpeg_decode.hip": ["jpeg_core.h", "jpeg_decode_core.h"]}
 
@@ -37,7 +39,7 @@ def needs_build():
     if _flags_changed(os.environ.get("DIFFSAL_EXTRA_HIPCC_FLAGS", "").split()):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + [os.path.join(CSRC, "common.h"), HEADER] + [os.path.join(CSRC, h) for hs in OWN_HEADERS.values() for h in hs]
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + SHARED_HEADERS + [os.path.join(CSRC, h) for hs in OWN_HEADERS.values() for h in hs]
     # an installed copy may ship the binary without its .hip sources: nothing to compare against, nothing to rebuild (the
     # header always ships: _lib.py reads it)
     return any(os.path.exists(d) and os.path.getmtime(d) > t for d in deps)
@@ -64,7 +66,7 @@ def build_library(force=False, verbose=False):
     flags (e.g. -DDIFFSAL_DEV_STAMPS for tools/probe_halo_stamps.py) come from DIFFSAL_EXTRA_HIPCC_FLAGS."""
     if not force and not needs_build():
         return LIB
-    common = [os.path.join(CSRC, "common.h"), HEADER]
+    common = SHARED_HEADERS
     extra = os.environ.get("DIFFSAL_EXTRA_HIPCC_FLAGS", "").split()
     force = force or _flags_changed(extra)
     objs, todo = [], []

@@ -11,7 +11,7 @@
 // A workgroup (4 wavefronts) = one (image, head) and 128 queries; K and V^T of the head in LDS (56 KB at d = 384: two workgroups per
 // CU).  fp32 accumulation and softmax; the probabilities enter O^T as a 16-bit hi + lo pair (no rounding to speak of), one rounding on
 // the output.
-#include "common.h"
+#include "gemm_family.h"
 
 namespace diffsal {
 

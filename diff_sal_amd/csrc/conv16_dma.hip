@@ -23,7 +23,7 @@
 //
 // Accumulation order (chunk, tap, two 16-channel halves, fp32 MFMA accumulation) is that of igemm16.hip / conv16_halo.hip:
 // results are bit-identical to them.  Weight layout: pack_conv_weight's [Cout][Cin / 32][9][32].
-#include "common.h"
+#include "gemm_family.h"
 
 namespace diffsal {
 
@@ -355,40 +355,33 @@ static CdPlan cd_plan(const diffsal_conv_desc* d) {
   return best;
 }
 
-// 1 if this kernel handles the descriptor (16-bit storage assumed)
-int conv16_dma_applies(const diffsal_conv_desc* d, const float* bias, const float* scale, const float* shift, const float* rowvec,
-                       const void* residual, const void* out) {
-  // DIFFSAL_FORCE_HALO = 2 takes this kernel on every shape it can run (tests); = 1 forces conv16_halo.hip's
-  const bool force = tune(TUNE_FORCE_HALO) == 2;
-  if (tune(TUNE_NO_STREAM16) == 1 || tune(TUNE_NO_HALO) == 1 || tune(TUNE_FORCE_HALO) == 1 || tune(TUNE_IGEMM16_CFG) >= 0) return 0;
+// does this kernel run the descriptor?  force (DIFFSAL_FORCE_HALO = 2, tests): on every shape it can run
+bool conv16_dma_takes(const diffsal_conv_desc* d, const GemmOperands* o, Offer& f) {
   const bool shape_ok = d->KH == 3 && d->KW == 3 && d->stride_h == 1 && d->stride_w == 1 && d->dil_h == d->dil_w &&
                         (d->dil_h == 1 || d->dil_h == 2) && d->pad_t == d->pad_l && d->pad_t >= 0 &&
                         d->Ho == d->H + 2 * d->pad_t - 2 * d->dil_h && d->Wo == d->W + 2 * d->pad_l - 2 * d->dil_w &&
                         d->Cin % 32 == 0 && d->Cout % 8 == 0 && d->Ho >= 4 && d->Wo >= 8 && d->Cout >= 64 &&
                         static_cast<long>(d->H) * d->W * d->Cin * 2 < (1L << 31) && static_cast<long>(d->Cout) * 9 * d->Cin * 2 < (1L << 31);
-  if (!shape_ok) return 0;
-  const int ld = d->rowvec_ld > 0 ? d->rowvec_ld : d->Cout;
-  if (!aligned16(out) || !aligned16(residual) || !aligned16(bias) || !aligned16(scale) || !aligned16(shift) || !aligned16(rowvec) ||
-      (rowvec && ld % 4 != 0))
-    return 0;
+  if (!shape_ok) return false;
+  if (o && (o->in2 || !aligned16(o->out) || !aligned16(o->residual) || !aligned16(o->bias) || !aligned16(o->scale) || !aligned16(o->shift) ||
+            !aligned16(o->rowvec) || (o->rowvec && o->rowvec_ld % 4 != 0)))
+    return false;
   const CdPlan pl = cd_plan(d);
-  if (!pl.tile) return 0;
+  if (!pl.tile) return false;
   // Measured against what the planner took before (tools/bench_conv16.py, 4 .. 64 clips): ahead wherever the tiles are not mostly
   // padding (the 9 x 14 extended grid of a 7 x 12 map fills 0.49 of a tile: the generic kernel's flattened rows win) and the
   // launch is not a handful of workgroups with a long K walk (14 x 24 maps of the noise encoder at 4 clips, K = 6912: the generic
   // kernel splits K over the idle CUs)
-  return force || (pl.used >= 0.6 && pl.blocks >= 96 && (pl.blocks >= 512 || 9 * d->Cin <= 3456));
+  return f.flag || (pl.used >= 0.6 && pl.blocks >= 96 && (pl.blocks >= 512 || 9 * d->Cin <= 3456));
 }
 
 template <typename T>
-static int run_cd(const diffsal_conv_desc* d, const void* in, const void* w, const float* bias, const float* scale, const float* shift,
-                  const float* rowvec, const void* residual, void* out, hipStream_t s) {
+static int run_cd(const diffsal_conv_desc* d, const GemmOperands& o, hipStream_t s) {
   CdArgs<T> a;
-  a.in = static_cast<const T*>(in); a.w = static_cast<const T*>(w); a.bias = bias; a.scale = scale; a.shift = shift;
-  a.rowvec = rowvec; a.residual = static_cast<const T*>(residual); a.out = static_cast<T*>(out);
+  a.in = static_cast<const T*>(o.in); a.w = static_cast<const T*>(o.w); a.bias = o.bias; a.scale = o.scale; a.shift = o.shift;
+  a.rowvec = o.rowvec; a.residual = static_cast<const T*>(o.residual); a.out = static_cast<T*>(o.out);
   a.N = d->N; a.H = d->H; a.W = d->W; a.Ho = d->Ho; a.Wo = d->Wo; a.Cin = d->Cin; a.Cout = d->Cout; a.K = 9 * d->Cin;
-  a.dil = d->dil_h; a.pad = d->pad_t; a.act = d->act;
-  a.rowvec_ld = d->rowvec_ld > 0 ? d->rowvec_ld : d->Cout;
+  a.dil = d->dil_h; a.pad = d->pad_t; a.act = d->act; a.rowvec_ld = o.rowvec_ld;
   const CdPlan pl = cd_plan(d);
   // fewer workgroups than CUs on the 256-pixel tiles: 128-pixel tiles (DIFFSAL_CONV16_HALF = 0 / 1: never / on every 8 x 32, 16 x 16 shape)
   const int fh = tune(TUNE_CONV16_HALF);
@@ -401,10 +394,8 @@ static int run_cd(const diffsal_conv_desc* d, const void* in, const void* w, con
   }
 }
 
-int conv16_dma_launch(const diffsal_conv_desc* d, const void* in, const void* w, const float* bias, const float* scale,
-                      const float* shift, const float* rowvec, const void* residual, void* out, hipStream_t s) {
-  if (d->dtype == DIFFSAL_BF16) return run_cd<__bf16>(d, in, w, bias, scale, shift, rowvec, residual, out, s);
-  return run_cd<_Float16>(d, in, w, bias, scale, shift, rowvec, residual, out, s);
+int conv16_dma_launch(const diffsal_conv_desc* d, const GemmOperands& o, const Offer&, hipStream_t s) {
+  return d->dtype == DIFFSAL_BF16 ? run_cd<__bf16>(d, o, s) : run_cd<_Float16>(d, o, s);
 }
 
 }  // namespace diffsal

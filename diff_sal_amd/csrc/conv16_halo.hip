@@ -19,7 +19,7 @@
 // R/models/saliency_decoder/common_block.py:196-216, sal_unet.py:104-112,407).
 #include <cstdlib>
 
-#include "common.h"
+#include "gemm_family.h"
 
 namespace diffsal {
 
@@ -273,13 +273,11 @@ static void halo_tiles(const diffsal_conv_desc* d, bool* wide, bool* n128) {
 }
 
 template <typename T>
-static int run_halo(const diffsal_conv_desc* d, const void* in, const void* w, const float* bias, const float* scale,
-                    const float* shift, const float* rowvec, const void* residual, void* out, hipStream_t s) {
+static int run_halo(const diffsal_conv_desc* d, const GemmOperands& o, hipStream_t s) {
   HaloArgs<T> a;
-  a.in = static_cast<const T*>(in); a.w = static_cast<const T*>(w); a.bias = bias; a.scale = scale; a.shift = shift;
-  a.rowvec = rowvec; a.residual = static_cast<const T*>(residual); a.out = static_cast<T*>(out);
-  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.K = 9 * d->Cin; a.dil = d->dil_h; a.act = d->act;
-  a.rowvec_ld = d->rowvec_ld > 0 ? d->rowvec_ld : d->Cout;
+  a.in = static_cast<const T*>(o.in); a.w = static_cast<const T*>(o.w); a.bias = o.bias; a.scale = o.scale; a.shift = o.shift;
+  a.rowvec = o.rowvec; a.residual = static_cast<const T*>(o.residual); a.out = static_cast<T*>(o.out);
+  a.N = d->N; a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Cout = d->Cout; a.K = 9 * d->Cin; a.dil = d->dil_h; a.act = d->act; a.rowvec_ld = o.rowvec_ld;
 #ifdef DIFFSAL_DEV_STAMPS
   a.stamps = g_halo_stamps;
   if (a.stamps) {   // 8 stamps per workgroup: refuse a buffer the launch would overrun
@@ -296,34 +294,26 @@ static int run_halo(const diffsal_conv_desc* d, const void* in, const void* w, c
   return n128 ? launch_halo<16, 4, 4, T>(a, s) : launch_halo<16, 4, 3, T>(a, s);
 }
 
-// 1 if the halo kernel handles this descriptor (16-bit storage assumed), else 0
-int conv16_halo_applies(const diffsal_conv_desc* d) {
-  bool force = false;
-  if (tune(TUNE_NO_HALO) == 1) return 0;
-  force = tune(TUNE_FORCE_HALO) == 1;
+// does the halo kernel run this descriptor?  force (DIFFSAL_FORCE_HALO = 1, tests): on every shape it can run
+bool conv16_halo_takes(const diffsal_conv_desc* d, const GemmOperands* o, Offer& f) {
   const bool shape_ok = d->KH == 3 && d->KW == 3 && d->stride_h == 1 && d->stride_w == 1 && d->dil_h == d->dil_w &&
                         (d->dil_h == 1 || d->dil_h == 2) && d->pad_t == d->dil_h && d->pad_l == d->dil_w && d->Ho == d->H &&
                         d->Wo == d->W && d->Cin % 32 == 0 && d->Cout % 4 == 0 && d->H >= 8 && d->W >= 16 && d->Cout >= 64;
-  if (!shape_ok) return 0;
+  if (!shape_ok) return false;
   bool wide, n128;
   halo_tiles(d, &wide, &n128);
   const size_t lds = (2 * static_cast<size_t>(16 + 2 * d->dil_h) * ((wide ? 32 : 16) + 2 * d->dil_h) + 6 * (n128 ? 128 : 96)) * HP * 2;
-  if (lds > 160 * 1024) return 0;
-  return force || static_cast<long>(d->N) * d->H * d->W >= 80000;   // below that the generic tiles fill the chip better
-}
-
-// the coalesced epilogue moves 8-byte output / residual pieces and 16-byte parameter pieces
-int conv16_halo_pointers_ok(const diffsal_conv_desc* d, const float* bias, const float* scale, const float* shift,
-                            const float* rowvec, const void* residual, const void* out) {
+  if (lds > 160 * 1024) return false;
+  if (!f.flag && static_cast<long>(d->N) * d->H * d->W < 80000) return false;   // below that the generic tiles fill the chip better
+  if (!o) return true;
+  // the coalesced epilogue moves 8-byte output / residual pieces and 16-byte parameter pieces
   auto al = [](const void* q, uintptr_t m) { return (reinterpret_cast<uintptr_t>(q) & m) == 0; };
-  const int ld = d->rowvec_ld > 0 ? d->rowvec_ld : d->Cout;
-  return al(out, 7) && al(residual, 7) && al(bias, 15) && al(scale, 15) && al(shift, 15) && al(rowvec, 15) && (!rowvec || ld % 4 == 0);
+  return !o->in2 && al(o->out, 7) && al(o->residual, 7) && al(o->bias, 15) && al(o->scale, 15) && al(o->shift, 15) && al(o->rowvec, 15) &&
+         (!o->rowvec || o->rowvec_ld % 4 == 0);
 }
 
-int conv16_halo_launch(const diffsal_conv_desc* d, const void* in, const void* w, const float* bias, const float* scale,
-                       const float* shift, const float* rowvec, const void* residual, void* out, hipStream_t s) {
-  if (d->dtype == DIFFSAL_BF16) return run_halo<__bf16>(d, in, w, bias, scale, shift, rowvec, residual, out, s);
-  return run_halo<_Float16>(d, in, w, bias, scale, shift, rowvec, residual, out, s);
+int conv16_halo_launch(const diffsal_conv_desc* d, const GemmOperands& o, const Offer&, hipStream_t s) {
+  return d->dtype == DIFFSAL_BF16 ? run_halo<__bf16>(d, o, s) : run_halo<_Float16>(d, o, s);
 }
 
 }  // namespace diffsal

@@ -15,7 +15,7 @@
 //     residual in the order of the other 16-bit kernels.  Accumulation: K in order, fp32 -- the same sums as igemm16 / gemm_dma.
 //
 // R/models/saliency_decoder/attention.py:97-111 (proj_q / k / v, proj), common_block.py:125-147 (Mlp), transformer.py:150-157.
-#include "common.h"
+#include "gemm_family.h"
 
 namespace diffsal {
 
@@ -206,43 +206,53 @@ __global__ __launch_bounds__(256, 2) void gemm16_dma2_kernel(GdArgs<T> p) {
   }
 }
 
-// 1 if launched, 0 if the shape is not handled here (the caller goes on to the other kernels), < 0 on error
-int try_gemm16_dma2(const diffsal_conv_desc* d, const void* a, const void* w, const float* bias, const float* scale, const float* shift,
-                    const float* rowvec, int rowvec_ld, const void* residual, void* out, hipStream_t s, bool out_f32) {
-  if (tune(TUNE_NO_STREAM16) == 1 || tune(TUNE_IGEMM16_CFG) >= 0) return 0;
-  const int forced = tune(TUNE_GEMM_DMA16);         // 0: off, 3: on every shape it can run (tests); 1 / 2 force gemm_dma.hip's tiles
-  if (forced == 0 || forced == 1 || forced == 2) return 0;     // 3 / 4: this kernel's 256 x 96 / 192 x 192 tile on every shape it can run
-  const long M = static_cast<long>(d->N) * d->Ho * d->Wo;
-  const int K = d->KH * d->KW * d->Cin, N = d->Cout;
+// the row form (ReduceTemp): taps > 1 rows of one image feed an output row
+static bool gd_rowform(const diffsal_conv_desc* d) { return d->KH > 1 && d->Ho == 1 && d->KH <= d->H; }   // one output frame: the stride does not matter
+
+// f.cfg in: 0 the choice below, 1 / 2 the 256 x 96 / 192 x 192 tile on every shape it can run (DIFFSAL_GEMM_DMA16 = 3 / 4); out: the tile.
+// false: not mine (the caller goes on to the other kernels).
+bool gemm16_dma2_takes(const diffsal_conv_desc* d, const GemmOperands* o, Offer& f) {
+  const int tile = f.cfg;
+  const long M = gemm_M(d);
+  const int K = gemm_K(d), N = d->Cout;
   if (d->dtype == DIFFSAL_F32 || d->KW != 1 || d->stride_w != 1 || d->pad_t != 0 || d->pad_l != 0 || d->dil_h != 1 || d->Wo != d->W) return 0;
   const bool plain = d->KH == 1 && d->stride_h == 1 && d->Ho == d->H;
-  const bool rowform = d->KH > 1 && d->Ho == 1 && d->KH <= d->H;           // one output frame: the stride does not matter
+  const bool rowform = gd_rowform(d);
   if (!plain && !rowform) return 0;
   const long in_bytes = static_cast<long>(d->N) * d->H * d->W * d->Cin * 2;
-  if (K % 32 != 0 || d->Cin % 32 != 0 || K < 64 || N % 8 != 0 || M <= 0 || M >= (1L << 31) || 256L * K * 2 >= (1L << 31) || 96L * K * 2 >= (1L << 31) ||
-      (rowform && (static_cast<long>(d->H) * d->W * d->Cin * 2 * 2 >= (1L << 31) || in_bytes >= (1L << 40))))
+  if (K % 32 != 0 || d->Cin % 32 != 0 || K < 64 || N % 8 != 0 || M <= 0 || M >= (1L << 31) || 256L * K * 2 >= (1L << 31) || 96L * K * 2 >= (1L << 31))
     return 0;
-  if (!aligned16(a) || !aligned16(w) || !aligned16(out) || !aligned16(bias) || !aligned16(scale) || !aligned16(shift) || !aligned16(rowvec) ||
-      !aligned16(residual) || (rowvec && rowvec_ld % 4 != 0) || ((scale == nullptr) != (shift == nullptr)))
-    return 0;
-  if (out_f32 && residual) return 0;
+  // row form: a tile's A rows are addressed with 32-bit byte offsets from the first image the tile touches, and BM consecutive output
+  // rows span up to BM / W + 2 images (256 covers both tile heights)
+  if (rowform && ((256 / d->W + 2) * (static_cast<long>(d->H) * d->W * d->Cin * 2) >= (1L << 31) || in_bytes >= (1L << 40))) return 0;
+  if (o && (o->in2 || (o->out_f32 && o->residual) || !aligned16(o->in) || !aligned16(o->w) || !aligned16(o->out) || !aligned16(o->bias) || !aligned16(o->scale) || !aligned16(o->shift) ||
+        !aligned16(o->rowvec) || !aligned16(o->residual) || (o->rowvec && o->rowvec_ld % 4 != 0) || ((o->scale == nullptr) != (o->shift == nullptr))))
+    return false;
   const long tiles = ((M + 255) / 256) * ((N + 95) / 96);
   if (tiles >= (1L << 31)) return 0;
-  // 192 x 192 tiles (DIFFSAL_GEMM_DMA16 = 4 forces them, 3 the 256 x 96 ones): from 400 tiles on (measured at 4 .. 64 clips: faster than
+  // 192 x 192 tiles: from 400 tiles on (measured at 4 .. 64 clips: faster than
   // both the 256 x 96 tiles and gemm_dma.hip's 96 x 96 ones from ~500 tiles, slower at ~250), unless a quarter of the last tile column
   // lies past N -- or any of it on a short K walk (N = 864, K = 192: 70 -> 78 us; K = 768: 1006 -> 885)
   const long tiles_sq = ((M + 191) / 192) * ((N + 191) / 192);
   const int n_waste = ((N + 191) / 192) * 192 - N;
-  const bool square = forced == 4 || (forced != 3 && tiles_sq >= 400 && (n_waste == 0 || (n_waste <= N / 4 && K >= 384)));
+  const bool square = tile == 2 || (tile != 1 && tiles_sq >= 400 && (n_waste == 0 || (n_waste <= N / 4 && K >= 384)));
   // 256 x 96: from a chip's worth of tiles (two workgroups per CU) on; below that gemm_dma.hip's 96 x 96 tiles (and their K split) fill
   // the chip better
-  if (!square && forced != 3 && tiles < 512) return 0;
+  if (!square && tile != 1 && tiles < 512) return 0;
+  f.cfg = square ? 2 : 1;
+  return true;
+}
+
+int gemm16_dma2_launch(const diffsal_conv_desc* d, const GemmOperands& o, const Offer& f, hipStream_t s) {
+  const long M = gemm_M(d);
+  const int K = gemm_K(d), N = d->Cout;
+  const bool rowform = gd_rowform(d), square = f.cfg == 2;
   const int bm = square ? 192 : 256, bn = square ? 192 : 96;
   const size_t lds = 3 * static_cast<size_t>(bm + bn) * 64 + 1024;
 #define GD_LAUNCH(T, TM_, WN_)                                                                                              \
   do {                                                                                                                      \
-    GdArgs<T> g{static_cast<const T*>(a), static_cast<const T*>(w), bias, scale, shift, rowvec, static_cast<const T*>(residual), out, \
-                static_cast<int>(M), N, K, d->act, rowvec_ld, d->Ho * d->Wo, out_f32 ? 1 : 0, static_cast<int>((M + bm - 1) / bm), (N + bn - 1) / bn, \
+    GdArgs<T> g{static_cast<const T*>(o.in), static_cast<const T*>(o.w), o.bias, o.scale, o.shift, o.rowvec, static_cast<const T*>(o.residual), o.out, \
+                static_cast<int>(M), N, K, d->act, o.rowvec_ld, d->Ho * d->Wo, o.out_f32 ? 1 : 0, static_cast<int>((M + bm - 1) / bm), (N + bn - 1) / bn, \
                 rowform ? d->KH : 1, rowform ? d->W : static_cast<int>(M), rowform ? d->H : 1, d->Cin};                        \
     DS_RAISE_DYNAMIC_LDS((gemm16_dma2_kernel<T, TM_, WN_>), 160 * 1024);                                                    \
     hipLaunchKernelGGL((gemm16_dma2_kernel<T, TM_, WN_>), dim3(static_cast<unsigned>(g.tiles_m) * g.tiles_n), dim3(256), lds, s, g); \
@@ -254,8 +264,7 @@ int try_gemm16_dma2(const diffsal_conv_desc* d, const void* a, const void* w, co
   }
 #undef GD_LAUNCH
   note_kernel("gemm16_dma2_kernel<%s> [%dx%d tile, LDS-DMA, 2 workgroups per CU]", d->dtype == DIFFSAL_BF16 ? "__bf16" : "_Float16", bm, bn);
-  const int rc = check_launch("diffsal_conv_igemm(16-bit DMA, 2 per CU)");
-  return rc == DIFFSAL_OK ? 1 : rc;
+  return check_launch("diffsal_conv_igemm(16-bit DMA, 2 per CU)");
 }
 
 }  // namespace diffsal

@@ -30,7 +30,7 @@
 // {j, j+4}), so results differ from that kernel by fp32 rounding (~1e-7 relative); both are exact-fp32 fmaf chains.
 #include <type_traits>
 
-#include "common.h"
+#include "gemm_family.h"
 
 namespace diffsal {
 
@@ -708,24 +708,31 @@ struct DmaCfg { int bm, bn, stages; };
 constexpr int kNumDmaCfgs = 2;                 // selectable through DIFFSAL_GEMM_DMA; entry 2: the wide tile of batched launches
 const DmaCfg kDmaCfgs[kNumDmaCfgs + 2] = {{96, 96, 3}, {96, 96, 6}, {96, 128, 3}, {192, 192, 3}};   // entry 3: 16-bit storage, large products
 
-// fills the problem-independent part of the arguments; false: shape not handled by tile configuration c.  esz: bytes per
-// element of the storage type (a K slice is 128 bytes of a row)
-bool dma_fill(DmaGemmArgs& g, const DmaCfg& c, const diffsal_conv_desc* d, bool as_conv, int esz, const void* a, const void* w,
-              const float* bias, const float* scale, const float* shift, const float* rowvec, int rowvec_ld, const void* residual, void* out) {
-  const long M = static_cast<long>(d->N) * d->Ho * d->Wo;
-  const int K = d->KH * d->KW * d->Cin, N = d->Cout;
+// does tile configuration c handle the shape (o == nullptr) / the shape with these operands?  esz: bytes per element of the storage type
+// (a K slice is 128 bytes of a row)
+bool dma_fits(const DmaCfg& c, const diffsal_conv_desc* d, bool as_conv, int esz, const GemmOperands* o) {
+  const long M = gemm_M(d);
+  const int K = gemm_K(d), N = d->Cout;
   const int epk = 128 / esz;                                       // elements per K slice
   if (K % epk != 0 || (K / epk) % c.stages != 0) return false;     // a unit must start on ring stage 0
   if (esz != 4 && as_conv) return false;
   // 32-bit byte offsets: plain products address A rows relative to the tile (any M), the output / residual through 64-bit
   // pointers; the weight matrix and (convolutions) the whole input must stay below 4 GiB, which validate() has checked
   if (N % 4 != 0 || M <= 0 || M >= (1L << 31) || static_cast<long>(N) * K * esz >= (1L << 32) - 16 || 96L * K * esz >= (1L << 31)) return false;
-  if (!aligned16(a) || !aligned16(w) || !aligned16(out) || (bias && !aligned16(bias)) || (scale && !(aligned16(scale) && aligned16(shift))) ||
-      (rowvec && !(aligned16(rowvec) && rowvec_ld % 4 == 0)) || (residual && !aligned16(residual)) || d->KH * d->KW > 32)
-    return false;
+  if (d->KH * d->KW > 32) return false;
+  if (!o) return true;
+  if (o->out_f32 && (esz == 4 || o->residual)) return false;       // 16-bit storage only; a residual would be read in the storage type
+  return aligned16(o->in) && aligned16(o->w) && aligned16(o->out) && aligned16(o->bias) && aligned16(o->scale) && aligned16(o->shift) &&
+         aligned16(o->rowvec) && (!o->rowvec || o->rowvec_ld % 4 == 0) && aligned16(o->residual);
+}
+
+// fills the problem-independent part of the arguments (of a problem dma_fits has passed)
+void dma_fill(DmaGemmArgs& g, const DmaCfg& c, const diffsal_conv_desc* d, bool as_conv, int esz, const GemmOperands& o) {
+  const long M = gemm_M(d);
+  const int K = gemm_K(d), N = d->Cout;
   g = DmaGemmArgs{};
-  g.a = a; g.w = w; g.bias = bias; g.scale = scale; g.shift = shift; g.rowvec = rowvec; g.residual = residual; g.out = out;
-  g.M = static_cast<int>(M); g.N = N; g.K = K; g.act = d->act; g.rowvec_ld = rowvec_ld; g.rows_per_img = d->Ho * d->Wo;
+  g.a = o.in; g.w = o.w; g.bias = o.bias; g.scale = o.scale; g.shift = o.shift; g.rowvec = o.rowvec; g.residual = o.residual; g.out = o.out;
+  g.M = static_cast<int>(M); g.N = N; g.K = K; g.act = d->act; g.rowvec_ld = o.rowvec_ld; g.rows_per_img = d->Ho * d->Wo;
   g.n_tiles_m = static_cast<int>((M + c.bm - 1) / c.bm);
   g.n_tiles_n = (N + c.bn - 1) / c.bn;
   g.n_tiles = g.n_tiles_m * g.n_tiles_n;
@@ -735,9 +742,15 @@ bool dma_fill(DmaGemmArgs& g, const DmaCfg& c, const diffsal_conv_desc* d, bool 
     g.in_bytes = static_cast<unsigned>(static_cast<long>(d->N) * d->H * d->W * d->Cin * 4);
   }
   g.splits = 1;
-  g.kt_per_unit = K / epk;
+  g.kt_per_unit = K / (128 / esz);
   g.batch = 1;
-  return true;
+}
+
+// the tile configuration behind cfg for d's storage type, nullptr: none
+const DmaCfg* dma_cfg(int cfg, const diffsal_conv_desc* d) {
+  const bool big16 = cfg == 3 && d->dtype != DIFFSAL_F32;     // 192 x 192 tiles, one workgroup per CU: twice the flops per staged byte
+  if (cfg < 0 || (cfg >= kNumDmaCfgs && !big16) || (d->dtype != DIFFSAL_F32 && cfg != 0 && !big16)) return nullptr;
+  return &kDmaCfgs[cfg];
 }
 
 }  // namespace
@@ -745,54 +758,50 @@ bool dma_fill(DmaGemmArgs& g, const DmaCfg& c, const diffsal_conv_desc* d, bool 
 // Tile configurations of this kernel, in the order of DIFFSAL_GEMM_DMA's value - 1.
 //   0: 96 x 96, 3 stages (72 KB), two workgroups per CU      1: 96 x 96, 6 stages (144 KB), one per CU
 // (96 x 192 tiles were built and measured in round 4: 5-15 % slower on every shape of the step, removed.)
-// as_conv: the convolution form (taps, padding); false = d is a plain [M, K] x [N, K]^T product.  esz: 4 (fp32), 2 (dtype names
-// bf16 or f16; plain products only).  Split-K is planned when the workspace allows (gemm_dma_ws_bytes).  Returns 1 if launched,
-// 0 if the shape is not handled here, < 0 on error.
-size_t gemm_dma_ws_bytes(int cfg, long M, int K, int N, int esz) {
-  if (cfg < 0 || cfg >= kNumDmaCfgs || K % (128 / esz) != 0) return 0;
+// fp32: plain products and, for everything else, the convolution form (taps, padding).  16-bit storage (dtype names bf16 or f16): plain
+// products only, cfg 0 or 3 = 192 x 192 tiles, one workgroup per CU.  Split-K is planned when the workspace allows (gemm_dma_ws_bytes).
+bool gemm_dma_takes(const diffsal_conv_desc* d, const GemmOperands* o, Offer& f) {
+  const DmaCfg* c = dma_cfg(f.cfg, d);
+  return c && dma_fits(*c, d, !is_linear(d), d->dtype == DIFFSAL_F32 ? 4 : 2, o);
+}
+
+// K split of tile configuration cfg on an M x K x N product (1: none, or a shape not handled); *t: the model's time estimate, 1e30 then
+static int dma_split(int cfg, long M, int K, int N, int esz, double* t = nullptr) {
+  if (t) *t = 1e30;
+  if (cfg < 0 || cfg >= kNumDmaCfgs || K % (128 / esz) != 0) return 1;
   const DmaCfg& c = kDmaCfgs[cfg];
-  const long tiles = ((M + c.bm - 1) / c.bm) * ((N + c.bn - 1) / c.bn);
-  const int S = choose_split(tiles, K / (128 / esz), c.stages, M * N);
-  return S > 1 ? static_cast<size_t>(S) * M * N * sizeof(float) : 0;
+  return choose_split(((M + c.bm - 1) / c.bm) * ((N + c.bn - 1) / c.bn), K / (128 / esz), c.stages, M * N, t);
+}
+
+size_t gemm_dma_ws_bytes(const diffsal_conv_desc* d, const Offer& f) {
+  const int S = dma_split(f.cfg, gemm_M(d), gemm_K(d), d->Cout, d->dtype == DIFFSAL_F32 ? 4 : 2);
+  return S > 1 ? static_cast<size_t>(S) * gemm_M(d) * d->Cout * sizeof(float) : 0;
 }
 
 // the planner's time estimate (seconds) for this kernel on a plain fp32 M x K x N product, 1e30 if the shape is not handled
 double gemm_dma_estimate(int cfg, long M, int K, int N) {
-  if (cfg < 0 || cfg >= kNumDmaCfgs || K % 32 != 0 || (K / 32) % kDmaCfgs[cfg].stages != 0) return 1e30;
-  const DmaCfg& c = kDmaCfgs[cfg];
-  const long tiles = ((M + c.bm - 1) / c.bm) * ((N + c.bn - 1) / c.bn);
-  double t = 1e30;
-  choose_split(tiles, K / 32, c.stages, M * N, &t);
+  double t;
+  dma_split(cfg, M, K, N, 4, &t);
   return t;
 }
 
-int try_gemm_dma(int cfg, const diffsal_conv_desc* d, bool as_conv, const void* a, const void* w, const float* bias, const float* scale,
-                 const float* shift, const float* rowvec, int rowvec_ld, const void* residual, void* out, void* ws, size_t ws_bytes,
-                 hipStream_t s, bool out_f32) {
-  const int esz = d->dtype == DIFFSAL_F32 ? 4 : 2;
-  const bool big16 = cfg == 3 && esz == 2;     // 192 x 192 tiles, one workgroup per CU: twice the flops per staged byte
-  if (cfg < 0 || (cfg >= kNumDmaCfgs && !big16)) return 0;
-  const DmaCfg& c = kDmaCfgs[cfg];
+int gemm_dma_launch(const diffsal_conv_desc* d, const GemmOperands& o, const Offer& f, hipStream_t s) {
+  const int cfg = f.cfg, esz = d->dtype == DIFFSAL_F32 ? 4 : 2;
+  const bool as_conv = !is_linear(d), big16 = cfg == 3 && esz == 2;
+  const DmaCfg* c = dma_cfg(cfg, d);
   DmaGemmArgs g;
-  if (!dma_fill(g, c, d, as_conv, esz, a, w, bias, scale, shift, rowvec, rowvec_ld, residual, out)) return 0;
+  dma_fill(g, *c, d, as_conv, esz, o);
   const long MN = static_cast<long>(g.M) * g.N;
   const int kt = g.kt_per_unit;
-  g.splits = big16 ? 1 : choose_split(g.n_tiles, kt, c.stages, MN);
-  if (g.splits > 1 && (!ws || ws_bytes < static_cast<size_t>(g.splits) * MN * sizeof(float) || !aligned16(ws))) g.splits = 1;
+  // fp32 output: no split, the slab sum writes the storage type
+  g.splits = big16 || o.out_f32 ? 1 : choose_split(g.n_tiles, kt, c->stages, MN);
+  if (g.splits > 1 && (!o.ws || o.ws_bytes < static_cast<size_t>(g.splits) * MN * sizeof(float) || !aligned16(o.ws))) g.splits = 1;
   g.kt_per_unit = kt / g.splits;
-  g.partial = g.splits > 1 ? static_cast<float*>(ws) : nullptr;
-  if (out_f32) {
-    if (esz == 4 || residual) return 0;         // 16-bit storage only; a residual would be read in the storage type
-    g.out_f32 = 1;
-    if (g.splits > 1) { g.splits = 1; g.kt_per_unit = kt; g.partial = nullptr; }     // the slab sum writes the storage type
-  }
-  int rc;
-  if (d->dtype == DIFFSAL_F32) rc = cfg == 0 ? launch_dma<float, 3, 3, 3, 2>(g, as_conv, s) : launch_dma<float, 3, 3, 6, 1>(g, as_conv, s);
-  else if (big16) rc = d->dtype == DIFFSAL_BF16 ? launch_dma<bf16_t, 6, 6, 3, 1>(g, false, s) : launch_dma<f16_t, 6, 6, 3, 1>(g, false, s);
-  else if (cfg != 0) return 0;
-  else if (d->dtype == DIFFSAL_BF16) rc = launch_dma<bf16_t, 3, 3, 3, 2>(g, false, s);
-  else rc = launch_dma<f16_t, 3, 3, 3, 2>(g, false, s);
-  return rc == DIFFSAL_OK ? 1 : rc;
+  g.partial = g.splits > 1 ? static_cast<float*>(o.ws) : nullptr;
+  g.out_f32 = o.out_f32 ? 1 : 0;
+  if (d->dtype == DIFFSAL_F32) return cfg == 0 ? launch_dma<float, 3, 3, 3, 2>(g, as_conv, s) : launch_dma<float, 3, 3, 6, 1>(g, as_conv, s);
+  if (big16) return d->dtype == DIFFSAL_BF16 ? launch_dma<bf16_t, 6, 6, 3, 1>(g, false, s) : launch_dma<f16_t, 6, 6, 3, 1>(g, false, s);
+  return d->dtype == DIFFSAL_BF16 ? launch_dma<bf16_t, 3, 3, 3, 2>(g, false, s) : launch_dma<f16_t, 3, 3, 3, 2>(g, false, s);
 }
 
 // `batch` plain fp32 products of one shape in ONE launch of the 96 x 96 / 3-stage kernel, no epilogue: out_b [M, N] = a_b [M, K] x
@@ -822,7 +831,10 @@ int gemm_dma_batched(const float* a, const float* w, float* out, long M, int K, 
   const int force = tune(TUNE_BATCH_TILE);
   const bool wide = N % 128 == 0 && (force == 1 || (force != 0 && t128 * 1.1 < t96));
   DmaGemmArgs g;
-  if (!dma_fill(g, kDmaCfgs[wide ? 2 : 0], &d, false, 4, a, w, nullptr, nullptr, nullptr, nullptr, 0, nullptr, out)) return 0;
+  GemmOperands o{};
+  o.in = a; o.w = w; o.out = out;
+  if (!dma_fits(kDmaCfgs[wide ? 2 : 0], &d, false, 4, &o)) return 0;
+  dma_fill(g, kDmaCfgs[wide ? 2 : 0], &d, false, 4, o);
   g.batch = batch; g.a_bs = a_bs; g.w_bs = w_bs; g.o_bs = o_bs;
   if (side_rows > 0) {
     g.batch2 = static_cast<int>(nb2);
@@ -837,14 +849,11 @@ int gemm_dma_batched(const float* a, const float* w, float* out, long M, int K, 
 // Up to four fp32 problems in ONE launch of the 96 x 96 / 3-stage kernel (convolution form: a plain product is its 1x1 case).
 // No split-K: every problem's units are whole tiles; the host sorts the problems by K slices per unit (longest first) and the
 // grid has one workgroup per unit, so the hardware dispatcher hands the next (shorter) unit to whichever CU frees up first.
-// Returns 1 if launched, 0 if some problem does not fit this kernel (the caller then launches them one by one).
-int try_gemm_dma_group(int n, const diffsal_conv_desc* const* d, const float* const* a, const float* const* w, const float* const* bias,
-                       float* const* out, hipStream_t s) {
-  if (n < 1 || n > kMaxGroup) return 0;
+// The caller has asked gemm_dma_takes (tile configuration 0) about every problem.
+int gemm_dma_group_launch(int n, const diffsal_conv_desc* const* d, const GemmOperands* o, hipStream_t s) {
   const DmaCfg& c = kDmaCfgs[0];
   DmaGemmArgs pr[kMaxGroup];
-  for (int i = 0; i < n; ++i)
-    if (!dma_fill(pr[i], c, d[i], true, 4, a[i], w[i], bias ? bias[i] : nullptr, nullptr, nullptr, nullptr, 0, nullptr, out[i])) return 0;
+  for (int i = 0; i < n; ++i) dma_fill(pr[i], c, d[i], true, 4, o[i]);
   int order[kMaxGroup];
   for (int i = 0; i < n; ++i) order[i] = i;
   for (int i = 0; i < n; ++i)
@@ -867,8 +876,7 @@ int try_gemm_dma_group(int n, const diffsal_conv_desc* const* d, const float* co
   const int grid = persist > 0 && units > persist ? persist : units;
   hipLaunchKernelGGL((gemm_dma_kernel<float, 3, 3, 3, 2, true, true>), dim3(grid), dim3(256), 0, s, g);
   note_kernel("gemm_dma_kernel<float, 3, 3, 3, 2, true, true> [96x96 tile, 3 stages, %d problems, %d units]", n, units);
-  const int rc = check_launch("diffsal_conv_igemm_group(dma)");
-  return rc == DIFFSAL_OK ? 1 : rc;
+  return check_launch("diffsal_conv_igemm_group(dma)");
 }
 
 }  // namespace diffsal

@@ -18,35 +18,13 @@
 //
 // Replaces the cuDNN/cuBLAS call sites behind torch.nn.Conv2d / Linear / Conv3d(k,1,1) in
 // R/models/saliency_decoder/{sal_unet,common_block,attention,transformer}.py (see diffsal.h).
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "gemm_family.h"
 
 namespace diffsal {
-
-// igemm16.hip: the same operator on bf16 / fp16 storage (native 16-bit MFMA)
-size_t igemm16_ws_bytes(const diffsal_conv_desc* d);
-int igemm16_launch(const diffsal_conv_desc* d, const void* in, const void* w, const float* bias, const float* scale,
-                   const float* shift, const float* rowvec, const void* residual, void* out, void* ws, size_t ws_bytes,
-                   hipStream_t s, const void* in2 = nullptr, const void* w2 = nullptr, const float* bias2 = nullptr,
-                   void* out2 = nullptr);
-
-// lin_stream.hip: barrier-free streaming kernel for short-K, huge-M linear layers
-int try_linear_stream(const float* x, const float* w, const float* bias, const float* residual, float* out, long M,
-                      int K, int N, int act, hipStream_t s);
-
-// gemm_dma.hip: products / convolutions with LDS-DMA staging, 96-wide tiles (fp32; plain products also on 16-bit storage)
-int try_gemm_dma(int cfg, const diffsal_conv_desc* d, bool as_conv, const void* a, const void* w, const float* bias, const float* scale,
-                 const float* shift, const float* rowvec, int rowvec_ld, const void* residual, void* out, void* ws, size_t ws_bytes,
-                 hipStream_t s, bool out_f32 = false);
-int try_gemm_dma_group(int n, const diffsal_conv_desc* const* d, const float* const* a, const float* const* w, const float* const* bias,
-                       float* const* out, hipStream_t s);
-size_t gemm_dma_ws_bytes(int cfg, long M, int K, int N, int esz);
-// gemm16_dma.hip: 16-bit plain products on 256 x 96 tiles, two workgroups per CU
-int try_gemm16_dma2(const diffsal_conv_desc* d, const void* a, const void* w, const float* bias, const float* scale, const float* shift,
-                    const float* rowvec, int rowvec_ld, const void* residual, void* out, hipStream_t s, bool out_f32);
-double gemm_dma_estimate(int cfg, long M, int K, int N);
 
 struct IgemmArgs {
   const float* in;
@@ -785,11 +763,6 @@ struct Plan { int cfg, splits; double t; };   // t: the model's time estimate (s
 //   round = max(occ * t_mfma, t_mfma + t_fixed),  time = ceil(workgroups / (256 occ)) * round
 // (+ the slab round trip for split-K).  Short-K GEMMs therefore prefer more, smaller residents;
 // long-K convolutions prefer the widest tile that still fills the chip.
-static bool is_linear(const diffsal_conv_desc* d) {
-  return d->KH == 1 && d->KW == 1 && d->stride_h == 1 && d->stride_w == 1 && d->pad_t == 0 && d->pad_l == 0 && d->Ho == d->H &&
-         d->Wo == d->W;
-}
-
 static Plan choose_plan(long M, int Cout, int K, int precision, bool linear = false) {
   // the bf16x3 loop sustains ~2x the fp32 one on large tiles: split-K slabs and fixed latencies weigh twice as much
   const double mac_per_s_cu = (precision == DIFFSAL_PREC_BF16X3 ? 2.0 : 1.0) * 157.3e12 / 2.0 / kCUs;
@@ -862,7 +835,100 @@ static int launch(IgemmArgs& a, hipStream_t s, int precision) {
 
 using namespace diffsal;
 
-// Which LDS-DMA tile configuration (gemm_dma.hip) takes this fp32 launch, -1: none.
+static int validate(const diffsal_conv_desc* d) {
+  DS_REQUIRE(d, DIFFSAL_E_ARG, "conv_igemm: null descriptor");
+  DS_REQUIRE(d->Cin > 0 && d->Cin % 32 == 0, DIFFSAL_E_SHAPE, "conv_igemm: Cin=%d must be a multiple of 32", d->Cin);
+  DS_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 && d->stride_h > 0 &&
+                 d->stride_w > 0 && d->dil_h > 0 && d->dil_w > 0,
+             DIFFSAL_E_SHAPE, "conv_igemm: non-positive dimension");
+  DS_REQUIRE(d->Ho > 0 && d->Wo > 0, DIFFSAL_E_SHAPE, "conv_igemm: empty output %dx%d", d->Ho, d->Wo);
+  const long M = gemm_M(d);
+  DS_REQUIRE(M < (1L << 31) && M * d->Cout < (1L << 40), DIFFSAL_E_SHAPE, "conv_igemm: problem too large");
+  DS_REQUIRE(d->KH * d->KW <= 32, DIFFSAL_E_SHAPE, "conv_igemm: at most 32 taps (KH*KW=%d)", d->KH * d->KW);
+  DS_REQUIRE(d->precision == DIFFSAL_PREC_FP32 || d->precision == DIFFSAL_PREC_BF16X3, DIFFSAL_E_ARG,
+             "conv_igemm: precision %d (DIFFSAL_PREC_FP32 or DIFFSAL_PREC_BF16X3)", d->precision);
+  DS_REQUIRE(d->dtype == DIFFSAL_F32 || d->dtype == DIFFSAL_BF16 || d->dtype == DIFFSAL_F16, DIFFSAL_E_ARG,
+             "conv_igemm: dtype %d (DIFFSAL_F32, DIFFSAL_BF16 or DIFFSAL_F16)", d->dtype);
+  DS_REQUIRE(d->dtype == DIFFSAL_F32 || (d->precision == DIFFSAL_PREC_FP32 && d->w_format == 0), DIFFSAL_E_ARG,
+             "conv_igemm: 16-bit storage uses the native MFMA (precision and w_format must be 0)");
+  const long esz = d->dtype == DIFFSAL_F32 ? 4 : 2;
+  const long in_bytes = static_cast<long>(d->N) * d->H * d->W * d->Cin * esz;
+  const long w_bytes = static_cast<long>(d->Cout) * d->KH * d->KW * d->Cin * esz;
+  DS_REQUIRE(in_bytes < (1L << 32) - 16 && w_bytes < (1L << 32) - 16, DIFFSAL_E_SHAPE,
+             "conv_igemm: input (%ld B) and weight (%ld B) must each stay below 4 GiB (32-bit buffer offsets); "
+             "split the batch", in_bytes, w_bytes);
+  return DIFFSAL_OK;
+}
+
+// the planner's choice, or the tuning aid's: forced >= 0 (DIFFSAL_IGEMM_CFG) = tile shape (value % 8) and 2^(value / 8) K splits
+static Plan plan_or_forced(const diffsal_conv_desc* d, int forced) {
+  const int K = gemm_K(d);
+  Plan pl = choose_plan(gemm_M(d), d->Cout, K, d->precision, is_linear(d));
+  if (forced >= 0) {
+    pl.cfg = (forced % 8) % kNumCfgs;
+    pl.splits = 1;
+    for (int e = 0; e < forced / 8 && e < 4; ++e)
+      if (K / BK / (pl.splits * 2) >= 4 && d->Cout % 4 == 0) pl.splits *= 2;
+  }
+  return pl;
+}
+
+static size_t igemm_ws_bytes(const diffsal_conv_desc* d, const Offer& f) {
+  const Plan pl = plan_or_forced(d, f.cfg);
+  return pl.splits > 1 ? static_cast<size_t>(pl.splits) * gemm_M(d) * d->Cout * sizeof(float) : 0;
+}
+
+static int igemm_launch(const diffsal_conv_desc* d, const GemmOperands& o, const Offer& f, hipStream_t s) {
+  IgemmArgs a;
+  fill_tiled_args<float>(a, d, o);
+  a.w_split = d->w_format;
+  const Plan pl = plan_or_forced(d, f.cfg);
+  a.splits = pl.splits;
+  a.kt_per_split = (a.K / BK + pl.splits - 1) / pl.splits;
+  if (pl.splits > 1) {
+    const size_t one = static_cast<size_t>(pl.splits) * a.M * d->Cout * sizeof(float);
+    const size_t need = a.pair ? 2 * one : one;
+    DS_REQUIRE(o.ws && o.ws_bytes >= need && aligned16(o.ws) && aligned16(o.out), DIFFSAL_E_ARG,
+               "conv_igemm: split-K needs %zu bytes of 16-byte aligned workspace (diffsal_conv_igemm_ws_bytes), got %zu",
+               need, o.ws_bytes);
+    a.partial = static_cast<float*>(o.ws);
+    a.partial2 = a.pair ? a.partial + one / sizeof(float) : nullptr;
+  }
+  a.vec_epilogue = d->Cout % 4 == 0 && aligned16(o.out) && aligned16(o.residual) && aligned16(o.bias) && aligned16(o.scale) &&
+                   aligned16(o.shift) && aligned16(o.rowvec) && (!o.rowvec || a.rowvec_ld % 4 == 0) && aligned16(o.out2) && aligned16(o.bias2);
+  a.persist_wgs = kCUs * kCfgs[pl.cfg].occ;
+  if (tune(TUNE_NO_PERSIST) == 1) a.persist_wgs = 0;
+  switch (pl.cfg) {
+    case 0: return launch<2, 2, 2, 3>(a, s, d->precision);
+    case 1: return launch<2, 2, 2, 2>(a, s, d->precision);
+    case 2: return launch<4, 1, 1, 3>(a, s, d->precision);
+    case 3: return launch<2, 2, 1, 2>(a, s, d->precision);
+    case 4: return launch<2, 2, 2, 1>(a, s, d->precision);
+    default: return launch<2, 2, 1, 1>(a, s, d->precision);
+  }
+}
+
+// ---- the candidates, in order, and the one function that walks them -----------------------------------------------------------
+//
+// For a descriptor and its operands the FIRST kernel of its storage type's list that is offered (the switches) and takes it (its own
+// predicate; none: everything validate() lets through) launches.  GEMM_DMA_GROUP is off the lists: the grouped form, see launch_group().
+enum Kernel { LIN_STREAM, GEMM16_DMA2, GEMM_DMA, CONV16_DMA, CONV16_HALO, IGEMM16, IGEMM, GEMM_DMA_GROUP };
+struct Candidate {
+  Kernel k;
+  bool (*takes)(const diffsal_conv_desc*, const GemmOperands*, Offer&);
+  size_t (*ws_bytes)(const diffsal_conv_desc*, const Offer&);
+  int (*launch)(const diffsal_conv_desc*, const GemmOperands&, const Offer&, hipStream_t);
+};
+static const Candidate kOrderF32[] = {{LIN_STREAM, lin_stream_takes, nullptr, lin_stream_launch},
+                                      {GEMM_DMA, gemm_dma_takes, gemm_dma_ws_bytes, gemm_dma_launch},
+                                      {IGEMM, nullptr, igemm_ws_bytes, igemm_launch}};
+static const Candidate kOrder16[] = {{GEMM16_DMA2, gemm16_dma2_takes, nullptr, gemm16_dma2_launch},
+                                     {GEMM_DMA, gemm_dma_takes, gemm_dma_ws_bytes, gemm_dma_launch},
+                                     {CONV16_DMA, conv16_dma_takes, nullptr, conv16_dma_launch},
+                                     {CONV16_HALO, conv16_halo_takes, nullptr, conv16_halo_launch},
+                                     {IGEMM16, nullptr, igemm16_ws_bytes, igemm16_launch}};
+
+// Which LDS-DMA tile configuration (gemm_dma.hip) is offered this launch, -1: none.
 //  * plain products with K a multiple of 96 whose tile grid (x K split) fills the chip.  Measured (tools/bench_gemm_dma.py, B = 4
 //    shapes): M = 3024: 1.35x, M = 12096: 1.1-1.2x, M = 48384: 1.0-1.05x against the tiled kernels; at one clip per step
 //    (M = 756 .. 12096) 1.1-1.4x with its K split, but 0.8x on M = 756 x N = 3456 (288 tiles on 256 CUs).
@@ -873,14 +939,20 @@ using namespace diffsal;
 //    (UpEmbed-2 of stage 3: 275 -> 265 us, ReduceTemp of stage 3: 143 -> 136) and M <= ~400 rows with a long K, where its K
 //    split fills the chip (Downsample 768: 61 -> 49 us, ReduceTemp of stage 0: 38 -> 35).  DIFFSAL_CONV_DMA=0 switches it
 //    off, 1..4 force a configuration.
-static int dma_route(const diffsal_conv_desc* d, bool linear, long M, int K, bool pair) {
-  if (d->precision != DIFFSAL_PREC_FP32 || d->w_format != 0 || pair) return -1;
+// DIFFSAL_IGEMM_CFG / DIFFSAL_IGEMM16_CFG >= 0 force the generic kernel of their storage type: everybody else stands down.  (offer()'s helper.)
+static int dma_route(const diffsal_conv_desc* d, bool out_f32) {
+  const long M = gemm_M(d);
+  const int K = gemm_K(d);
+  const bool linear = is_linear(d);
+  if (d->precision != DIFFSAL_PREC_FP32 || d->w_format != 0) return -1;
   if (d->dtype != DIFFSAL_F32) {
     // 16-bit storage: plain products with K a multiple of 192 (three 64-element slices per ring pass).  Measured on the token
     // GEMMs of a B = 4 step (tools/bench_gemm_dma.py, DMA_DTYPE=bf16): 12-19 us instead of 14-25 from ~192 tiles on (the
     // 16-bit products are bound by operand delivery and launch latency, not by the matrix pipe: the DMA ring has no
     // staging instructions to issue); below that the tiled kernel's small tiles win.  DIFFSAL_GEMM_DMA16=0 switches it off, 1
-    // forces it on every shape it accepts.
+    // forces it on every shape it accepts, 2 forces its 192 x 192 tiles (3 / 4 are gemm16_dma2's tiles: where that kernel declines,
+    // this one runs as under 1).
+    if (out_f32) return 0;       // fp32 output exists on this kernel and gemm16_dma2 only: its floor, whatever the switches say
     if (!linear || tune(TUNE_IGEMM16_CFG) >= 0 || K % 192 != 0 || d->Cout % 4 != 0) return -1;
     const int forced = tune(TUNE_GEMM_DMA16);
     if (forced == 0) return -1;
@@ -908,207 +980,121 @@ static int dma_route(const diffsal_conv_desc* d, bool linear, long M, int K, boo
   return ((tiles96 >= 1024 && K <= 1024) || (M <= 400 && K >= 3072)) ? 0 : -1;
 }
 
-static int validate(const diffsal_conv_desc* d) {
-  DS_REQUIRE(d, DIFFSAL_E_ARG, "conv_igemm: null descriptor");
-  DS_REQUIRE(d->Cin > 0 && d->Cin % 32 == 0, DIFFSAL_E_SHAPE, "conv_igemm: Cin=%d must be a multiple of 32", d->Cin);
-  DS_REQUIRE(d->N > 0 && d->H > 0 && d->W > 0 && d->Cout > 0 && d->KH > 0 && d->KW > 0 && d->stride_h > 0 &&
-                 d->stride_w > 0 && d->dil_h > 0 && d->dil_w > 0,
-             DIFFSAL_E_SHAPE, "conv_igemm: non-positive dimension");
-  DS_REQUIRE(d->Ho > 0 && d->Wo > 0, DIFFSAL_E_SHAPE, "conv_igemm: empty output %dx%d", d->Ho, d->Wo);
-  const long M = static_cast<long>(d->N) * d->Ho * d->Wo;
-  DS_REQUIRE(M < (1L << 31) && M * d->Cout < (1L << 40), DIFFSAL_E_SHAPE, "conv_igemm: problem too large");
-  DS_REQUIRE(d->KH * d->KW <= 32, DIFFSAL_E_SHAPE, "conv_igemm: at most 32 taps (KH*KW=%d)", d->KH * d->KW);
-  DS_REQUIRE(d->precision == DIFFSAL_PREC_FP32 || d->precision == DIFFSAL_PREC_BF16X3, DIFFSAL_E_ARG,
-             "conv_igemm: precision %d (DIFFSAL_PREC_FP32 or DIFFSAL_PREC_BF16X3)", d->precision);
-  DS_REQUIRE(d->dtype == DIFFSAL_F32 || d->dtype == DIFFSAL_BF16 || d->dtype == DIFFSAL_F16, DIFFSAL_E_ARG,
-             "conv_igemm: dtype %d (DIFFSAL_F32, DIFFSAL_BF16 or DIFFSAL_F16)", d->dtype);
-  DS_REQUIRE(d->dtype == DIFFSAL_F32 || (d->precision == DIFFSAL_PREC_FP32 && d->w_format == 0), DIFFSAL_E_ARG,
-             "conv_igemm: 16-bit storage uses the native MFMA (precision and w_format must be 0)");
-  const long esz = d->dtype == DIFFSAL_F32 ? 4 : 2;
-  const long in_bytes = static_cast<long>(d->N) * d->H * d->W * d->Cin * esz;
-  const long w_bytes = static_cast<long>(d->Cout) * d->KH * d->KW * d->Cin * esz;
-  DS_REQUIRE(in_bytes < (1L << 32) - 16 && w_bytes < (1L << 32) - 16, DIFFSAL_E_SHAPE,
-             "conv_igemm: input (%ld B) and weight (%ld B) must each stay below 4 GiB (32-bit buffer offsets); "
-             "split the batch", in_bytes, w_bytes);
+// The one place that reads the switches which choose BETWEEN kernels (a kernel's own tile switches stay with it): is candidate k
+// offered this call, and with what (f, see gemm_family.h)?
+static bool offer(Kernel k, const diffsal_conv_desc* d, bool pair, bool out_f32, Offer& f) {
+  f = Offer{0, false};
+  // a pair launch exists on the generic kernels only; fp32 output (plain 16-bit products) on gemm16_dma2 and gemm_dma only
+  if ((pair && k != IGEMM && k != IGEMM16) || (out_f32 && k != GEMM16_DMA2 && k != GEMM_DMA)) return false;
+  // the 16-bit kernels with two workgroups per CU: DIFFSAL_NO_STREAM16 = 1 switches them off
+  const bool stream16 = tune(TUNE_NO_STREAM16) != 1 && tune(TUNE_IGEMM16_CFG) < 0;
+  // DIFFSAL_FORCE_HALO = 1 / 2 takes conv16_halo / conv16_dma on every shape it can run (tests); DIFFSAL_NO_HALO = 1: neither
+  const bool no_halo = tune(TUNE_NO_HALO) == 1;
+  const int halo = tune(TUNE_FORCE_HALO), dma16 = tune(TUNE_GEMM_DMA16);
+  switch (k) {
+    case LIN_STREAM: return true;
+    // DIFFSAL_GEMM_DMA16: 0 off, 1 / 2 force gemm_dma.hip's tiles, 3 / 4 this kernel's 256 x 96 / 192 x 192 tile
+    case GEMM16_DMA2: f.cfg = dma16 == 3 ? 1 : dma16 == 4 ? 2 : 0; return stream16 && !(dma16 >= 0 && dma16 <= 2);
+    case GEMM_DMA: f.cfg = dma_route(d, out_f32); return f.cfg >= 0;
+    // the grouped form of gemm_dma (up to four fp32 problems in one launch, exact arithmetic): off with DIFFSAL_GEMM_DMA = 0 and when
+    // the tiled kernel is forced
+    case GEMM_DMA_GROUP:
+      return tune(TUNE_GEMM_DMA) != 0 && tune(TUNE_IGEMM_CFG) < 0 && d->dtype == DIFFSAL_F32 && d->precision == DIFFSAL_PREC_FP32 && d->w_format == 0;
+    case CONV16_DMA: f.flag = halo == 2; return stream16 && !no_halo && halo != 1;
+    case CONV16_HALO: f.flag = halo == 1; return !no_halo;
+    case IGEMM16: {
+      // The one cross-kernel exception, kept here: a shape the halo kernel takes reaches this kernel only with pointers the halo kernel
+      // refuses -- which a K split's slab sum could not use either -- so it runs unsplit, and the workspace query, a plain maximum over
+      // the list, reports none for it.
+      Offer h;
+      f.flag = offer(CONV16_HALO, d, false, false, h) && conv16_halo_takes(d, nullptr, h);
+      f.cfg = tune(TUNE_IGEMM16_CFG);
+      return true;
+    }
+    default: f.cfg = tune(TUNE_IGEMM_CFG); return true;
+  }
+}
+
+static void plan_debug(const diffsal_conv_desc* d) {   // tuning aid: the kernel, tile shape and split that took the launch
+  if (tune(TUNE_PLAN_DEBUG) == 1)
+    fprintf(stderr, "[diffsal plan] M=%ld K=%d N=%d linear=%d -> %s\n", gemm_M(d), gemm_K(d), d->Cout, is_linear(d) ? 1 : 0,
+            diffsal_last_gemm_kernel());
+}
+
+// With operands: launches the first taker.  Without (the workspace query): *need = the largest workspace any taker could use.
+static int walk(const diffsal_conv_desc* d, const GemmOperands* o, hipStream_t s, size_t* need) {
+  const bool f32 = d->dtype == DIFFSAL_F32;
+  const Candidate* list = f32 ? kOrderF32 : kOrder16;
+  const int n = f32 ? sizeof(kOrderF32) / sizeof(Candidate) : sizeof(kOrder16) / sizeof(Candidate);
+  for (int i = 0; i < n; ++i) {
+    const Candidate& c = list[i];
+    Offer f;
+    if (!offer(c.k, d, o && o->in2, o && o->out_f32, f) || (c.takes && !c.takes(d, o, f))) continue;
+    if (!o) { *need = std::max(*need, c.ws_bytes ? c.ws_bytes(d, f) : 0); continue; }
+    const int rc = c.launch(d, *o, f, s);
+    if (rc == DIFFSAL_OK) plan_debug(d);
+    return rc;
+  }
+  // only a list without its generic kernel (fp32 output) gets here
+  DS_REQUIRE(!o, DIFFSAL_E_SHAPE, "no kernel with fp32 output takes K=%d, N=%d (K must be a multiple of 192 and N of 4)", gemm_K(d), d->Cout);
   return DIFFSAL_OK;
 }
 
-// the planner's choice, or the tuning aid's: DIFFSAL_IGEMM_CFG = tile shape (value % 8) and 2^(value / 8) K splits
-static Plan plan_or_forced(long M, int Cout, int K, int precision, bool linear) {
-  Plan pl = choose_plan(M, Cout, K, precision, linear);
-  const int v = tune(TUNE_IGEMM_CFG);
-  if (v >= 0) {
-    pl.cfg = (v % 8) % kNumCfgs;
-    pl.splits = 1;
-    for (int e = 0; e < v / 8 && e < 4; ++e)
-      if (K / BK / (pl.splits * 2) >= 4 && Cout % 4 == 0) pl.splits *= 2;
+// the grouped form of gemm_dma where it is offered and every problem fits its 96 x 96 / 3-stage tile: 1 launched, 0 not taken, < 0 error
+static int launch_group(int n, const diffsal_conv_desc* const* d, const GemmOperands* o, hipStream_t s) {
+  for (int i = 0; i < n; ++i) {
+    Offer f;
+    if (!offer(GEMM_DMA_GROUP, d[i], false, false, f) || !gemm_dma_takes(d[i], &o[i], f)) return 0;
   }
-  return pl;
+  const int rc = gemm_dma_group_launch(n, d, o, s);
+  if (rc == DIFFSAL_OK) plan_debug(d[0]);
+  return rc == DIFFSAL_OK ? 1 : rc;
 }
 
 extern "C" size_t diffsal_conv_igemm_ws_bytes(const diffsal_conv_desc* d) {
-  if (validate(d) != DIFFSAL_OK) return 0;
-  const long M = static_cast<long>(d->N) * d->Ho * d->Wo;
-  const int K = d->KH * d->KW * d->Cin;
-  size_t need;
-  if (d->dtype != DIFFSAL_F32) {
-    need = igemm16_ws_bytes(d);
-  } else {
-    const Plan pl = plan_or_forced(M, d->Cout, K, d->precision, is_linear(d));
-    need = pl.splits > 1 ? static_cast<size_t>(pl.splits) * M * d->Cout * sizeof(float) : 0;
-  }
-  const int r = dma_route(d, is_linear(d), M, K, false);
-  if (r >= 0) {
-    const size_t nd = gemm_dma_ws_bytes(r, M, K, d->Cout, d->dtype == DIFFSAL_F32 ? 4 : 2);
-    need = nd > need ? nd : need;
-  }
+  size_t need = 0;
+  if (validate(d) == DIFFSAL_OK) walk(d, nullptr, nullptr, &need);
   return need;
 }
 
-// second problem of a pair launch (same descriptor): diffsal_linear_pair
-struct PairExtra {
-  const void* in2;
-  const void* w2;
-  const float* bias2;
-  void* out2;
-};
-
-static int conv_igemm_impl(const diffsal_conv_desc* d, const void* in_v, const void* w_v, const float* bias, const float* scale,
-                           const float* shift, const float* rowvec, const void* residual_v, void* out_v, void* ws,
-                           size_t ws_bytes, diffsal_stream_t stream, const PairExtra* px) {
+static int conv_igemm_impl(const diffsal_conv_desc* d, GemmOperands& o, diffsal_stream_t stream) {
   int rc = validate(d);
   if (rc) return rc;
-  DS_REQUIRE(in_v && w_v && out_v, DIFFSAL_E_ARG, "conv_igemm: null argument");
-  DS_REQUIRE((scale == nullptr) == (shift == nullptr), DIFFSAL_E_ARG, "conv_igemm: scale and shift go together");
-  DS_REQUIRE(aligned16(in_v) && aligned16(w_v), DIFFSAL_E_ALIGN, "conv_igemm: in/w must be 16-byte aligned");
+  DS_REQUIRE(o.in && o.w && o.out, DIFFSAL_E_ARG, "conv_igemm: null argument");
+  DS_REQUIRE((o.scale == nullptr) == (o.shift == nullptr), DIFFSAL_E_ARG, "conv_igemm: scale and shift go together");
+  DS_REQUIRE(aligned16(o.in) && aligned16(o.w), DIFFSAL_E_ALIGN, "conv_igemm: in/w must be 16-byte aligned");
   DS_REQUIRE((d->act >= DIFFSAL_ACT_NONE && d->act <= DIFFSAL_ACT_SIGMOID) ||
-                 (d->act == DIFFSAL_ACT_GELU_GRAD && d->dtype == DIFFSAL_F32 && residual_v && !px),
+                 (d->act == DIFFSAL_ACT_GELU_GRAD && d->dtype == DIFFSAL_F32 && o.residual && !o.in2),
              DIFFSAL_E_ARG, "conv_igemm: act=%d (DIFFSAL_ACT_GELU_GRAD: fp32 only, the pre-activation goes in `residual`)", d->act);
-  if (d->dtype != DIFFSAL_F32 && !px && d->precision == DIFFSAL_PREC_FP32 && d->w_format == 0 && d->act != DIFFSAL_ACT_GELU_GRAD) {
-    // plain products and ReduceTemp's row form
-    const int rr = try_gemm16_dma2(d, in_v, w_v, bias, scale, shift, rowvec, d->rowvec_ld > 0 ? d->rowvec_ld : d->Cout, residual_v, out_v,
-                                   static_cast<hipStream_t>(stream), false);
-    if (rr != 0) return rr < 0 ? rr : DIFFSAL_OK;
-  }
-  if (d->dtype != DIFFSAL_F32) {
-    const long M16 = static_cast<long>(d->N) * d->Ho * d->Wo;
-    const int r16 = dma_route(d, is_linear(d), M16, d->KH * d->KW * d->Cin, px != nullptr);
-    if (r16 >= 0 && (!rowvec || d->rowvec_ld % 4 == 0)) {
-      const int rr = try_gemm_dma(r16, d, false, in_v, w_v, bias, scale, shift, rowvec, d->rowvec_ld > 0 ? d->rowvec_ld : d->Cout, residual_v,
-                                  out_v, ws, ws_bytes, static_cast<hipStream_t>(stream));
-      if (rr != 0) return rr < 0 ? rr : DIFFSAL_OK;
-    }
-  }
-  if (d->dtype != DIFFSAL_F32)
-    return igemm16_launch(d, in_v, w_v, bias, scale, shift, rowvec, residual_v, out_v, ws, ws_bytes,
-                          static_cast<hipStream_t>(stream), px ? px->in2 : nullptr, px ? px->w2 : nullptr,
-                          px ? px->bias2 : nullptr, px ? px->out2 : nullptr);
-  const float* in = static_cast<const float*>(in_v);
-  const float* w = static_cast<const float*>(w_v);
-  const float* residual = static_cast<const float*>(residual_v);
-  float* out = static_cast<float*>(out_v);
-  const long M = static_cast<long>(d->N) * d->Ho * d->Wo;
-
-  IgemmArgs a;
-  a.xcd_order = 0;
-  a.pair = px ? 1 : 0;
-  a.in2 = px ? static_cast<const float*>(px->in2) : nullptr;
-  a.w2 = px ? static_cast<const float*>(px->w2) : nullptr;
-  a.bias2 = px ? px->bias2 : nullptr;
-  a.out2 = px ? static_cast<float*>(px->out2) : nullptr;
-  a.partial2 = nullptr;
-  a.in = in; a.w = w; a.bias = bias; a.scale = scale; a.shift = shift; a.rowvec = rowvec;
-  a.residual = residual; a.out = out;
-  a.M = static_cast<int>(M);
-  a.K = d->KH * d->KW * d->Cin;
-  a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
-  a.KW = d->KW; a.taps = d->KH * d->KW; a.stride_h = d->stride_h; a.stride_w = d->stride_w;
-  a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.dil_h = d->dil_h; a.dil_w = d->dil_w; a.act = d->act;
-  a.rowvec_ld = d->rowvec_ld > 0 ? d->rowvec_ld : d->Cout;
-  a.linear = d->KH == 1 && d->KW == 1 && d->stride_h == 1 && d->stride_w == 1 && d->pad_t == 0 && d->pad_l == 0 && d->Ho == d->H && d->Wo == d->W;
   DS_REQUIRE(d->w_format == 0 || (d->w_format == 1 && d->precision == DIFFSAL_PREC_BF16X3), DIFFSAL_E_ARG,
              "conv_igemm: w_format=%d needs precision = DIFFSAL_PREC_BF16X3 in the descriptor", d->w_format);
-  a.w_split = d->w_format;
-  a.in_bytes = static_cast<unsigned>(static_cast<long>(d->N) * d->H * d->W * d->Cin * 4);
-  a.w_bytes = static_cast<unsigned>(static_cast<long>(d->Cout) * a.K * 4);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-
-  if (d->w_format == 0 && d->KH == 1 && d->KW == 1 && d->stride_h == 1 && d->stride_w == 1 && d->pad_t == 0 && d->pad_l == 0 &&
-      d->Ho == d->H && d->Wo == d->W && !scale && !rowvec && aligned16(out) && (!residual || aligned16(residual)) && !px &&
-      d->act != DIFFSAL_ACT_GELU_GRAD) {
-    const int r = try_linear_stream(in, w, bias, residual, out, M, d->Cin, d->Cout, d->act, s);
-    if (r > 0) note_kernel("lin_stream_kernel [K=%d, N=%d]", d->Cin, d->Cout);
-    if (r != 0) return r < 0 ? r : DIFFSAL_OK;
-  }
-  {
-    const int r = dma_route(d, a.linear != 0, M, a.K, px != nullptr);
-    if (r >= 0) {
-      const int rr = try_gemm_dma(r, d, !a.linear, in, w, bias, scale, shift, rowvec, a.rowvec_ld, residual, out, ws, ws_bytes, s);
-      if (rr != 0) return rr < 0 ? rr : DIFFSAL_OK;
-    }
-  }
-  const Plan pl = plan_or_forced(M, d->Cout, a.K, d->precision, a.linear != 0);
-  if (tune(TUNE_PLAN_DEBUG) == 1) {   // tuning aid: which tile shape / split the planner chose
-    fprintf(stderr, "[diffsal plan] M=%ld K=%d N=%d linear=%d -> %dx%d splits=%d\n", M, a.K, d->Cout, a.linear,
-                             kCfgs[pl.cfg].bm, kCfgs[pl.cfg].bn, pl.splits);
-  }
-  a.splits = pl.splits;
-  a.kt_per_split = (a.K / BK + pl.splits - 1) / pl.splits;
-  a.partial = nullptr;
-  if (pl.splits > 1) {
-    const size_t one = static_cast<size_t>(pl.splits) * M * d->Cout * sizeof(float);
-    const size_t need = px ? 2 * one : one;
-    DS_REQUIRE(ws && ws_bytes >= need && aligned16(ws) && aligned16(out), DIFFSAL_E_ARG,
-               "conv_igemm: split-K needs %zu bytes of 16-byte aligned workspace (diffsal_conv_igemm_ws_bytes), got %zu",
-               need, ws_bytes);
-    a.partial = static_cast<float*>(ws);
-    a.partial2 = px ? a.partial + one / sizeof(float) : nullptr;
-  }
-  a.vec_epilogue = d->Cout % 4 == 0 && aligned16(out) && (!residual || aligned16(residual)) && (!bias || aligned16(bias)) &&
-                   (!scale || (aligned16(scale) && aligned16(shift))) && (!rowvec || (aligned16(rowvec) && a.rowvec_ld % 4 == 0));
-  if (px) a.vec_epilogue = a.vec_epilogue && aligned16(px->out2) && (!px->bias2 || aligned16(px->bias2));
-  a.persist_wgs = kCUs * kCfgs[pl.cfg].occ;
-  if (tune(TUNE_NO_PERSIST) == 1) a.persist_wgs = 0;
-  switch (pl.cfg) {
-    case 0: return launch<2, 2, 2, 3>(a, s, d->precision);
-    case 1: return launch<2, 2, 2, 2>(a, s, d->precision);
-    case 2: return launch<4, 1, 1, 3>(a, s, d->precision);
-    case 3: return launch<2, 2, 1, 2>(a, s, d->precision);
-    case 4: return launch<2, 2, 2, 1>(a, s, d->precision);
-    default: return launch<2, 2, 1, 1>(a, s, d->precision);
-  }
+  o.rowvec_ld = rowvec_ld(d);
+  return walk(d, &o, static_cast<hipStream_t>(stream), nullptr);
 }
 
 extern "C" int diffsal_conv_igemm(const diffsal_conv_desc* d, const void* in_v, const void* w_v,
                                   const float* bias, const float* scale, const float* shift,
                                   const float* rowvec, const void* residual_v, void* out_v, void* ws,
                                   size_t ws_bytes, diffsal_stream_t stream) {
-  return conv_igemm_impl(d, in_v, w_v, bias, scale, shift, rowvec, residual_v, out_v, ws, ws_bytes, stream, nullptr);
+  GemmOperands o{in_v, w_v, bias, scale, shift, rowvec, 0, residual_v, out_v, ws, ws_bytes};
+  return conv_igemm_impl(d, o, stream);
 }
 
 extern "C" int diffsal_conv_igemm_group(int n, const diffsal_conv_desc* const* descs, const void* const* in, const void* const* w,
                                         const float* const* bias, void* const* out, void* ws, size_t ws_bytes, diffsal_stream_t stream) {
   DS_REQUIRE(n >= 1 && n <= 4 && descs && in && w && out, DIFFSAL_E_ARG, "conv_igemm_group: 1..4 problems, non-null tables");
-  bool dma_ok = tune(TUNE_GEMM_DMA) != 0 && tune(TUNE_IGEMM_CFG) < 0;
+  GemmOperands o[4] = {};
   for (int i = 0; i < n; ++i) {
     const int rc = validate(descs[i]);
     if (rc) return rc;
     DS_REQUIRE(in[i] && w[i] && out[i], DIFFSAL_E_ARG, "conv_igemm_group: null operand of problem %d", i);
     DS_REQUIRE(descs[i]->act >= DIFFSAL_ACT_NONE && descs[i]->act <= DIFFSAL_ACT_SIGMOID, DIFFSAL_E_ARG, "conv_igemm_group: act=%d", descs[i]->act);
-    dma_ok = dma_ok && descs[i]->dtype == DIFFSAL_F32 && descs[i]->precision == DIFFSAL_PREC_FP32 && descs[i]->w_format == 0;
+    o[i].in = in[i]; o[i].w = w[i]; o[i].bias = bias ? bias[i] : nullptr; o[i].out = out[i]; o[i].ws = ws; o[i].ws_bytes = ws_bytes;
   }
-  if (dma_ok) {
-    const float* a_[4]; const float* w_[4]; const float* b_[4]; float* o_[4];
-    for (int i = 0; i < n; ++i) {
-      a_[i] = static_cast<const float*>(in[i]); w_[i] = static_cast<const float*>(w[i]);
-      b_[i] = bias ? bias[i] : nullptr; o_[i] = static_cast<float*>(out[i]);
-    }
-    const int r = try_gemm_dma_group(n, descs, a_, w_, b_, o_, static_cast<hipStream_t>(stream));
-    if (r != 0) return r < 0 ? r : DIFFSAL_OK;
-  }
+  const int r = launch_group(n, descs, o, static_cast<hipStream_t>(stream));
+  if (r != 0) return r < 0 ? r : DIFFSAL_OK;
   for (int i = 0; i < n; ++i) {     // some problem does not fit the grouped kernel: one launch each (same results)
-    const int rc = conv_igemm_impl(descs[i], in[i], w[i], bias ? bias[i] : nullptr, nullptr, nullptr, nullptr, nullptr, out[i], ws, ws_bytes,
-                                   stream, nullptr);
+    const int rc = conv_igemm_impl(descs[i], o[i], stream);
     if (rc) return rc;
   }
   return DIFFSAL_OK;
@@ -1117,7 +1103,7 @@ extern "C" int diffsal_conv_igemm_group(int n, const diffsal_conv_desc* const* d
 /* 16-bit storage in, fp32 out: out [M, N] (fp32) = act(in [M, K] x w [N, K]^T + bias) for a plain product described by d (KH = KW = 1,
  * dtype bf16 / f16): the sums leave the matrix cores without a rounding to the storage type -- for consumers that add many of them
  * (the nine tap products of mt_proj under the 4-scale interpolation, R/models/saliency_decoder/sal_unet.py:480-489).  Runs on
- * gemm_dma_kernel only: K % 192 == 0, N % 4 == 0; DIFFSAL_E_SHAPE otherwise. */
+ * gemm16_dma2_kernel or gemm_dma_kernel only: K % 192 == 0, N % 4 == 0; DIFFSAL_E_SHAPE otherwise. */
 extern "C" int diffsal_linear_f32out(const diffsal_conv_desc* d, const void* in, const void* w, const float* bias, float* out,
                                      diffsal_stream_t stream) {
   DS_REQUIRE(d && in && w && out, DIFFSAL_E_ARG, "linear_f32out: null argument");
@@ -1127,42 +1113,33 @@ extern "C" int diffsal_linear_f32out(const diffsal_conv_desc* d, const void* in,
                  d->act >= DIFFSAL_ACT_NONE && d->act <= DIFFSAL_ACT_SIGMOID,
              DIFFSAL_E_ARG, "linear_f32out: a plain product on bf16 / f16 storage");
   DS_REQUIRE(aligned16(in) && aligned16(w) && aligned16(out) && (!bias || aligned16(bias)), DIFFSAL_E_ALIGN, "linear_f32out: misaligned pointer");
-  int rr = try_gemm16_dma2(d, in, w, bias, nullptr, nullptr, nullptr, d->Cout, nullptr, out, static_cast<hipStream_t>(stream), true);
-  if (rr == 0)
-    rr = try_gemm_dma(0, d, false, in, w, bias, nullptr, nullptr, nullptr, d->Cout, nullptr, out, nullptr, 0,
-                      static_cast<hipStream_t>(stream), true);
-  if (rr < 0) return rr;
-  DS_REQUIRE(rr == 1, DIFFSAL_E_SHAPE, "linear_f32out: K=%d must be a multiple of 192 and N=%d of 4", d->KH * d->KW * d->Cin, d->Cout);
-  return DIFFSAL_OK;
+  GemmOperands o{};
+  o.in = in; o.w = w; o.bias = bias; o.out = out; o.rowvec_ld = d->Cout; o.out_f32 = true;
+  return walk(d, &o, static_cast<hipStream_t>(stream), nullptr);
 }
 
 extern "C" int diffsal_linear_pair(const diffsal_conv_desc* d, const void* in0, const void* in1, const void* w0, const void* w1,
                                    const float* bias0, const float* bias1, void* out0, void* out1, void* ws, size_t ws_bytes,
                                    diffsal_stream_t stream) {
   DS_REQUIRE(d && in0 && in1 && w0 && w1 && out0 && out1, DIFFSAL_E_ARG, "linear_pair: null argument");
-  DS_REQUIRE(d->KH == 1 && d->KW == 1 && d->stride_h == 1 && d->stride_w == 1 && d->pad_t == 0 && d->pad_l == 0 &&
-                 d->Ho == d->H && d->Wo == d->W && d->act == DIFFSAL_ACT_NONE && d->w_format == 0 && d->precision == DIFFSAL_PREC_FP32,
+  DS_REQUIRE(is_linear(d) && d->act == DIFFSAL_ACT_NONE && d->w_format == 0 && d->precision == DIFFSAL_PREC_FP32,
              DIFFSAL_E_SHAPE, "linear_pair: two plain [M,K] x [K,N] products of one shape (1x1, no activation, exact arithmetic)");
   DS_REQUIRE((bias0 == nullptr) == (bias1 == nullptr), DIFFSAL_E_ARG, "linear_pair: both products carry a bias or neither does");
   DS_REQUIRE(aligned16(in1) && aligned16(w1), DIFFSAL_E_ALIGN, "linear_pair: in/w must be 16-byte aligned");
-  {
-    // fp32 pairs whose 96 x 96 tiles fill three quarters of the CUs: the LDS-DMA kernel's grouped form (same sums, another order).
-    // Measured at B = 4, 2 x (M = 648, K = 768, N = 1536), 224 tiles: 38.6 us against 47.3 on the paired 64 x 64 kernel; the
-    // 112 tiles of (K = 384, N = 768) lose, 25.3 against 18.3.
-    const long M = static_cast<long>(d->N) * d->Ho * d->Wo;
-    const long tiles = 2 * ((M + 95) / 96) * ((d->Cout + 95) / 96);
-    if (d->dtype == DIFFSAL_F32 && tiles >= 192 && tune(TUNE_GEMM_DMA) != 0 && tune(TUNE_IGEMM_CFG) < 0) {
-      const int rv = validate(d);
-      if (rv) return rv;
-      const diffsal_conv_desc* dd[2] = {d, d};
-      const float* a_[2] = {static_cast<const float*>(in0), static_cast<const float*>(in1)};
-      const float* w_[2] = {static_cast<const float*>(w0), static_cast<const float*>(w1)};
-      const float* b_[2] = {bias0, bias1};
-      float* o_[2] = {static_cast<float*>(out0), static_cast<float*>(out1)};
-      const int r = try_gemm_dma_group(2, dd, a_, w_, b_, o_, static_cast<hipStream_t>(stream));
-      if (r != 0) return r < 0 ? r : DIFFSAL_OK;
-    }
+  const int rv = validate(d);
+  if (rv) return rv;
+  // fp32 pairs whose 96 x 96 tiles fill three quarters of the CUs: the LDS-DMA kernel's grouped form (same sums, another order).
+  // Measured at B = 4, 2 x (M = 648, K = 768, N = 1536), 224 tiles: 38.6 us against 47.3 on the paired 64 x 64 kernel; the
+  // 112 tiles of (K = 384, N = 768) lose, 25.3 against 18.3.
+  const long tiles = 2 * ((gemm_M(d) + 95) / 96) * ((d->Cout + 95) / 96);
+  const diffsal_conv_desc* dd[2] = {d, d};
+  if (tiles >= 192) {
+    GemmOperands g[2] = {{in0, w0, bias0}, {in1, w1, bias1}};
+    g[0].out = out0; g[1].out = out1;
+    const int r = launch_group(2, dd, g, static_cast<hipStream_t>(stream));
+    if (r != 0) return r < 0 ? r : DIFFSAL_OK;
   }
-  const PairExtra px{in1, w1, bias1, out1};
-  return conv_igemm_impl(d, in0, w0, bias0, nullptr, nullptr, nullptr, nullptr, out0, ws, ws_bytes, stream, &px);
+  GemmOperands o{in0, w0, bias0, nullptr, nullptr, nullptr, 0, nullptr, out0, ws, ws_bytes, false, in1, w1, bias1, out1};
+  return conv_igemm_impl(d, o, stream);
 }
+

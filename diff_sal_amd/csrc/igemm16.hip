@@ -15,7 +15,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
+#include "gemm_family.h"
 
 namespace diffsal {
 
@@ -618,83 +618,45 @@ static int launch16(Igemm16Args<T>& a, hipStream_t s) {
   return check_launch("diffsal_conv_igemm(16-bit split-K reduce)");
 }
 
-// conv16_halo.hip: LDS-halo kernel for 3x3 stride-1 "same" convolutions
-int conv16_halo_applies(const diffsal_conv_desc* d);
-int conv16_halo_pointers_ok(const diffsal_conv_desc* d, const float* bias, const float* scale, const float* shift,
-                            const float* rowvec, const void* residual, const void* out);
-int conv16_halo_launch(const diffsal_conv_desc* d, const void* in, const void* w, const float* bias, const float* scale,
-                       const float* shift, const float* rowvec, const void* residual, void* out, hipStream_t s);
-
-// conv16_dma.hip: the same convolutions (any padding) with an LDS-DMA halo patch, two workgroups per CU
-int conv16_dma_applies(const diffsal_conv_desc* d, const float* bias, const float* scale, const float* shift, const float* rowvec,
-                       const void* residual, const void* out);
-int conv16_dma_launch(const diffsal_conv_desc* d, const void* in, const void* w, const float* bias, const float* scale,
-                      const float* shift, const float* rowvec, const void* residual, void* out, hipStream_t s);
-
-static Plan16 plan_for(const diffsal_conv_desc* d) {
-  const long M = static_cast<long>(d->N) * d->Ho * d->Wo;
-  Plan16 pl = choose_plan16(M, d->Cout, d->KH * d->KW * d->Cin);
-  if (tune(TUNE_IGEMM16_CFG) >= 0) {  // tuning aid: force a tile shape (value % 8) and 2^(value / 8) K splits
-    const int v = tune(TUNE_IGEMM16_CFG);
-    pl.cfg = v % kNumCfgs16;
+// forced >= 0 (DIFFSAL_IGEMM16_CFG, a tuning aid): tile shape forced % 8 and 2^(forced / 8) K splits.  unsplit: see igemm.hip's offer().
+static Plan16 plan_for(const diffsal_conv_desc* d, int forced, bool unsplit) {
+  Plan16 pl = choose_plan16(gemm_M(d), d->Cout, gemm_K(d));
+  if (forced >= 0) {
+    pl.cfg = forced % kNumCfgs16;
     pl.splits = 1;
-    const int NST = (d->KH * d->KW * d->Cin / SUBK + 1) / 2;
-    for (int e = 0; e < v / kNumCfgs16 && e < 4; ++e)
+    const int NST = (gemm_K(d) / SUBK + 1) / 2;
+    for (int e = 0; e < forced / kNumCfgs16 && e < 4; ++e)
       if (NST / (pl.splits * 2) >= 4 && d->Cout % 4 == 0) pl.splits *= 2;
   }
-  if (conv16_halo_applies(d)) pl.splits = 1;   // halo-eligible shapes report no workspace; keep the pointer-alignment fallback valid
+  if (unsplit) pl.splits = 1;
   return pl;
 }
 
-size_t igemm16_ws_bytes(const diffsal_conv_desc* d) {
-  if (conv16_halo_applies(d)) return 0;
-  const long M = static_cast<long>(d->N) * d->Ho * d->Wo;
-  const Plan16 pl = plan_for(d);
-  return pl.splits > 1 ? static_cast<size_t>(pl.splits) * M * d->Cout * sizeof(float) : 0;
+size_t igemm16_ws_bytes(const diffsal_conv_desc* d, const Offer& f) {
+  const Plan16 pl = plan_for(d, f.cfg, f.flag);
+  return pl.splits > 1 ? static_cast<size_t>(pl.splits) * gemm_M(d) * d->Cout * sizeof(float) : 0;
 }
 
 template <typename T>
-static int run16(const diffsal_conv_desc* d, const void* in, const void* w, const float* bias, const float* scale,
-                 const float* shift, const float* rowvec, const void* residual, void* out, void* ws, size_t ws_bytes,
-                 hipStream_t s, const void* in2, const void* w2, const float* bias2, void* out2) {
-  const long M = static_cast<long>(d->N) * d->Ho * d->Wo;
+static int run16(const diffsal_conv_desc* d, const GemmOperands& o, const Offer& f, hipStream_t s) {
   Igemm16Args<T> a;
-  a.xcd_order = 0;
-  a.pair = in2 ? 1 : 0;
-  a.in2 = static_cast<const T*>(in2); a.w2 = static_cast<const T*>(w2); a.bias2 = bias2; a.out2 = static_cast<T*>(out2);
-  a.partial2 = nullptr;
-  a.in = static_cast<const T*>(in); a.w = static_cast<const T*>(w); a.bias = bias; a.scale = scale; a.shift = shift;
-  a.rowvec = rowvec; a.residual = static_cast<const T*>(residual); a.out = static_cast<T*>(out);
-  a.M = static_cast<int>(M);
-  a.K = d->KH * d->KW * d->Cin;
-  a.H = d->H; a.W = d->W; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
-  a.KW = d->KW; a.taps = d->KH * d->KW; a.stride_h = d->stride_h; a.stride_w = d->stride_w;
-  a.pad_t = d->pad_t; a.pad_l = d->pad_l; a.dil_h = d->dil_h; a.dil_w = d->dil_w; a.act = d->act;
-  a.rowvec_ld = d->rowvec_ld > 0 ? d->rowvec_ld : d->Cout;
-  a.linear = d->KH == 1 && d->KW == 1 && d->stride_h == 1 && d->stride_w == 1 && d->pad_t == 0 && d->pad_l == 0 && d->Ho == d->H && d->Wo == d->W;
-  a.in_bytes = static_cast<unsigned>(static_cast<long>(d->N) * d->H * d->W * d->Cin * 2);
-  a.w_bytes = static_cast<unsigned>(static_cast<long>(d->Cout) * a.K * 2);
-  const Plan16 pl = plan_for(d);
+  fill_tiled_args<T>(a, d, o);
+  const Plan16 pl = plan_for(d, f.cfg, f.flag);
   a.splits = pl.splits;
   const int n_stages = (a.K / SUBK + 1) / 2;
   a.st_per_split = (n_stages + pl.splits - 1) / pl.splits;
-  a.partial = nullptr;
+  auto al = [](const void* q, uintptr_t m) { return (reinterpret_cast<uintptr_t>(q) & m) == 0; };
   if (pl.splits > 1) {
-    const size_t one = static_cast<size_t>(pl.splits) * M * d->Cout * sizeof(float);
-    const size_t need = in2 ? 2 * one : one;
-    DS_REQUIRE(ws && ws_bytes >= need && aligned16(ws) && (reinterpret_cast<uintptr_t>(out) & 7u) == 0 &&
-                   (!residual || (reinterpret_cast<uintptr_t>(residual) & 7u) == 0),
-               DIFFSAL_E_ARG,
+    const size_t one = static_cast<size_t>(pl.splits) * a.M * d->Cout * sizeof(float);
+    const size_t need = a.pair ? 2 * one : one;
+    DS_REQUIRE(o.ws && o.ws_bytes >= need && aligned16(o.ws) && al(o.out, 7) && al(o.residual, 7), DIFFSAL_E_ARG,
                "conv_igemm(16-bit): split-K needs %zu bytes of 16-byte aligned workspace (diffsal_conv_igemm_ws_bytes), got %zu",
-               need, ws_bytes);
-    a.partial = static_cast<float*>(ws);
-    a.partial2 = in2 ? a.partial + one / sizeof(float) : nullptr;
+               need, o.ws_bytes);
+    a.partial = static_cast<float*>(o.ws);
+    a.partial2 = a.pair ? a.partial + one / sizeof(float) : nullptr;
   }
-  {
-    auto al = [](const void* q, uintptr_t m) { return (reinterpret_cast<uintptr_t>(q) & m) == 0; };
-    a.vec_epilogue = d->Cout % 4 == 0 && al(out, 7) && al(residual, 7) && al(bias, 15) && al(scale, 15) && al(shift, 15) &&
-                     al(rowvec, 15) && (!rowvec || a.rowvec_ld % 4 == 0) && al(a.partial, 15) && al(out2, 7) && al(bias2, 15);
-  }
+  a.vec_epilogue = d->Cout % 4 == 0 && al(o.out, 7) && al(o.residual, 7) && al(o.bias, 15) && al(o.scale, 15) && al(o.shift, 15) &&
+                   al(o.rowvec, 15) && (!o.rowvec || a.rowvec_ld % 4 == 0) && al(a.partial, 15) && al(o.out2, 7) && al(o.bias2, 15);
   a.persist_wgs = kCUs16 * kCfgs16[pl.cfg].occ;
   if (tune(TUNE_NO_PERSIST) == 1) a.persist_wgs = 0;
   switch (pl.cfg) {
@@ -709,16 +671,8 @@ static int run16(const diffsal_conv_desc* d, const void* in, const void* w, cons
   }
 }
 
-int igemm16_launch(const diffsal_conv_desc* d, const void* in, const void* w, const float* bias, const float* scale,
-                   const float* shift, const float* rowvec, const void* residual, void* out, void* ws, size_t ws_bytes,
-                   hipStream_t s, const void* in2, const void* w2, const float* bias2, void* out2) {
-  if (!in2 && conv16_dma_applies(d, bias, scale, shift, rowvec, residual, out))
-    return conv16_dma_launch(d, in, w, bias, scale, shift, rowvec, residual, out, s);
-  if (!in2 && conv16_halo_applies(d) && conv16_halo_pointers_ok(d, bias, scale, shift, rowvec, residual, out))
-    return conv16_halo_launch(d, in, w, bias, scale, shift, rowvec, residual, out, s);
-  if (d->dtype == DIFFSAL_BF16)
-    return run16<__bf16>(d, in, w, bias, scale, shift, rowvec, residual, out, ws, ws_bytes, s, in2, w2, bias2, out2);
-  return run16<_Float16>(d, in, w, bias, scale, shift, rowvec, residual, out, ws, ws_bytes, s, in2, w2, bias2, out2);
+int igemm16_launch(const diffsal_conv_desc* d, const GemmOperands& o, const Offer& f, hipStream_t s) {
+  return d->dtype == DIFFSAL_BF16 ? run16<__bf16>(d, o, f, s) : run16<_Float16>(d, o, f, s);
 }
 
 }  // namespace diffsal

@@ -7,7 +7,7 @@
 // LDS for the lifetime of the workgroup, each WAVEFRONT owns 32-row tiles of x on its own and streams them
 // through registers (double-buffered, one 96-wide K half ahead), so the steady state has NO barriers, no LDS
 // traffic for x and statically counted vmcnt waits (loads are always older than the stores of the previous tile).
-#include "common.h"
+#include "gemm_family.h"
 
 namespace diffsal {
 
@@ -149,17 +149,26 @@ static int launch_stream(const LinStreamArgs& a, hipStream_t s) {
   return check_launch("linear_stream");
 }
 
-// Returns 1 if the shape is handled here (and launches), 0 if the caller should use the tiled kernel, <0 on error.
-int try_linear_stream(const float* x, const float* w, const float* bias, const float* residual, float* out, long M,
-                      int K, int N, int act, hipStream_t s) {
-  if (M < 65536 || M >= (1L << 31) / 192) return 0;  // below ~256 tiles per CU-wave the tiled kernel wins
-  if (!((K == 96 || K == 192) && (N == 96 || N == 192)) || (K == 192 && N == 192)) return 0;
-  LinStreamArgs a{x, w, bias, residual, out, static_cast<int>(M), act};
+// A plain fp32 product with bias / activation / residual only; otherwise the tiled kernel runs.
+bool lin_stream_takes(const diffsal_conv_desc* d, const GemmOperands* o, Offer&) {
+  const long M = gemm_M(d);
+  const int K = d->Cin, N = d->Cout;
+  if (d->dtype != DIFFSAL_F32 || d->w_format != 0 || !is_linear(d) || d->act == DIFFSAL_ACT_GELU_GRAD) return false;
+  if (M < 65536 || M >= (1L << 31) / 192) return false;  // below ~256 tiles per CU-wave the tiled kernel wins
+  if (!((K == 96 || K == 192) && (N == 96 || N == 192)) || (K == 192 && N == 192)) return false;
+  return !o || (!o->scale && !o->rowvec && !o->in2 && aligned16(o->out) && aligned16(o->residual));
+}
+
+int lin_stream_launch(const diffsal_conv_desc* d, const GemmOperands& o, const Offer&, hipStream_t s) {
+  const int K = d->Cin, N = d->Cout;
+  LinStreamArgs a{static_cast<const float*>(o.in), static_cast<const float*>(o.w), o.bias, static_cast<const float*>(o.residual),
+                  static_cast<float*>(o.out), static_cast<int>(gemm_M(d)), d->act};
   int rc;
-  if (K == 96 && N == 96) rc = residual ? launch_stream<1, 3, true>(a, s) : launch_stream<1, 3, false>(a, s);
-  else if (K == 96 && N == 192) rc = residual ? launch_stream<1, 6, true>(a, s) : launch_stream<1, 6, false>(a, s);
-  else rc = residual ? launch_stream<2, 3, true>(a, s) : launch_stream<2, 3, false>(a, s);
-  return rc == DIFFSAL_OK ? 1 : rc;
+  if (K == 96 && N == 96) rc = o.residual ? launch_stream<1, 3, true>(a, s) : launch_stream<1, 3, false>(a, s);
+  else if (K == 96 && N == 192) rc = o.residual ? launch_stream<1, 6, true>(a, s) : launch_stream<1, 6, false>(a, s);
+  else rc = o.residual ? launch_stream<2, 3, true>(a, s) : launch_stream<2, 3, false>(a, s);
+  if (rc == DIFFSAL_OK) note_kernel("lin_stream_kernel [K=%d, N=%d]", K, N);
+  return rc;
 }
 
 // =================================================================================================================

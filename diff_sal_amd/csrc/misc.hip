@@ -1,6 +1,6 @@
 // Small / HBM-bound kernels of the SalUNet step: timestep-embedding MLP, conv_in, frame packing,
 // bilinear resizes, audio fusion, the pooled-KV attention core, the sigmoid head and the sampler axpy.
-#include "common.h"
+#include "gemm_family.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -1694,10 +1694,6 @@ static void attention_t(const T* q, const T* k, const T* v, T* o, int N, int Lq,
   else launch_attention_g<32, T>(G, q, k, v, o, N, Lq, Lk, C, heads, scale, s);
 }
 
-namespace diffsal {
-int try_attention16_mfma(const void* q, const void* k, const void* v, void* o, int N, int Lq, int Lk, int C, int heads, float scale,
-                         int dtype, hipStream_t s);
-}
 extern "C" int diffsal_attention(const void* q, const void* k, const void* v, void* o, int N, int Lq, int Lk,
                                  int C, int heads, float scale, int dtype, diffsal_stream_t stream) {
   DS_REQUIRE(q && k && v && o, DIFFSAL_E_ARG, "attention: null argument");

@@ -2,7 +2,7 @@
 // diffsal_conv_igemm / diffsal_layernorm): patch-embedding im2col, the depthwise-Conv3d poolings of q / k / v fused with
 // their LayerNorm, the max-pool of the skip path, the relative-position projections that feed diffsal_attention_general,
 // and the token -> NCTHW output transpose.  Tokens are [B, 1 + T*H*W, C] with the class token in row 0 (mvit.py:1097-1099).
-#include "common.h"
+#include "gemm_family.h"
 
 namespace diffsal {
 
@@ -595,12 +595,6 @@ __global__ __launch_bounds__(256) void relpos_bwd_tables_kernel(const float* __r
     }
   }
 }
-
-// mvit_pool.hip: head dimension 96 (8 lanes per query, 12 channels per lane)
-int relpos_project96(const float* q, const float* Rt, const float* Rh, const float* Rw, float* extra, long rows, int qt, int qh,
-                     int qw, int kt, int kh, int kw, int E, hipStream_t s);
-int relpos_bwd_q96(const float* dE, const float* Rt, const float* Rh, const float* Rw, float* dq, long rows, int qt, int qh,
-                   int qw, int kt, int kh, int kw, int accumulate, int E, hipStream_t s);
 
 static int rows_grid(long rows, int per_block) {
   long g = (rows + per_block - 1) / per_block;

@@ -9,7 +9,7 @@
 // an absent tap selects that row and reads the class token (a valid address), so a kernel plane is nine independent loads
 // with no branch.  Tap order and fmaf chains are those of pool3d_ln_kernel / pool3d_bwd_data_kernel: the convolution results
 // are bit-identical to the per-tensor kernels.
-#include "common.h"
+#include "gemm_family.h"
 
 namespace diffsal {
 

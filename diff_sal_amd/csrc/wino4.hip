@@ -20,12 +20,9 @@
 //
 // A dilated convolution is d*d undilated ones on the polyphase sub-grids: a tile is (image, py, px, ty, tx) and covers outputs
 // (py + d(4 ty + a), px + d(4 tx + b)), a, b in 0..3; its inputs are rows py + d(4 ty + i - 1), i in 0..5.
-#include "common.h"
+#include "gemm_family.h"
 
 namespace diffsal {
-
-int gemm_dma_batched(const float* a, const float* w, float* out, long M, int K, int N, int batch, long a_bs, long w_bs, long o_bs,
-                     hipStream_t s, const float* side_a, const float* side_w, float* side_out, long side_rows);
 
 struct Wino4Geom {
   int N, H, W, Cin, Cout, d;

@@ -9,6 +9,7 @@ There is no CPU / PyTorch fallback: a missing library or a non-GPU tensor raises
 from __future__ import annotations
 
 import contextlib
+import math
 import ctypes as C
 import threading
 from typing import List, Optional, Sequence, Tuple
@@ -649,6 +650,28 @@ def pack_conv_weight_diff(w: Tensor) -> Tensor:
     return _PackWeightFn.apply(w, _PACKS.get(w, _as_conv4(w.detach()), 0))
 
 
+def _conv_desc(x: Tensor, w: Tensor, kh: int = 1, kw: int = 1, stride=(1, 1), pad=(0, 0), dil=(1, 1), out_hw=None, act: int = ACT_NONE,
+               rowvec: Optional[Tensor] = None, split: bool = False, exact: bool = False):
+    """(ConvDesc, Ho, Wo) of a GEMM-family call on NHWC ``x`` ([1, 1, M, K]: a plain product) and packed ``w``; ``out_hw`` overrides the size
+    ``pad`` (top, left) implies.  fp32 storage follows ``set_gemm_precision`` (a pre-split weight: bf16x3) unless ``exact``."""
+    N, H, W, Cin = x.shape
+    Cout = w.shape[0]
+    assert w.shape[1] == kh * kw * Cin, (w.shape, kh, kw, Cin)
+    if out_hw is None:
+        Ho = (H + 2 * pad[0] - dil[0] * (kh - 1) - 1) // stride[0] + 1
+        Wo = (W + 2 * pad[1] - dil[1] * (kw - 1) - 1) // stride[1] + 1
+    else:
+        Ho, Wo = out_hw
+    dt = _dt(x)
+    prec = _lib.PREC_FP32 if exact or dt != _lib.F32 else GEMM_PRECISIONS["bf16x3" if split else get_gemm_precision()]
+    d = ConvDesc(N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], act,
+                 rowvec.shape[-1] if rowvec is not None else 0, 1 if split else 0, prec, dt)
+    if rowvec is not None:
+        assert rowvec.stride(-1) == 1 and rowvec.dtype == torch.float32 and rowvec.is_cuda
+        d.rowvec_ld = rowvec.stride(0)
+    return d, Ho, Wo
+
+
 def conv_igemm(x: Tensor, w_packed: Tensor, *, kh: int = 1, kw: int = 1, stride=(1, 1), pad=(0, 0), dil=(1, 1),
                out_hw: Optional[Sequence[int]] = None, bias: Optional[Tensor] = None, scale: Optional[Tensor] = None,
                shift: Optional[Tensor] = None, rowvec: Optional[Tensor] = None, residual: Optional[Tensor] = None,
@@ -666,25 +689,11 @@ def conv_igemm(x: Tensor, w_packed: Tensor, *, kh: int = 1, kw: int = 1, stride=
     lib = _lib.load()
     N, H, W, Cin = x.shape
     Cout = w_packed.shape[0]
-    assert w_packed.shape[1] == kh * kw * Cin, (w_packed.shape, kh, kw, Cin)
-    if out_hw is None:
-        Ho = (H + 2 * pad[0] - dil[0] * (kh - 1) - 1) // stride[0] + 1
-        Wo = (W + 2 * pad[1] - dil[1] * (kw - 1) - 1) // stride[1] + 1
-    else:
-        Ho, Wo = out_hw
-    dt = _dt(x)
+    d, Ho, Wo = _conv_desc(x, w_packed, kh, kw, stride, pad, dil, out_hw, act, rowvec, bool(getattr(w_packed, "_diffsal_split", False)))
+    dt = d.dtype
     if out is None:
         out = torch.empty((N, Ho, Wo, Cout), device=x.device, dtype=x.dtype)
-    split = bool(getattr(w_packed, "_diffsal_split", False))
-    prec = GEMM_PRECISIONS["bf16x3" if split else get_gemm_precision()] if dt == _lib.F32 else _lib.PREC_FP32
-    d = ConvDesc(N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], act,
-                 rowvec.shape[-1] if rowvec is not None else 0, 1 if split else 0, prec, dt)
-    if rowvec is not None:
-        assert rowvec.stride(-1) == 1 and rowvec.dtype == torch.float32 and rowvec.is_cuda
-        d.rowvec_ld = rowvec.stride(0)
-        rv = rowvec.data_ptr()
-    else:
-        rv = None
+    rv = rowvec.data_ptr() if rowvec is not None else None
     wino4 = None
     if isinstance(wino, WinoWeights):
         wino, wino4 = wino.f2, wino.f4
@@ -777,31 +786,21 @@ def conv_igemm_group(problems: Sequence[dict], tag: str = "gemm") -> List[Tensor
         raise RuntimeError("conv_igemm_group: 1..4 problems")
     if get_gemm_precision() != "fp32" or any(getattr(pr["w"], "_diffsal_split", False) for pr in problems):
         # split-precision mode (pre-split weights, per-call precision): the grouped entry point is exact-arithmetic only
-        return [conv_igemm(pr["x"], pr["w"], kh=pr.get("kh", 1), kw=pr.get("kw", 1), stride=pr.get("stride", (1, 1)),
-                           pad=pr.get("pad", (0, 0)), dil=pr.get("dil", (1, 1)), out_hw=pr.get("out_hw"), bias=pr.get("bias"),
-                           act=pr.get("act", ACT_NONE), out=pr.get("out"), tag=tag) for pr in problems]
-    descs, outs, keep = [], [], []
+        keys = ("kh", "kw", "stride", "pad", "dil", "out_hw", "bias", "act", "out")
+        return [conv_igemm(pr["x"], pr["w"], tag=tag, **{k: pr[k] for k in keys if k in pr}) for pr in problems]
+    descs, outs, keep, notes = [], [], [], []
     flops = nbytes = 0.0
     ws_bytes = 0
-    notes = []
     for pr in problems:
         x, w = pr["x"], pr["w"]
         kh, kw = pr.get("kh", 1), pr.get("kw", 1)
         stride, pad, dil = pr.get("stride", (1, 1)), pr.get("pad", (0, 0)), pr.get("dil", (1, 1))
         N, H, W, Cin = x.shape
         Cout = w.shape[0]
-        assert w.shape[1] == kh * kw * Cin, (w.shape, kh, kw, Cin)
-        if pr.get("out_hw") is None:
-            Ho = (H + 2 * pad[0] - dil[0] * (kh - 1) - 1) // stride[0] + 1
-            Wo = (W + 2 * pad[1] - dil[1] * (kw - 1) - 1) // stride[1] + 1
-        else:
-            Ho, Wo = pr["out_hw"]
-        dt = _dt(x)
+        d, Ho, Wo = _conv_desc(x, w, kh, kw, stride, pad, dil, pr.get("out_hw"), pr.get("act", ACT_NONE), exact=True)
         out = pr.get("out")
         if out is None:
             out = torch.empty((N, Ho, Wo, Cout), device=x.device, dtype=x.dtype)
-        d = ConvDesc(N, H, W, Cin, Ho, Wo, Cout, kh, kw, stride[0], stride[1], pad[0], pad[1], dil[0], dil[1], pr.get("act", ACT_NONE),
-                     0, 0, _lib.PREC_FP32, dt)
         descs.append(d)
         outs.append(out)
         ws_bytes = max(ws_bytes, lib.diffsal_conv_igemm_ws_bytes(C.byref(d)))
@@ -830,18 +829,16 @@ def linear(x: Tensor, w: Tensor, bias: Optional[Tensor] = None, *, act: int = AC
     """Token GEMM: x [..., K] @ w[N, K]^T (+bias, act, +residual) through the same MFMA kernel.  ``out_f32`` (16-bit storage
     only, no residual, K % 192 == 0): the result is fp32 -- the sums are not rounded to the storage type (``diffsal_linear_f32out``)."""
     lead = x.shape[:-1]
-    M = 1
-    for s in lead:
-        M *= s
+    M = math.prod(lead)
     if out_f32:
         if x.dtype == torch.float32 or residual is not None:
             raise RuntimeError("linear(out_f32=True): 16-bit storage in, no residual")
         lib = _lib.load()
         K, N = x.shape[-1], w.shape[0]
         dt = _dt(x)
-        d = ConvDesc(1, 1, M, K, 1, M, N, 1, 1, 1, 1, 0, 0, 1, 1, act, 0, 0, _lib.PREC_FP32, dt)
-        out = torch.empty((M, N), device=x.device, dtype=torch.float32)
         xc = x.reshape(M, K)
+        d, _, _ = _conv_desc(xc.view(1, 1, M, K), w, act=act)
+        out = torch.empty((M, N), device=x.device, dtype=torch.float32)
         with _prof(tag, 2.0 * M * N * K, _nb(xc, w, out), f"M={M} K={K} N={N} 1x1 (fp32 out)" if PROFILE is not None else "") as pr:
             _lib.check(lib.diffsal_linear_f32out(C.byref(d), _pa(xc, dt), _pa(w, dt), _p(bias), _p(out), _stream()), "linear_f32out")
             if PROFILE is not None:
@@ -858,9 +855,7 @@ def linear_group(xs: Sequence[Tensor], ws: Sequence[Tensor], biases: Sequence[Op
     probs, leads = [], []
     for x, w, b in zip(xs, ws, biases):
         lead = x.shape[:-1]
-        M = 1
-        for s_ in lead:
-            M *= s_
+        M = math.prod(lead)
         probs.append(dict(x=x.reshape(1, 1, M, x.shape[-1]), w=w, bias=b))
         leads.append(lead)
     outs = conv_igemm_group(probs, tag=tag)
@@ -874,18 +869,15 @@ def linear_pair(x0: Tensor, x1: Tensor, w0: Tensor, w1: Tensor, b0: Optional[Ten
     lib = _lib.load()
     if x0.shape != x1.shape or w0.shape != w1.shape or x0.dtype != x1.dtype or (b0 is None) != (b1 is None):
         raise RuntimeError("linear_pair: the two products must have one shape and storage type")
-    lead, K = x0.shape[:-1], x0.shape[-1]
-    M = 1
-    for s_ in lead:
-        M *= s_
-    N = w0.shape[0]
+    lead, K, N = x0.shape[:-1], x0.shape[-1], w0.shape[0]
+    M = math.prod(lead)
     dt = _dt(x0)
-    d = ConvDesc(1, 1, M, K, 1, M, N, 1, 1, 1, 1, 0, 0, 1, 1, ACT_NONE, 0, 0, _lib.PREC_FP32, dt)
+    x0c, x1c = x0.contiguous(), x1.contiguous()
+    d, _, _ = _conv_desc(x0c.view(1, 1, M, K), w0, exact=True)
     y0 = torch.empty((*lead, N), device=x0.device, dtype=x0.dtype)
     y1 = torch.empty_like(y0)
     ws_bytes = 2 * lib.diffsal_conv_igemm_ws_bytes(C.byref(d))
     ws = torch.empty((ws_bytes // 4,), device=x0.device, dtype=torch.float32) if ws_bytes else None
-    x0c, x1c = x0.contiguous(), x1.contiguous()
     with _prof(tag, 4.0 * M * K * N, _nb(x0c, x1c, w0, w1, y0, y1), f"2 x (M={M} K={K} N={N}) 1x1 pair") as pr:
         _lib.check(lib.diffsal_linear_pair(C.byref(d), _pa(x0c, dt), _pa(x1c, dt), _pa(w0, dt), _pa(w1, dt), _p(b0), _p(b1),
                                            y0.data_ptr(), y1.data_ptr(), _p(ws), ws_bytes, _stream()), "linear_pair")

@@ -187,8 +187,9 @@ enum {
 };
 size_t diffsal_workspace_bytes(int op, const diffsal_conv_desc* d /*host, may be NULL*/, const long* dims /*host*/, int n_dims);
 
-/* Bytes of scratch the call below needs for this shape (0 unless the planner picks split-K, which it does
- * when the M x Cout grid alone cannot fill the 256 CUs). */
+/* Bytes of scratch the call below can use for this descriptor: the largest workspace any candidate kernel could ask for, over all
+ * candidates that can take the descriptor under any pointer alignment (csrc/igemm.hip walks the same ordered list as the launch).
+ * 0 unless some candidate plans a split-K, which it does when the M x Cout grid alone cannot fill the 256 CUs. */
 size_t diffsal_conv_igemm_ws_bytes(const diffsal_conv_desc* d /*host*/);
 int diffsal_conv_igemm(const diffsal_conv_desc* d /*host*/, const void* in, const void* w,
                        const float* bias, const float* scale, const float* shift, const float* rowvec,

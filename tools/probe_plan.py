@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Print the fp32 planner's tile shape / split-K for every GEMM-family launch of one denoising step (DIFFSAL_PLAN_DEBUG=1)."""
+"""Print the kernel, tile shape and split-K that took every GEMM-family launch of one denoising step (DIFFSAL_PLAN_DEBUG=1)."""
 import os
 import subprocess
 import sys
