@@ -19,7 +19,7 @@ __global__ __launch_bounds__(256) void act_bwd_kernel(const float* __restrict__ 
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
       float d;
-      if (mode == 1) d = rv[c] > 0.f ? 1.f : 0.f;
+      if (mode == 1) d = rv[c] <= 0.f ? 0.f : 1.f;   // y = NaN passes dy on, as torch's threshold_backward does
       else if (mode == 2) d = gelu_erf_grad(rv[c]);
       else d = rv[c] * (1.0f - rv[c]);
       gv[c] *= d;
@@ -58,6 +58,14 @@ __global__ __launch_bounds__(256) void rowstats_kernel(const float* __restrict__
   const long rb = r0 + static_cast<long>(seg_rows) * chunk / chunks;
   const long re = r0 + static_cast<long>(seg_rows) * (chunk + 1) / chunks;
   float s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
+  // mode 0 sums d = x - pivot in fp32, pivot = the channel's value in the segment's first row (every workgroup can read it): sum d^2
+  // does not grow with the square of the channel's mean, which sum x^2 in fp32 paid for with mean^2 / var * 2^-24 of the
+  // variance.  (sum x, sum x^2) are restored in fp64 where the partials are written.
+  float pv[4] = {0, 0, 0, 0};
+  if (mode == 0 && rsub < rpp) {
+    const float4 p4 = ld4(x + r0 * C + c);
+    pv[0] = p4.x; pv[1] = p4.y; pv[2] = p4.z; pv[3] = p4.w;
+  }
   if (rsub < rpp) {
     float m4[4] = {0, 0, 0, 0}, r4[4] = {1, 1, 1, 1}, g4[4] = {1, 1, 1, 1}, b4[4] = {0, 0, 0, 0};
     if (mode != 0) {
@@ -74,7 +82,7 @@ __global__ __launch_bounds__(256) void rowstats_kernel(const float* __restrict__
       const float xa[4] = {xv.x, xv.y, xv.z, xv.w};
       if (mode == 0) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) { s1[k] += xa[k]; s2[k] += xa[k] * xa[k]; }
+        for (int k = 0; k < 4; ++k) { const float d = xa[k] - pv[k]; s1[k] += d; s2[k] += d * d; }
       } else {
         const float4 gv = ld4(dy + m * C + c);
         const float ga[4] = {gv.x, gv.y, gv.z, gv.w};
@@ -84,7 +92,7 @@ __global__ __launch_bounds__(256) void rowstats_kernel(const float* __restrict__
         for (int k = 0; k < 4; ++k) {
           const float xh = (xa[k] - m4[k]) * r4[k];
           float dz = ga[k];
-          if (mode == 1) dz = ya[k] > 0.f ? dz : 0.f;
+          if (mode == 1) dz = ya[k] <= 0.f ? 0.f : dz;   // y = NaN passes dy on, as in act_bwd_kernel
           else if (mode == 2) dz *= swish_grad(xh * g4[k] + b4[k]);
           s1[k] += dz;
           s2[k] += dz * xh;
@@ -103,7 +111,16 @@ __global__ __launch_bounds__(256) void rowstats_kernel(const float* __restrict__
   }
   __syncthreads();
   double* o = part + (static_cast<long>(seg) * chunks + chunk) * 2 * C;
-  for (int i = threadIdx.x; i < 2 * C; i += 256) o[i] = shd[i];
+  if (mode == 0) {
+    const double n = static_cast<double>(re - rb);
+    for (int i = threadIdx.x; i < C; i += 256) {
+      const double p = static_cast<double>(x[r0 * C + i]), sd = shd[i];
+      o[i] = sd + n * p;
+      o[C + i] = shd[C + i] + 2.0 * p * sd + n * p * p;
+    }
+  } else {
+    for (int i = threadIdx.x; i < 2 * C; i += 256) o[i] = shd[i];
+  }
 }
 
 // out[seg][j] = sum over chunks of part[seg][chunk][j] (fp64 in, fp64 or fp32 out).  Workgroup = (8 columns, segment),
@@ -266,7 +283,7 @@ __global__ __launch_bounds__(256) void norm_bwd_apply_kernel(const float* __rest
     for (int k = 0; k < 4; ++k) {
       const float xh = (xa[k] - ma[k]) * ra[k];
       float dz = ga[k];
-      if (mode == 1) dz = ya[k] > 0.f ? dz : 0.f;
+      if (mode == 1) dz = ya[k] <= 0.f ? 0.f : dz;   // y = NaN passes dy on, as in act_bwd_kernel
       else if (mode == 2) dz *= swish_grad(xh * gm[k] + bt[k]);
       o[k] = ka[k] * dz - kb[k] - kc[k] * xh;
     }

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(NW * 64, 1) void block16_kernel(Block16Args<T> p) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) s += v[u][r];
     s += lane_xor32(s);
-    mean = s * (1.0f / C);
+    mean = s / C;   // a true division: s (1 / C) misses the mean of a constant row by an ulp, which 1 / sqrt(eps) then multiplies
     float q = 0.f;
 #pragma unroll
     for (int u = 0; u < 3; ++u)

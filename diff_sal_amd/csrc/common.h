@@ -89,11 +89,19 @@ __device__ __forceinline__ float group_max(float v) {
   return group_reduce<WIDTH>(v, [](float a, float b) { return fmaxf(a, b); });
 }
 
-__device__ __forceinline__ float swishf(float x) { return x / (1.0f + expf(-x)); }
+// x sigmoid(x) with e = exp(-|x|) <= 1: x / (1 + e) for x >= 0 (the plain form, bit for bit), x e / (1 + e) below.  The plain form
+// x / (1 + exp(-x)) overflows its exponential below x = -88.7 and returns 0 where the value, down to 2e-37, is still a normal float.
+__device__ __forceinline__ float swishf(float x) {
+  const float e = expf(-fabsf(x));
+  return (x < 0.f ? x * e : x) / (1.0f + e);
+}
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 // x sigmoid(x) on the hardware transcendentals (v_exp_f32, v_rcp_f32: ~1 ulp each, five instructions instead of the ~30 of
 // libm's expf + an IEEE division): for kernels that evaluate it per LOADED element (the F(4x4) input transform reads every
 // pixel 2.25 times).  exp2 of a large positive argument overflows to +inf, rcp(+inf) = 0: the limit x -> -inf is exact.
+// Below x = -88.72 (exp2 argument above 128) that overflow comes early: the result is -0 where x sigmoid(x), between -2.6e-37 and
+// the smallest subnormal, is still representable -- an absolute error below 2.6e-37, which swishf's exp(-|x|) form avoids and this
+// one accepts (its consumer, the Winograd input transform, carries 1e-5 of the map's maximum).  NaN stays NaN; +inf gives +inf.
 __device__ __forceinline__ float swishf_fast(float x) {
   return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
 }
@@ -354,7 +362,7 @@ template <int N>
 __device__ __forceinline__ void epi_act(float (&v)[N], int act) {
   if (act == DIFFSAL_ACT_RELU) {
 #pragma unroll
-    for (int e = 0; e < N; ++e) v[e] = fmaxf(v[e], 0.f);
+    for (int e = 0; e < N; ++e) v[e] = v[e] < 0.f ? 0.f : v[e];   // not fmaxf: max(NaN, 0) is 0, and a NaN must stay one
   } else if (act == DIFFSAL_ACT_GELU_ERF) {
 #pragma unroll
     for (int e = 0; e < N; ++e) v[e] = gelu_erf(v[e]);

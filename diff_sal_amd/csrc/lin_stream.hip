@@ -244,7 +244,7 @@ __global__ __launch_bounds__(512) void mlp_block_kernel(MlpBlockArgs p) {
 #pragma unroll
     for (int i = 0; i < 12; ++i) s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     s += lane_xor32(s);
-    mean = s * (1.0f / C);
+    mean = s / C;   // a true division: s (1 / C) misses the mean of a constant row by an ulp, which 1 / sqrt(eps) then multiplies
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < 12; ++i) {

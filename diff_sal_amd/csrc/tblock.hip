@@ -228,7 +228,7 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 4 || C > 96) ? 1 : 2)) void blo
 #pragma unroll
       for (int i = 0; i < 3; ++i) s += (vv[i].x + vv[i].y) + (vv[i].z + vv[i].w);
       s = group_sum<G>(s);
-      const float mean = s * (1.0f / C);
+      const float mean = s / C;   // a true division: s (1 / C) misses the mean of a constant row by an ulp, which 1 / sqrt(eps) then multiplies
       float qq = 0.f;
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
@@ -305,7 +305,7 @@ __global__ __launch_bounds__(256, ((sizeof(T) == 4 || C > 96) ? 1 : 2)) void blo
 #pragma unroll
       for (int g = 0; g < NG; ++g) s += (qin[g].x + qin[g].y) + (qin[g].z + qin[g].w);
       s += lane_xor32(s);
-      const float mean = s * (1.0f / C);
+      const float mean = s / C;   // a true division: s (1 / C) misses the mean of a constant row by an ulp, which 1 / sqrt(eps) then multiplies
       float qq = 0.f;
 #pragma unroll
       for (int g = 0; g < NG; ++g) {
@@ -742,7 +742,7 @@ __global__ __launch_bounds__(256, (AHEAD ? 1 : 2)) void block_front_fold_kernel(
 #pragma unroll
       for (int i = 0; i < 3; ++i) s += (vv[i].x + vv[i].y) + (vv[i].z + vv[i].w);
       s = group_sum<G>(s);
-      const float mean = s * (1.0f / C);
+      const float mean = s / C;   // a true division: s (1 / C) misses the mean of a constant row by an ulp, which 1 / sqrt(eps) then multiplies
       float qq = 0.f;
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
@@ -833,7 +833,7 @@ __global__ __launch_bounds__(256, (AHEAD ? 1 : 2)) void block_front_fold_kernel(
 #pragma unroll
       for (int g = 0; g < NG; ++g) s += (qin[g].x + qin[g].y) + (qin[g].z + qin[g].w);
       s += lane_xor32(s);
-      const float mean = s * (1.0f / C);
+      const float mean = s / C;   // a true division: s (1 / C) misses the mean of a constant row by an ulp, which 1 / sqrt(eps) then multiplies
       float qq = 0.f;
 #pragma unroll
       for (int g = 0; g < NG; ++g) {

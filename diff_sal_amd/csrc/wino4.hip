@@ -294,12 +294,15 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(Wino4Out p) {
   const long pos_stride = static_cast<long>(g.n_tiles) * g.Cout;
   const long HW = static_cast<long>(g.HO) * g.WO;
   // STATS: every thread leaves the per-channel sums of its item in LDS; the workgroup's (image, group) sums are then added
-  // up in a FIXED order (tile, channel) -- no atomics, the statistics are bit-reproducible from run to run
-  __shared__ float2 st_sh[STATS ? 256 * VW : 1];
+  // up in a FIXED order (tile, channel) -- no atomics, the statistics are bit-reproducible from run to run.  A thread's fp32 sums
+  // run over d = v - pivot, the pivot being the first value the thread itself produced for the channel (nobody knows the
+  // output's mean before the convolution has run, but every thread knows its own first value): (sum d, sum d^2, pivot, count),
+  // turned back into (sum v, sum v^2) in fp64 below.  Sums of v^2 in fp32 lost mean^2 / var * 2^-24 of the variance.
+  __shared__ float4 st_sh[STATS ? 256 * VW : 1];
   int n_first = 0;
   if constexpr (STATS) {          // one pass per workgroup (grid = ceil(items / 256)): its statistics slot is blockIdx.x
 #pragma unroll
-    for (int e = 0; e < VW; ++e) st_sh[threadIdx.x * VW + e] = make_float2(0.f, 0.f);    // threads past the last item
+    for (int e = 0; e < VW; ++e) st_sh[threadIdx.x * VW + e] = make_float4(0.f, 0.f, 0.f, 0.f);    // threads past the last item
     n_first = static_cast<int>((static_cast<long>(blockIdx.x) * 256) / q4n) / p.tiles_per_img;
   }
   for (long it = static_cast<long>(blockIdx.x) * 256 + threadIdx.x; it < items; it += static_cast<long>(gridDim.x) * 256) {
@@ -320,9 +323,10 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(Wino4Out p) {
       for (int a = 0; a < 4; ++a) s[a][j] = y[a];
     }
     float bb[VW], ss[VW], hh[VW], rr[VW];
-    float ssum[VW], ssq[VW];
+    float ssum[VW], ssq[VW], piv[VW];
+    int cnt = 0;
 #pragma unroll
-    for (int e = 0; e < VW; ++e) { ssum[e] = 0.f; ssq[e] = 0.f; }
+    for (int e = 0; e < VW; ++e) { ssum[e] = 0.f; ssq[e] = 0.f; piv[e] = 0.f; }
 #pragma unroll
     for (int e = 0; e < VW; ++e) {
       bb[e] = p.bias ? p.bias[co + e] : 0.f;
@@ -357,7 +361,12 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(Wino4Out p) {
         }
         if constexpr (STATS) {
 #pragma unroll
-          for (int e = 0; e < VW; ++e) { ssum[e] += v[e]; ssq[e] = fmaf(v[e], v[e], ssq[e]); }
+          for (int e = 0; e < VW; ++e) {
+            if (cnt == 0) piv[e] = v[e];
+            const float dv = v[e] - piv[e];
+            ssum[e] += dv; ssq[e] = fmaf(dv, dv, ssq[e]);
+          }
+          ++cnt;
         }
         VT ov;
         if constexpr (VW == 4) ov = make_float4(v[0], v[1], v[2], v[3]);
@@ -368,7 +377,7 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(Wino4Out p) {
     }
     if constexpr (STATS) {
 #pragma unroll
-      for (int e = 0; e < VW; ++e) st_sh[threadIdx.x * VW + e] = make_float2(ssum[e], ssq[e]);
+      for (int e = 0; e < VW; ++e) st_sh[threadIdx.x * VW + e] = make_float4(ssum[e], ssq[e], piv[e], static_cast<float>(cnt));
     }
   }
   if constexpr (STATS) {
@@ -389,8 +398,9 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(Wino4Out p) {
         for (int c = grp * cpg; c < (grp + 1) * cpg; ++c) {
           const long item = static_cast<long>(t) * q4n + c / VW;
           if (item < base || item > last) continue;
-          const float2 v = st_sh[static_cast<int>(item - base) * VW + (c % VW)];
-          acc += static_cast<double>(which ? v.y : v.x);
+          const float4 v = st_sh[static_cast<int>(item - base) * VW + (c % VW)];
+          const double sd = v.x, pd = v.z, nd = v.w;
+          acc += which ? static_cast<double>(v.y) + 2.0 * pd * sd + nd * pd * pd : sd + nd * pd;
         }
       }
       p.stats[(static_cast<long>(blockIdx.x) * 2 + img) * (p.groups * 2) + r] = acc;
