@@ -30,7 +30,7 @@ def constants(prefix, names):
 _STRUCTS = dict.fromkeys(_H.structs)
 ConvDesc = _cdecl.structure("ConvDesc", _H.structs["diffsal_conv_desc"], _STRUCTS, "struct diffsal_conv_desc (include/diffsal.h).")
 Wino4Ext = _cdecl.structure("Wino4Ext", _H.structs["diffsal_wino4_ext"], _STRUCTS,
-                            "struct diffsal_wino4_ext (include/diffsal.h): optional extras of diffsal_conv_wino4_ex.")
+                            "struct diffsal_wino4_ext (include/diffsal.h): optional extras of diffsal_conv_wino4.")
 PackJob = _cdecl.structure("PackJob", _H.structs["diffsal_pack_job"], _STRUCTS, "struct diffsal_pack_job (include/diffsal.h).")
 _STRUCTS.update(diffsal_conv_desc=ConvDesc, diffsal_wino4_ext=Wino4Ext)
 
@@ -43,9 +43,9 @@ ABI_VERSION = K["DIFFSAL_ABI_VERSION"]
 SIGNATURES = {name: (_cdecl.ctype(res, _STRUCTS), [_cdecl.ctype(a, _STRUCTS) for a in args])
               for name, (res, args) in _H.prototypes.items()}
 
-(WS_GROUPNORM, WS_CONV_IGEMM, WS_CONV_WINO, WS_CONV_WINO4, WS_CONV_WINO4_STATS, WS_CONV_WGRAD, WS_WGRAD_SEGMENTED, WS_TAPSUM_BWD,
+(WS_GROUPNORM, WS_CONV_IGEMM, WS_CONV_WINO4, WS_CONV_WINO4_STATS, WS_CONV_WGRAD, WS_WGRAD_SEGMENTED, WS_TAPSUM_BWD,
  WS_SALIENCY_METRICS, WS_ATTENTION_TAIL, WS_ATTENTION_BWD_QTAIL, WS_ATTENTION_BWD_DS) = constants(
-    "WS_", "GROUPNORM CONV_IGEMM CONV_WINO CONV_WINO4 CONV_WINO4_STATS CONV_WGRAD WGRAD_SEGMENTED TAPSUM_BWD SALIENCY_METRICS "
+    "WS_", "GROUPNORM CONV_IGEMM CONV_WINO4 CONV_WINO4_STATS CONV_WGRAD WGRAD_SEGMENTED TAPSUM_BWD SALIENCY_METRICS "
            "ATTENTION_TAIL ATTENTION_BWD_QTAIL ATTENTION_BWD_DS")
 
 

@@ -42,7 +42,7 @@ constexpr int kWave = 64;  // CDNA wavefront
 #define DIFFSAL_TUNE_KEYS(X) \
   X(NO_PERSIST) X(NO_XCD_ORDER) X(NO_HALO) X(FORCE_HALO) X(IGEMM_CFG) X(IGEMM16_CFG) X(PLAN_DEBUG) \
   X(WGRAD_CFG) X(WGRAD_SPLITS) X(WGRAD_VERBOSE) X(NO_FUSED_BLOCK) X(NO_WINOGRAD) X(FORCE_WINOGRAD) X(GN_CHUNKS) \
-  X(GN_APPLY_WGS) X(GEMM_DMA) X(CONV_DMA) X(GROUP_GRID) X(GEMM_DMA16) X(WGRAD_DMA) X(NO_GN_SLAB) X(NO_WINOGRAD4) X(BATCH_TILE) \
+  X(GN_APPLY_WGS) X(GEMM_DMA) X(CONV_DMA) X(GROUP_GRID) X(GEMM_DMA16) X(WGRAD_DMA) X(NO_GN_SLAB) X(BATCH_TILE) \
   X(BATCH_XCD) X(NO_TAPSUM_ROWS) X(TAPSUM_ROWS_FORM) X(NO_ATTN_BWD_DS) X(NO_POOL_RUNS) X(NO_ATTN_SLOTS) X(NO_STREAM16) \
   X(CONV16_TILE) X(BLOCK16_WAVES) X(NO_ATTN16_MFMA) X(CONV16_HALF) X(FRONT_FOLD_WGS)
 #define DIFFSAL_TUNE_ENUM(name) TUNE_##name,

@@ -1210,7 +1210,6 @@ extern "C" size_t diffsal_workspace_bytes(int op, const diffsal_conv_desc* d, co
   switch (op) {
     case DIFFSAL_WS_GROUPNORM: return have && n_dims == 2 ? diffsal_groupnorm_ws_bytes(D(0), D(1)) : 0;
     case DIFFSAL_WS_CONV_IGEMM: return d ? diffsal_conv_igemm_ws_bytes(d) : 0;
-    case DIFFSAL_WS_CONV_WINO: return d ? diffsal_conv_wino_ws_bytes(d) : 0;
     case DIFFSAL_WS_CONV_WINO4: return d ? diffsal_conv_wino4_ws_bytes(d) : 0;
     case DIFFSAL_WS_CONV_WINO4_STATS: return d && have && n_dims == 1 ? diffsal_conv_wino4_stats_bytes(d, D(0)) : 0;
     case DIFFSAL_WS_CONV_WGRAD: return d ? diffsal_conv_wgrad_ws_bytes(d) : 0;

@@ -470,7 +470,7 @@ extern "C" int diffsal_up2_conv_commute(const void* c_ext, const void* tap_borde
 }
 
 /* Only the 3-pixel border ring of `out` is written (the pixels whose value needs the tap products): for a consumer that forms the
- * interior itself from c_ext -- diffsal_conv_wino4_ex with ext.up2_c (the interior never exists in memory). */
+ * interior itself from c_ext -- diffsal_conv_wino4 with ext.up2_c (the interior never exists in memory). */
 extern "C" int diffsal_up2_conv_commute_ring(const void* c_ext, const void* tap_border, const float* scale, const float* shift, void* out,
                                              int N, int h, int w, int C, int act, int dtype, diffsal_stream_t stream) {
   return up2_commute_impl(c_ext, tap_border, scale, shift, out, N, h, w, C, act, dtype, stream, true);

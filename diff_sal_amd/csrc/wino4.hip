@@ -1,20 +1,20 @@
 // 3x3 stride-1 "same" convolutions (dilation d = padding, d in {1, 2}) of the fp32 denoiser as Winograd F(4x4, 3x3): 36
 // multiplications per 4x4 output tile, input channel and output channel instead of 144 -- the matrix pipe does 4x fewer MFMAs
-// than the direct convolution (F(2x2, 3x3) of csrc/wino.hip: 2.25x fewer).  Same layers as that file: ResnetBlock.conv1 / conv2
-// (R/models/saliency_decoder/sal_unet.py:104-142) and UpEmbed's second convolution (common_block.py:196-216).
+// than the direct convolution.  The layers: ResnetBlock.conv1 / conv2 (R/models/saliency_decoder/sal_unet.py:104-142) and
+// UpEmbed's convolutions (common_block.py:196-216).
 //
 //   Y = A^T [ sum_ci (G g G^T) o (B^T x B) ] A        per tile; o = element-wise over the 36 positions xi = (i, j)
 //
 // interpolation points 0, +-1, +-2, infinity (Lavin & Gray 2015, the standard F(4x4, 3x3) matrices).  The transforms multiply by
-// up to 8 and cancel: results differ from the direct fp32 convolution by ~1e-5 of the output maximum (F(2x2): ~1e-6), two
-// orders inside the 1e-3 parity bar; DIFFSAL_NO_WINOGRAD4=1 keeps F(2x2) / the direct kernel.
+// up to 8 and cancel: results differ from the direct fp32 convolution by ~1e-5 of the output maximum, two orders inside the 1e-3
+// parity bar; DIFFSAL_NO_WINOGRAD=1 keeps the direct kernel.
 //
-// Unlike wino.hip this path is NOT fused: a 36-position accumulator set for a 64 x 64 tile block is 590 KB, more than the 512 KB
+// The path is NOT one fused kernel: a 36-position accumulator set for a 64 x 64 tile block is 590 KB, more than the 512 KB
 // of vector registers of a CU, and a block that fits (32 x 64) needs 12 TB/s of operand traffic to keep the matrix pipe busy.
 // The positions are 36 independent plain products [tiles, Cin] x [Cout, Cin]^T instead -- exactly what gemm_dma_kernel is built
 // for (96 x 96 tiles, LDS-DMA ring, 0.7-0.85 of the fp32 matrix peak) -- run as ONE batched launch between two streaming kernels:
 //
-//  1. wino4_input_kernel    V[xi][tile][ci] = B^T x B        2.25x the input bytes (F(2x2): 4x)
+//  1. wino4_input_kernel    V[xi][tile][ci] = B^T x B        2.25x the input bytes
 //  2. gemm_dma_kernel       M[xi][tile][co] = V[xi] U[xi]^T   batch of 36, K = Cin; U = G g G^T [36][Cout][Cin] from the host
 //  3. wino4_output_kernel   Y = A^T M A + the usual epilogue (bias, BN affine, per-image vector, activation, residual)
 //
@@ -515,14 +515,14 @@ extern "C" int diffsal_wino4_weight(const float* w, float* U, int Cout, int Cin,
   return check_launch("wino4_weight");
 }
 
-// 1 when diffsal_conv_wino4 accepts the descriptor AND the planner expects it to beat both the F(2x2) path and the direct kernel
+// 1 when diffsal_conv_wino4 accepts the descriptor AND the planner expects it to beat the direct kernel
 extern "C" int diffsal_conv_wino4_supported(const diffsal_conv_desc* d) {
-  if (!wino4_shape_ok(d) || tune(TUNE_NO_WINOGRAD) == 1 || tune(TUNE_NO_WINOGRAD4) == 1) return 0;
+  if (!wino4_shape_ok(d) || tune(TUNE_NO_WINOGRAD) == 1) return 0;
   if (tune(TUNE_FORCE_WINOGRAD) == 1) return 1;
   const Wino4Geom g = wino4_geom(d);
   // the transformed input and the position products (36 x tiles x (Cin + Cout) floats) are written and read back once: they have
   // to stay in the 256 MB Infinity Cache for the two streaming kernels to cost less than the products they save.  From 24 tiles
-  // (one 14 x 24 map): alone such a convolution was slower than F(2x2) (round 4: 0.71-0.83x, hence a bar of 96 tiles), but the
+  // (one 14 x 24 map): alone such a convolution was slower than the since-retired F(2x2) form (round 4: 0.71-0.83x), but the
   // fused ResnetBlock rides on this path (GroupNorm in the input transform, shortcut in the batched launch, statistics from the
   // output transform: three launches fewer per block) -- measured per step: B = 1 582 -> 602 steps/s, B = 2 877 -> 888
   return (wino4_v_bytes(g) + wino4_m_bytes(g) <= 400ul * 1000 * 1000 && d->Cout >= 96 && g.n_tiles >= 24) ? 1 : 0;
@@ -553,7 +553,7 @@ long wino4_out_wgs(const Wino4Geom& g) {
 }
 }  // namespace
 
-/* bytes of the `out_stats` buffer of diffsal_conv_wino4_ex for this convolution and group count; 0: not available for the shape */
+/* bytes of the `out_stats` buffer of diffsal_conv_wino4 for this convolution and group count; 0: not available for the shape */
 extern "C" size_t diffsal_conv_wino4_stats_bytes(const diffsal_conv_desc* d, int groups) {
   if (!wino4_shape_ok(d)) return 0;
   const Wino4Geom g = wino4_geom(d);
@@ -570,12 +570,12 @@ extern "C" int diffsal_conv_wino4_side_supported(const diffsal_conv_desc* d, lon
 
 // U: the transformed weight G g G^T as [36][Cout][Cin] fp32 (ops.pack_wino4_weight).  stages: bit 0 input transform, bit 1 the
 // position products, bit 2 output transform + epilogue -- the three launches of the path, callable one by one (same arguments,
-// same workspace) so that a profiler can bracket each: diffsal_conv_wino4 is stages = 7.  ext (may be NULL): GroupNorm affine +
+// same workspace) so that a profiler can bracket each: stages = 7 is the whole convolution.  ext (may be NULL): GroupNorm affine +
 // swish applied to the input as it is transformed, a plain product riding in the launch of the position products, statistics
 // of the result for the next GroupNorm (include/diffsal.h).
-extern "C" int diffsal_conv_wino4_ex(const diffsal_conv_desc* d, const float* x, const float* U, const float* bias, const float* scale,
-                                     const float* shift, const float* rowvec, const float* residual, float* out, void* ws,
-                                     size_t ws_bytes, const diffsal_wino4_ext* ext, int stages, diffsal_stream_t stream) {
+extern "C" int diffsal_conv_wino4(const diffsal_conv_desc* d, const float* x, const float* U, const float* bias, const float* scale,
+                                  const float* shift, const float* rowvec, const float* residual, float* out, void* ws,
+                                  size_t ws_bytes, const diffsal_wino4_ext* ext, int stages, diffsal_stream_t stream) {
   DS_REQUIRE(d && x && U && out && ws, DIFFSAL_E_ARG, "conv_wino4: null argument");
   DS_REQUIRE(wino4_shape_ok(d), DIFFSAL_E_SHAPE,
              "conv_wino4: fp32 3x3 stride-1 convolutions with padding = dilation in {1, 2} (or dilation 1, padding 2, output (H + 2) x "
@@ -659,7 +659,7 @@ extern "C" int diffsal_conv_wino4_ex(const diffsal_conv_desc* d, const float* x,
 }
 
 /* ab [N][2][Cout] (scale row, shift row) of GroupNorm(groups, eps; gamma, beta) over the OUTPUT of the convolution `d`, from the
- * workgroup sums diffsal_conv_wino4_ex left in `stats` (ext.out_stats, same d and groups). */
+ * workgroup sums diffsal_conv_wino4 left in `stats` (ext.out_stats, same d and groups). */
 extern "C" int diffsal_gn_affine_wino4(const diffsal_conv_desc* d, const double* stats, const float* gamma, const float* beta, int groups,
                                        float eps, float* ab, diffsal_stream_t stream) {
   DS_REQUIRE(d && stats && gamma && beta && ab, DIFFSAL_E_ARG, "gn_affine_wino4: null argument");
@@ -672,16 +672,4 @@ extern "C" int diffsal_gn_affine_wino4(const diffsal_conv_desc* d, const double*
   hipLaunchKernelGGL(wino4_gn_finalize_kernel, dim3(g.N, (groups + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), stats, gamma, beta, ab, g.Cout,
                      groups, static_cast<long>(tpi) * q4n, q4n, tpi, count, eps);
   return check_launch("gn_affine_wino4");
-}
-
-extern "C" int diffsal_conv_wino4_stages(const diffsal_conv_desc* d, const float* x, const float* U, const float* bias, const float* scale,
-                                         const float* shift, const float* rowvec, const float* residual, float* out, void* ws,
-                                         size_t ws_bytes, int stages, diffsal_stream_t stream) {
-  return diffsal_conv_wino4_ex(d, x, U, bias, scale, shift, rowvec, residual, out, ws, ws_bytes, nullptr, stages, stream);
-}
-
-extern "C" int diffsal_conv_wino4(const diffsal_conv_desc* d, const float* x, const float* U, const float* bias, const float* scale,
-                                  const float* shift, const float* rowvec, const float* residual, float* out, void* ws,
-                                  size_t ws_bytes, diffsal_stream_t stream) {
-  return diffsal_conv_wino4_ex(d, x, U, bias, scale, shift, rowvec, residual, out, ws, ws_bytes, nullptr, 7, stream);
 }

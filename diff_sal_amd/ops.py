@@ -277,9 +277,14 @@ def gn_affine(x: Tensor, gamma: Tensor, beta: Tensor, groups: int = 32, eps: flo
     return ab
 
 
-def _wino4_desc(x: Tensor, Cout: int, act: int, rowvec: Optional[Tensor], dil: int = 1):
+def _wino4_desc(x: Tensor, Cout: int, act: int, rowvec: Optional[Tensor], dil: int = 1, out_hw=None):
+    """Descriptor of a 3x3 stride-1 fp32 convolution with padding = dilation, or -- ``out_hw`` = (H + 2, W + 2), dilation 1 -- with
+    padding 2 on the grid extended by one pixel on every side."""
     N, H, W, Cin = x.shape
-    d = ConvDesc(N, H, W, Cin, H, W, Cout, 3, 3, 1, 1, dil, dil, dil, dil, act, rowvec.shape[-1] if rowvec is not None else 0, 0,
+    Ho, Wo = (H, W) if out_hw is None else out_hw
+    pad = dil if (Ho, Wo) == (H, W) else 2
+    assert (Ho, Wo) == (H, W) or ((Ho, Wo) == (H + 2, W + 2) and dil == 1), (x.shape, out_hw, dil)
+    d = ConvDesc(N, H, W, Cin, Ho, Wo, Cout, 3, 3, 1, 1, pad, pad, dil, dil, act, rowvec.shape[-1] if rowvec is not None else 0, 0,
                  _lib.PREC_FP32, _lib.F32)
     if rowvec is not None:
         assert rowvec.stride(-1) == 1 and rowvec.dtype == torch.float32 and rowvec.is_cuda
@@ -334,8 +339,9 @@ def wino4_supported(x: Tensor, Cout: int, dil: int = 1) -> bool:
 def conv3x3_wino4_ex(x: Tensor, wino4: Tensor, *, bias: Optional[Tensor] = None, scale: Optional[Tensor] = None,
                      shift: Optional[Tensor] = None, rowvec: Optional[Tensor] = None,
                      residual: Optional[Tensor] = None, act: int = ACT_NONE, gn_ab: Optional[Tensor] = None, gn_swish: bool = True,
-                     side=None, stats_groups: int = 0, dil: int = 1, up2=None, tag: str = "K4"):
-    """3x3 / padding 1 convolution of NHWC fp32 x on the F(4x4, 3x3) path with the ResnetBlock extras of ``diffsal_conv_wino4_ex``:
+                     side=None, stats_groups: int = 0, dil: int = 1, up2=None, out_hw=None, out: Optional[Tensor] = None,
+                     tag: str = "K4"):
+    """3x3 / padding 1 convolution of NHWC fp32 x on the F(4x4, 3x3) path with the ResnetBlock extras of ``diffsal_conv_wino4``:
     ``gn_ab`` [N,2,Cin] (``gn_affine``): the input is normalised (+ swish) as the input transform loads it; ``side = (a, w)``: the
     plain product a [N,H,W,K] x w [Cout, K]^T (the 1x1 shortcut, no bias) computed by the launch of the position products;
     ``stats_groups`` > 0: per-(image, group) sums of the result for the next GroupNorm.  Returns (out, side_out or None, stats or
@@ -343,12 +349,16 @@ def conv3x3_wino4_ex(x: Tensor, wino4: Tensor, *, bias: Optional[Tensor] = None,
 
     ``dil`` 1 or 2 (padding = dilation); ``scale`` / ``shift``: BatchNorm affine of the epilogue.  ``up2 = (c_ext, scale1, shift1,
     act1)``: x is the [N,H,W,Cin] buffer of which ``up2_conv3x3_d2(..., ring_only=True)`` wrote only the border ring; the input
-    transform forms the interior act1(BN1(interpolation of c_ext)) itself (dilation 2 only)."""
+    transform forms the interior act1(BN1(interpolation of c_ext)) itself (dilation 2 only).  ``out_hw`` = (H + 2, W + 2): the
+    extended grid (dilation 1, padding 2: the convolution evaluated one pixel beyond the map on every side, what
+    ``up2_conv3x3_d2`` interpolates).  ``out``: the tensor that receives the result."""
     lib = _lib.load()
     N, H, W, Cin = x.shape
     Cout = wino4.shape[1]
-    d = _wino4_desc(x, Cout, act, rowvec, dil)
-    out = torch.empty((N, H, W, Cout), device=x.device, dtype=torch.float32)
+    d = _wino4_desc(x, Cout, act, rowvec, dil, out_hw)
+    Ho, Wo = d.Ho, d.Wo
+    if out is None:
+        out = torch.empty((N, Ho, Wo, Cout), device=x.device, dtype=torch.float32)
     ws_bytes = lib.diffsal_conv_wino4_ws_bytes(C.byref(d))
     ws = torch.empty((ws_bytes // 4,), device=x.device, dtype=torch.float32)
     ext = _lib.Wino4Ext()
@@ -375,25 +385,28 @@ def conv3x3_wino4_ex(x: Tensor, wino4: Tensor, *, bias: Optional[Tensor] = None,
         ext.out_stats, ext.out_groups = stats.data_ptr(), stats_groups
     rv = rowvec.data_ptr() if rowvec is not None else None
     args = (C.byref(d), _p(x), _p(wino4), _p(bias), _p(scale), _p(shift), rv, _p(residual), _p(out), _p(ws), ws_bytes, C.byref(ext))
-    n_tiles = N * dil * dil * (((H + dil - 1) // dil + 3) // 4) * (((W + dil - 1) // dil + 3) // 4)
+    n_tiles = N * dil * dil * (((Ho + dil - 1) // dil + 3) // 4) * (((Wo + dil - 1) // dil + 3) // 4)
     if PROFILE is None:
-        _lib.check(lib.diffsal_conv_wino4_ex(*args, 7, _stream()), "conv_wino4_ex")
+        _lib.check(lib.diffsal_conv_wino4(*args, 7, _stream()), "conv_wino4")
     else:
-        note = f"M={N * H * W} K={9 * Cin} N={Cout} 3x3 winograd F(4x4,3x3)"
+        # profiling: the three launches bracketed one by one -- the transforms are streaming kernels (class <tag>-xf, HBM-bound),
+        # the products a launch of the GEMM kernel.  FLOPs actually issued: 36 products per 4x4 tile, input and output channel
+        # (the direct form has 144)
+        note = f"M={N * Ho * Wo} K={9 * Cin} N={Cout} 3x3 winograd F(4x4,3x3)"
         vb, mb = 36 * n_tiles * Cin * 4, 36 * n_tiles * Cout * 4
         nside = 0 if side is None else side[0].numel() // Cin
         xin = _nb(x) if up2 is None else _nb(up2[0])
         with _prof(tag + "-xf", 0.0, xin + vb, note + (": input transform (GroupNorm + swish on load)" if gn_ab is not None else
                                                         ": input transform (interpolation of the source-resolution convolution on load)" if up2 is not None
                                                         else ": input transform")) as pr:
-            _lib.check(lib.diffsal_conv_wino4_ex(*args, 1, _stream()), "conv_wino4_ex")
+            _lib.check(lib.diffsal_conv_wino4(*args, 1, _stream()), "conv_wino4")
             pr.kernel = "wino4_input_kernel"
         with _prof(tag, 2.0 * (n_tiles * 36 + nside) * Cin * Cout, vb + mb + _nb(wino4) + (0 if side is None else _nb(side[0], side_out)),
                    note + f": 36 x (M={n_tiles} K={Cin} N={Cout})" + (f" + 1x1 shortcut M={nside}" if nside else "")) as pr:
-            _lib.check(lib.diffsal_conv_wino4_ex(*args, 2, _stream()), "conv_wino4_ex")
+            _lib.check(lib.diffsal_conv_wino4(*args, 2, _stream()), "conv_wino4")
             pr.kernel = lib.diffsal_last_gemm_kernel().decode()
         with _prof(tag + "-xf", 0.0, mb + _nb(residual, out), note + ": output transform" + (" (+ GroupNorm sums)" if stats is not None else "")) as pr:
-            _lib.check(lib.diffsal_conv_wino4_ex(*args, 4, _stream()), "conv_wino4_ex")
+            _lib.check(lib.diffsal_conv_wino4(*args, 4, _stream()), "conv_wino4")
             pr.kernel = "wino4_output_kernel"
     if stats is not None:
         stats = (stats, d, stats_groups)
@@ -529,20 +542,6 @@ def pack_conv_weight(w: Tensor) -> Tensor:
     return _pack(_as_conv4(w.detach()), 0)
 
 
-def pack_wino_weight(w: Tensor) -> Tensor:
-    """[Cout, Cin, 3, 3] -> the Winograd F(2x2, 3x3) weight U = G w G^T in the blocked layout diffsal_conv_wino reads:
-    [Cin/8][ceil(Cout/64)][16][64][8] fp32 (output channels past Cout zero); include/diffsal.h."""
-    w = w.detach().float()
-    Cout, Cin = w.shape[:2]
-    assert tuple(w.shape[2:]) == (3, 3) and Cin % 8 == 0
-    G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], device=w.device)
-    U = torch.einsum("ia,ocab,jb->ijoc", G, w, G).reshape(16, Cout, Cin)
-    cb = (Cout + 63) // 64
-    if cb * 64 != Cout:
-        U = torch.cat([U, U.new_zeros(16, cb * 64 - Cout, Cin)], 1)
-    return U.view(16, cb, 64, Cin // 8, 8).permute(3, 1, 0, 2, 4).contiguous()
-
-
 def pack_wino4_weight(w: Tensor) -> Tensor:
     """[Cout, Cin, 3, 3] -> the Winograd F(4x4, 3x3) weight U = G w G^T as [36][Cout][Cin] fp32 (position-major: the B operand of
     the 36 position products of diffsal_conv_wino4); include/diffsal.h.  Computed in fp64, rounded once."""
@@ -565,15 +564,6 @@ def wino4_weight(w: Tensor, dgrad: bool = False) -> Tensor:
     U = torch.empty((36, Cin, Cout) if dgrad else (36, Cout, Cin), device=w.device, dtype=torch.float32)
     _lib.check(lib.diffsal_wino4_weight(_p(w.contiguous()), _p(U), Cout, Cin, int(dgrad), _stream()), "wino4_weight")
     return U
-
-
-class WinoWeights:
-    """The Winograd forms of one 3x3 weight: ``f2`` (pack_wino_weight) and ``f4`` (pack_wino4_weight); conv_igemm(wino=...) asks
-    the library per shape which of them -- if any -- to use."""
-
-    def __init__(self, w: Tensor, f2: bool = True, f4: bool = True):
-        self.f2 = pack_wino_weight(w) if f2 and w.shape[1] % 8 == 0 else None
-        self.f4 = pack_wino4_weight(w) if f4 and w.shape[1] % 96 == 0 else None
 
 
 @_classed("pack")
@@ -679,13 +669,12 @@ def conv_igemm(x: Tensor, w_packed: Tensor, *, kh: int = 1, kw: int = 1, stride=
     """Implicit-GEMM conv on NHWC x [N,H,W,Cin] with packed weight [Cout, kh*kw*Cin] -> [N,Ho,Wo,Cout].
 
     ``pad`` is (top, left); bottom/right padding is implied by ``out_hw`` (zero fill outside).  ``wino``: the same weight in
-    Winograd form (a ``pack_wino_weight`` tensor, or ``WinoWeights`` = F(2x2) and F(4x4) forms: F(4x4) where
-    ``diffsal_conv_wino4_supported`` says so, ~1e-5 relative rounding); used instead of the direct kernel when the library's planner expects a gain
-    (``diffsal_conv_wino_supported``: fp32 3x3 stride-1, padding = dilation in {1, 2}, Cin % 32 == 0, Cout >= 128, enough
-    workgroups and a transformed input of at most 160 MB -- both depend on the BATCH, so the same clip can take the Winograd
-    kernel in a large pass and the direct kernel alone: results then differ by the transforms' rounding, ~1e-6 relative for
-    F(2x2) and ~1e-5 for F(4x4); ``SalUNet.winograd = False`` / DIFFSAL_NO_WINOGRAD=1 pin the direct kernel for callers that need
-    chunked and whole-batch evaluation to agree bit for bit)."""
+    Winograd F(4x4, 3x3) form (a ``pack_wino4_weight`` tensor) or None; ``conv3x3_wino4_ex`` runs instead of the direct kernel when
+    the library's planner expects a gain (``diffsal_conv_wino4_supported``: fp32 3x3 stride-1, padding = dilation in {1, 2} or the
+    extended grid, Cin % 96 == 0, Cout >= 96, at least 24 tiles and at most 400 MB of transformed input and products -- both
+    depend on the BATCH, so the same clip can take the Winograd path in one pass and the direct kernel in another: results then
+    differ by the transforms' rounding, ~1e-5 of the output maximum; ``SalUNet.winograd = False`` / DIFFSAL_NO_WINOGRAD=1 pin the
+    direct kernel for callers that need chunked and whole-batch evaluation to agree bit for bit)."""
     lib = _lib.load()
     N, H, W, Cin = x.shape
     Cout = w_packed.shape[0]
@@ -694,46 +683,9 @@ def conv_igemm(x: Tensor, w_packed: Tensor, *, kh: int = 1, kw: int = 1, stride=
     if out is None:
         out = torch.empty((N, Ho, Wo, Cout), device=x.device, dtype=x.dtype)
     rv = rowvec.data_ptr() if rowvec is not None else None
-    wino4 = None
-    if isinstance(wino, WinoWeights):
-        wino, wino4 = wino.f2, wino.f4
-    if wino4 is not None and lib.diffsal_conv_wino4_supported(C.byref(d)):
-        ws_bytes = lib.diffsal_conv_wino4_ws_bytes(C.byref(d))
-        ws = torch.empty((ws_bytes // 4,), device=x.device, dtype=torch.float32)
-        dd = dil[0]
-        n_tiles = N * dd * dd * (((Ho + dd - 1) // dd + 3) // 4) * (((Wo + dd - 1) // dd + 3) // 4)
-        args = (C.byref(d), _p(x), _p(wino4), _p(bias), _p(scale), _p(shift), rv, _p(residual), _p(out), _p(ws), ws_bytes)
-        if PROFILE is None:
-            _lib.check(lib.diffsal_conv_wino4(*args, _stream()), "conv_wino4")
-            return out
-        # profiling: the three launches bracketed one by one -- the transforms are streaming kernels (class <tag>-xf, HBM-bound),
-        # the products a launch of the GEMM kernel.  FLOPs actually issued: 36 products per 4x4 tile, input and output channel
-        # (the direct form has 144)
-        note = f"M={N * Ho * Wo} K={kh * kw * Cin} N={Cout} {kh}x{kw} winograd F(4x4,3x3)"
-        vb, mb = 36 * n_tiles * Cin * 4, 36 * n_tiles * Cout * 4
-        with _prof(tag + "-xf", 0.0, _nb(x) + vb, note + ": input transform") as pr:
-            _lib.check(lib.diffsal_conv_wino4_stages(*args, 1, _stream()), "conv_wino4")
-            pr.kernel = "wino4_input_kernel"
-        with _prof(tag, 2.0 * n_tiles * 36 * Cin * Cout, vb + mb + _nb(wino4), note + f": 36 x (M={n_tiles} K={Cin} N={Cout})") as pr:
-            _lib.check(lib.diffsal_conv_wino4_stages(*args, 2, _stream()), "conv_wino4")
-            pr.kernel = lib.diffsal_last_gemm_kernel().decode()
-        with _prof(tag + "-xf", 0.0, mb + _nb(residual, out), note + ": output transform") as pr:
-            _lib.check(lib.diffsal_conv_wino4_stages(*args, 4, _stream()), "conv_wino4")
-            pr.kernel = "wino4_output_kernel"
-        return out
-    if wino is not None and lib.diffsal_conv_wino_supported(C.byref(d)):
-        ws_bytes = lib.diffsal_conv_wino_ws_bytes(C.byref(d))
-        ws = torch.empty((ws_bytes // 4,), device=x.device, dtype=torch.float32)
-        dd = dil[0]
-        n_tiles = N * dd * dd * (((H + dd - 1) // dd + 1) // 2) * (((W + dd - 1) // dd + 1) // 2)
-        # FLOPs actually issued: 16 products per 2x2 tile, input and output channel (the direct form has 36)
-        with _prof(tag, 2.0 * n_tiles * 16 * Cin * Cout, _nb(x, wino, residual, out) + 2 * 16 * n_tiles * Cin * 4,
-                   f"M={N * Ho * Wo} K={kh * kw * Cin} N={Cout} {kh}x{kw} winograd F(2x2,3x3)" if PROFILE is not None else "") as pr:
-            _lib.check(lib.diffsal_conv_wino(C.byref(d), _p(x), _p(wino), _p(bias), _p(scale), _p(shift), rv, _p(residual), _p(out),
-                                             _p(ws), ws_bytes, _stream()), "conv_wino")
-            if PROFILE is not None:
-                pr.kernel = lib.diffsal_last_gemm_kernel().decode()
-        return out
+    if wino is not None and lib.diffsal_conv_wino4_supported(C.byref(d)):
+        return conv3x3_wino4_ex(x, wino, bias=bias, scale=scale, shift=shift, rowvec=rowvec, residual=residual, act=act, dil=dil[0],
+                                out_hw=(Ho, Wo), out=out, tag=tag)[0]
     ws_bytes = lib.diffsal_conv_igemm_ws_bytes(C.byref(d))
     ws = torch.empty((ws_bytes // 4,), device=x.device, dtype=torch.float32) if ws_bytes else None
     with _prof(tag, 2.0 * N * Ho * Wo * Cout * kh * kw * Cin, _nb(x, w_packed, residual, out),

@@ -255,13 +255,13 @@ class SalUNet(nn.Module):
             return ops.cast(wp, self.compute_dtype)
         return ops.split_weight(wp) if self._precision() == "bf16x3" else wp
 
-    def _pack_wino(self, w: Tensor, f2: bool = True):
-        """Winograd forms of a 3x3 weight for the exact-fp32 path (F(2x2): ops.pack_wino_weight, F(4x4): ops.pack_wino4_weight), else
-        None: the library's planner then decides per shape which of them -- if any -- runs (ops.conv_igemm(wino=...)).  ``f2=False``:
-        only the F(4x4) form (a layer that can only use that one does not keep 16/9 of its weight bytes for nothing)."""
-        if self.compute_dtype != torch.float32 or self._precision() != "fp32" or not self.winograd:
-            return None
-        return ops.WinoWeights(w, f2=f2)
+    def _pack_wino(self, w: Tensor):
+        """The Winograd F(4x4, 3x3) form of a 3x3 weight (ops.pack_wino4_weight) for the exact-fp32 path where the kernel can take it
+        (Cin % 96 == 0), else None: the library's planner then decides per shape whether it runs (ops.conv_igemm(wino=...))."""
+        return ops.pack_wino4_weight(w) if self._winograd_fp32() and w.shape[1] % 96 == 0 else None
+
+    def _winograd_fp32(self) -> bool:
+        return self.compute_dtype == torch.float32 and self._precision() == "fp32" and self.winograd
 
     def _tap_weight(self, w: Tensor) -> Tensor:
         """Conv2d 3x3 weight -> the [9*Cout, Cin] matrix of its nine 1x1 tap mixings (row = tap * Cout + co), in the storage /
@@ -357,10 +357,12 @@ class SalUNet(nn.Module):
                 pe = st.patch_embed[0].proj
                 pk[f"s{i}.pe1.w"] = self._pack_conv(pe[1].weight)
                 pk[f"s{i}.pe1.tapw"] = self._tap_weight(pe[1].weight)
-                # UpEmbed's first convolution uses a Winograd form only at the source resolution (extended grid: F(4x4) only) and only
-                # where the source map is at least 12 x 12 (_forward_eval): stage i reads a map of img / 32 * 2^(i-1)
+                # UpEmbed's first convolution runs at the source resolution (extended grid, Winograd form where the weight has one)
+                # only on the exact-fp32 path and only where the source map is at least 12 x 12 (_up_embed): stage i reads a map of
+                # img / 32 * 2^(i-1)
                 hs, ws_ = (self.img_size[0] // 32) << (i - 1), (self.img_size[1] // 32) << (i - 1)
-                pk[f"s{i}.pe1.wino"] = self._pack_wino(pe[1].weight, f2=False) if min(hs, ws_) >= 12 else None
+                pk[f"s{i}.pe1.src"] = self._winograd_fp32() and min(hs, ws_) >= 12
+                pk[f"s{i}.pe1.wino"] = self._pack_wino(pe[1].weight) if pk[f"s{i}.pe1.src"] else None
                 pk[f"s{i}.pe1.scale"], pk[f"s{i}.pe1.shift"] = self._bn_affine(pe[2])
                 pk[f"s{i}.pe2.w"] = self._pack_conv(pe[4].weight)
                 pk[f"s{i}.pe2.wino"] = self._pack_wino(pe[4].weight)
@@ -418,7 +420,7 @@ class SalUNet(nn.Module):
             co = rb.conv1.out_channels
             w1, w2 = pk[f"res{i}.conv1.wino"], pk[f"res{i}.conv2.wino"]
             plan = None
-            if self.fuse_resblock and w1 is not None and w2 is not None and w1.f4 is not None and w2.f4 is not None:
+            if self.fuse_resblock and w1 is not None and w2 is not None:
                 plan = ops.resblock_wino4_plan(f, co, 32)
             if plan is not None:
                 # both convolutions on the F(4x4) path: GroupNorm + swish are applied as the input transforms load their tensors
@@ -427,7 +429,7 @@ class SalUNet(nn.Module):
                 ab1 = ops.gn_affine(f, rb.norm1.weight, rb.norm1.bias, 32, rb.norm1.eps)
                 has_nin = hasattr(rb, "nin_shortcut")
                 side = (f, pk[f"res{i}.nin.w"]) if has_nin and plan["side"] else None
-                h, sc, st = ops.conv3x3_wino4_ex(f, w1.f4, bias=rb.conv1.bias, rowvec=tproj[:, off:off + co], gn_ab=ab1, side=side,
+                h, sc, st = ops.conv3x3_wino4_ex(f, w1, bias=rb.conv1.bias, rowvec=tproj[:, off:off + co], gn_ab=ab1, side=side,
                                                  stats_groups=32 if plan["stats"] else 0)
                 off += co
                 if st is not None:
@@ -441,7 +443,7 @@ class SalUNet(nn.Module):
                     sc = ops.conv_igemm(f, pk[f"res{i}.nin.w"], bias=rb.nin_shortcut.bias, tag="K4")
                 else:
                     bias2 = pk[f"res{i}.bias2"]
-                f, _, _ = ops.conv3x3_wino4_ex(h, w2.f4, bias=bias2, residual=sc, gn_ab=ab2)
+                f, _, _ = ops.conv3x3_wino4_ex(h, w2, bias=bias2, residual=sc, gn_ab=ab2)
             else:
                 h = ops.groupnorm_swish(f, rb.norm1.weight, rb.norm1.bias, 32, rb.norm1.eps)
                 h = ops.conv_igemm(h, pk[f"res{i}.conv1.w"], kh=3, kw=3, pad=(1, 1), bias=rb.conv1.bias,
@@ -614,8 +616,8 @@ class SalUNet(nn.Module):
     # instead of 384 matrix instructions per wavefront and tile, no 96 x 96 weight in LDS, two workgroups per CU; same launch count.
     # Independent of fold_attn_proj.  Off: ops.block_front on the projected keys / values
     fold_front_proj = True
-    # fp32 3x3 stride-1 convolutions (ResnetBlock conv1 / conv2, UpEmbed's second convolution) as Winograd F(2x2, 3x3) where the
-    # library's planner expects a gain (csrc/wino.hip; ~1e-6 relative transform rounding).  Off: always the direct kernel
+    # fp32 3x3 stride-1 convolutions (ResnetBlock conv1 / conv2, UpEmbed's convolutions) as Winograd F(4x4, 3x3) where the
+    # library's planner expects a gain (csrc/wino4.hip; ~1e-5 of the output maximum in transform rounding).  Off: always the direct kernel
     winograd = True
     # ResnetBlocks whose two convolutions take the F(4x4) path: GroupNorm + swish folded into the input transforms, the 1x1
     # shortcut inside conv1's batched launch, norm2's statistics from conv1's output transform (ops.conv3x3_wino4_ex).  Off: the
@@ -714,7 +716,7 @@ class SalUNet(nn.Module):
         w1, wino1, tapw = pk[f"s{i}.pe1.w"], pk[f"s{i}.pe1.wino"], pk[f"s{i}.pe1.tapw"]
         s1, b1, s2, b2 = pk[f"s{i}.pe1.scale"], pk[f"s{i}.pe1.shift"], pk[f"s{i}.pe2.scale"], pk[f"s{i}.pe2.shift"]
         wino2 = pk[f"s{i}.pe2.wino"]
-        f32c = (self._use_tap_conv(taps, f"s{i}") and self.compute_dtype == torch.float32 and wino1 is not None
+        f32c = (self._use_tap_conv(taps, f"s{i}") and self.compute_dtype == torch.float32 and pk[f"s{i}.pe1.src"]
                 and h >= 12 and w >= 12)
         lowc = (self.compute_dtype != torch.float32 and self.up_commute16 and not (taps is not None and self.taps_reference_forms)
                 and h >= 2 and w >= 2)
@@ -723,7 +725,7 @@ class SalUNet(nn.Module):
             # the convolution at the source resolution + interpolation + border-ring corrections.  fp32: F(4x4) there, and only
             # where the interior is most of the map (stages 2 and 3 at 224 x 384; the alternative is the tap path).  16-bit
             # storage: every stage (the alternative is the convolution on the up-sampled map: 4x the products)
-            if (f32c and self.fuse_up_pe2 and wino2 is not None and wino2.f4 is not None
+            if (f32c and self.fuse_up_pe2 and wino2 is not None
                     and ops.wino4_supported(_ShapeOnly((Bn * T, 2 * h, 2 * w, C)), C, 2)):
                 # ... and UpEmbed's second convolution forms the interpolated interior itself as its input transform gathers
                 # it: only the border ring of the first convolution's output is ever written
@@ -739,7 +741,7 @@ class SalUNet(nn.Module):
             u = ops.conv_igemm(u, w1, kh=3, kw=3, pad=(d, d), dil=(d, d), scale=s1, shift=b1, act=ACT_RELU, tag="K12")
         res = None if skip is None else skip.view(Bn * T, 2 * h, 2 * w, C)
         if fuse_up is not None:
-            u, _, _ = ops.conv3x3_wino4_ex(u, wino2.f4, scale=s2, shift=b2, act=ACT_RELU, residual=res, dil=2, up2=fuse_up, tag="K12")
+            u, _, _ = ops.conv3x3_wino4_ex(u, wino2, scale=s2, shift=b2, act=ACT_RELU, residual=res, dil=2, up2=fuse_up, tag="K12")
         else:
             u = ops.conv_igemm(u, pk[f"s{i}.pe2.w"], kh=3, kw=3, pad=(d, d), dil=(d, d), scale=s2, shift=b2, act=ACT_RELU, tag="K12",
                                residual=res, wino=wino2)

@@ -45,10 +45,10 @@ enum { DIFFSAL_ACT_NONE = 0, DIFFSAL_ACT_RELU = 1, DIFFSAL_ACT_GELU_ERF = 2, DIF
 /* Bumped whenever a signature or struct in this header changes.  diffsal_version() returns the value the binary was compiled
  * with; a binding compares it with the header it reads, so a stale libdiffsal_hip.so is refused instead of being called with
  * other argument lists. */
-#define DIFFSAL_ABI_VERSION 52
+#define DIFFSAL_ABI_VERSION 53
 int diffsal_version(void);
 const char* diffsal_last_error(void);
-/* Name and tile plan of the kernel the last diffsal_conv_igemm / diffsal_linear_pair / diffsal_conv_wino call of THIS thread
+/* Name and tile plan of the kernel the last diffsal_conv_igemm / diffsal_linear_pair / diffsal_conv_wino4 call of THIS thread
  * launched (e.g. "gemm_dma_kernel<96x96,3 stages>", "igemm_linear_kernel<64x64>", "igemm_kernel<128x96> split-K 2"): lets a
  * profiler attribute HIP-event times to kernels without a tracing tool (bench.py's roofline.dominant_kernel).  Thread-local,
  * never NULL; not part of the reference's surface. */
@@ -174,7 +174,7 @@ enum { DIFFSAL_F32 = 0, DIFFSAL_BF16 = 1, DIFFSAL_F16 = 2 };
 enum {
   DIFFSAL_WS_GROUPNORM = 0,      /* dims = {B, groups}                 diffsal_groupnorm_ws_bytes (also diffsal_gn_affine) */
   DIFFSAL_WS_CONV_IGEMM = 1,     /* d                                  diffsal_conv_igemm_ws_bytes */
-  DIFFSAL_WS_CONV_WINO = 2,      /* d                                  diffsal_conv_wino_ws_bytes */
+                                 /* 2: retired (the F(2x2) Winograd path); answers 0 like any unknown operator */
   DIFFSAL_WS_CONV_WINO4 = 3,     /* d                                  diffsal_conv_wino4_ws_bytes */
   DIFFSAL_WS_CONV_WINO4_STATS = 4, /* d, dims = {groups}               diffsal_conv_wino4_stats_bytes */
   DIFFSAL_WS_CONV_WGRAD = 5,     /* d                                  diffsal_conv_wgrad_ws_bytes */
@@ -201,42 +201,28 @@ int diffsal_conv_igemm(const diffsal_conv_desc* d /*host*/, const void* in, cons
 int diffsal_linear_f32out(const diffsal_conv_desc* d /*host*/, const void* in, const void* w, const float* bias, float* out,
                           diffsal_stream_t stream);
 
-/* Winograd F(2x2, 3x3) form of the same operator for fp32 3x3 stride-1 convolutions with padding = dilation in {1, 2},
- * Cin % 32 == 0, Cout % 4 == 0 (ResnetBlock.conv1 / conv2, R/models/saliency_decoder/sal_unet.py:104-142; UpEmbed's second
- * convolution, common_block.py:196-216): 2.25x fewer multiplications; the result differs from the direct convolution by
- * transform rounding (~1e-6 relative).  `U` is the transformed weight G g G^T in blocked layout
- * [Cin/8][ceil(Cout/64)][16][64][8] (rows past Cout zero): the host mirror builds it with ops.pack_wino_weight.
- * diffsal_conv_wino_supported: 1 when the descriptor qualifies AND the planner expects a gain over diffsal_conv_igemm
- * (Cin, Cout >= 192; DIFFSAL_NO_WINOGRAD=1: never, DIFFSAL_FORCE_WINOGRAD=1: whenever the shape qualifies).
- * Epilogue and argument meaning as diffsal_conv_igemm; ws: diffsal_conv_wino_ws_bytes(d) bytes (transformed input + split slabs). */
-int diffsal_conv_wino_supported(const diffsal_conv_desc* d /*host*/);
-size_t diffsal_conv_wino_ws_bytes(const diffsal_conv_desc* d /*host*/);
-int diffsal_conv_wino(const diffsal_conv_desc* d /*host*/, const float* x, const float* U, const float* bias,
-                      const float* scale, const float* shift, const float* rowvec, const float* residual, float* out, void* ws,
-                      size_t ws_bytes, diffsal_stream_t stream);
-/* Winograd F(4x4, 3x3) form of the same operator (same layers and shape rules as diffsal_conv_wino, Cin % 96 == 0): 4x fewer
- * multiplications than the direct convolution; transform rounding ~1e-5 of the output maximum.  `U` is G g G^T as
+/* Winograd F(4x4, 3x3) form of the same operator for fp32 3x3 stride-1 convolutions with padding = dilation in {1, 2} (or dilation
+ * 1, padding 2, output (H + 2) x (W + 2): the extended grid diffsal_up2_conv_commute reads), Cin % 96 == 0, Cout % 4 == 0
+ * (ResnetBlock.conv1 / conv2, R/models/saliency_decoder/sal_unet.py:104-142; UpEmbed's convolutions, common_block.py:196-216):
+ * 4x fewer multiplications than the direct convolution; transform rounding ~1e-5 of the output maximum.  `U` is G g G^T as
  * [36][Cout][Cin] fp32 (ops.pack_wino4_weight).  Three launches: input transform, the 36 position products as one batched
  * plain product, output transform + epilogue.  ws: diffsal_conv_wino4_ws_bytes(d) = 36 * tiles * (Cin + Cout) floats.
- * diffsal_conv_wino4_supported: the shape qualifies and the planner expects a gain (DIFFSAL_NO_WINOGRAD4=1 /
- * DIFFSAL_NO_WINOGRAD=1: never, DIFFSAL_FORCE_WINOGRAD=1: whenever the shape qualifies). */
+ * diffsal_conv_wino4_supported: the shape qualifies and the planner expects a gain over diffsal_conv_igemm
+ * (DIFFSAL_NO_WINOGRAD=1: never, DIFFSAL_FORCE_WINOGRAD=1: whenever the shape qualifies). */
 int diffsal_conv_wino4_supported(const diffsal_conv_desc* d /*host*/);
 /* U = G g G^T on the device, fp32 (training: the weights change every step).  w [Cout][Cin][3][3]; dgrad = 0 -> U [36][Cout][Cin] (the forward
  * convolution); dgrad = 1 -> U [36][Cin][Cout] of the flipped kernel: the data gradient dX = conv(dY, .) of a stride-1, padding = dilation
  * convolution runs on the same F(4x4) path with it. */
 int diffsal_wino4_weight(const float* w, float* U, int Cout, int Cin, int dgrad, diffsal_stream_t stream);
 size_t diffsal_conv_wino4_ws_bytes(const diffsal_conv_desc* d /*host*/);
-int diffsal_conv_wino4(const diffsal_conv_desc* d /*host*/, const float* x, const float* U, const float* bias,
-                       const float* scale, const float* shift, const float* rowvec, const float* residual, float* out, void* ws,
-                       size_t ws_bytes, diffsal_stream_t stream);
-/* The same with the three launches selectable (stages: bit 0 input transform, bit 1 position products, bit 2 output transform +
- * epilogue; 7 = diffsal_conv_wino4): same arguments and workspace for every call of one convolution.  For profilers that bracket
- * operator launches (bench.py attributes the transforms to the HBM-bound classes and the products to the GEMM kernel). */
-int diffsal_conv_wino4_stages(const diffsal_conv_desc* d /*host*/, const float* x, const float* U, const float* bias,
-                              const float* scale, const float* shift, const float* rowvec, const float* residual, float* out,
-                              void* ws, size_t ws_bytes, int stages, diffsal_stream_t stream);
-/* Extensions of the F(4x4) path for a ResnetBlock (R/models/saliency_decoder/sal_unet.py:123-142: h = conv1(swish(norm1(x))) +
- * temb; out = nin_shortcut(x) + conv2(swish(norm2(h)))), all optional (zero / NULL = off):
+/* diffsal_conv_wino4: epilogue and argument meaning as diffsal_conv_igemm, plus
+ *   stages            which of the three launches run: bit 0 input transform, bit 1 position products, bit 2 output transform +
+ *                     epilogue; 7 = the whole convolution.  Same arguments and workspace for every call of one convolution: for
+ *                     profilers that bracket operator launches (bench.py attributes the transforms to the HBM-bound classes and
+ *                     the products to the GEMM kernel).
+ *   ext               (host, may be NULL) extras for a ResnetBlock (R/models/saliency_decoder/sal_unet.py:123-142: h =
+ *                     conv1(swish(norm1(x))) + temb; out = nin_shortcut(x) + conv2(swish(norm2(h)))) and for UpEmbed, all optional
+ *                     (zero / NULL = off):
  *   in_ab, in_swish   the input is read through y = a[n][c] x + b[n][c] (ab = [N][2][Cin]: scale row then shift row per image:
  *                     GroupNorm in affine form, diffsal_gn_affine / diffsal_gn_affine_wino4) and, if in_swish, y sigmoid(y), as the
  *                     input transform loads it: no normalised tensor in memory.  The zero padding applies to the normalised map.
@@ -245,14 +231,19 @@ int diffsal_conv_wino4_stages(const diffsal_conv_desc* d /*host*/, const float* 
  *                     shortcut; diffsal_conv_wino4_side_supported: side_rows must be a multiple of the tile count).
  *   out_stats, out_groups   the output transform leaves per-(image, group) sums / sums of squares of the RESULT in out_stats
  *                     (diffsal_conv_wino4_stats_bytes bytes; 0 = not available for the shape) for diffsal_gn_affine_wino4:
- *                     the GroupNorm that follows needs no statistics pass. */
+ *                     the GroupNorm that follows needs no statistics pass.
+ *   up2_c, up2_scale, up2_shift, up2_act   UpEmbed's second convolution (dilation 2) fed from the SOURCE-resolution result of the
+ *                     first one (R/.../common_block.py:196-216): up2_c = conv3x3(z) on the extended grid [N][H/2 + 2][W/2 + 2][Cin]
+ *                     (what diffsal_up2_conv_commute takes as c_ext); the input transform forms act(BN(interpolation of up2_c)) itself
+ *                     -- the arithmetic of diffsal_up2_conv_commute's interior -- and reads from `x` only the 3-pixel border ring, which
+ *                     diffsal_up2_conv_commute_ring must have written there.  dil = 2, H and W even, fp32; excludes in_ab. */
 typedef struct diffsal_wino4_ext {
   const float* in_ab;
   const float* side_a;
   const float* side_w;
   float* side_out;
   double* out_stats;
-  const float* up2_c;       /* see below */
+  const float* up2_c;
   const float* up2_scale;
   const float* up2_shift;
   long long side_rows;
@@ -261,20 +252,15 @@ typedef struct diffsal_wino4_ext {
   int up2_act;
   int reserved;
 } diffsal_wino4_ext;
-/*   up2_c, up2_scale, up2_shift, up2_act   UpEmbed's second convolution (dilation 2) fed from the SOURCE-resolution result of the
- *                     first one (R/.../common_block.py:196-216): up2_c = conv3x3(z) on the extended grid [N][H/2 + 2][W/2 + 2][Cin]
- *                     (what diffsal_up2_conv_commute takes as c_ext); the input transform forms act(BN(interpolation of up2_c)) itself
- *                     -- the arithmetic of diffsal_up2_conv_commute's interior -- and reads from `x` only the 3-pixel border ring, which
- *                     diffsal_up2_conv_commute_ring must have written there.  dil = 2, H and W even, fp32; excludes in_ab. */
 size_t diffsal_conv_wino4_stats_bytes(const diffsal_conv_desc* d /*host*/, int groups);
 int diffsal_conv_wino4_side_supported(const diffsal_conv_desc* d /*host*/, long side_rows);
-int diffsal_conv_wino4_ex(const diffsal_conv_desc* d /*host*/, const float* x, const float* U, const float* bias,
-                          const float* scale, const float* shift, const float* rowvec, const float* residual, float* out,
-                          void* ws, size_t ws_bytes, const diffsal_wino4_ext* ext /*host, may be NULL*/, int stages,
-                          diffsal_stream_t stream);
+int diffsal_conv_wino4(const diffsal_conv_desc* d /*host*/, const float* x, const float* U, const float* bias,
+                       const float* scale, const float* shift, const float* rowvec, const float* residual, float* out,
+                       void* ws, size_t ws_bytes, const diffsal_wino4_ext* ext /*host, may be NULL*/, int stages,
+                       diffsal_stream_t stream);
 /* GroupNorm(groups, eps; gamma, beta) in affine form: ab [B][2][C] with y = ab[b][0][c] x + ab[b][1][c] (statistics in fp64).
  * diffsal_gn_affine: from the tensor x [B, HW, C] (one statistics launch + a finishing launch; ws as diffsal_groupnorm_swish);
- * diffsal_gn_affine_wino4: from the sums a diffsal_conv_wino4_ex call left in ext.out_stats (same d, same groups).
+ * diffsal_gn_affine_wino4: from the sums a diffsal_conv_wino4 call left in ext.out_stats (same d, same groups).
  * R/models/saliency_decoder/sal_unet.py:41-44. */
 int diffsal_gn_affine(const void* x, const float* gamma, const float* beta, float* ab, int B, int HW, int C, int groups,
                       float eps, void* ws, size_t ws_bytes, int dtype, diffsal_stream_t stream);
@@ -293,7 +279,7 @@ int diffsal_border_gather(const void* z, void* zb, int N, int h, int w, int C, i
  * between); act: DIFFSAL_ACT_NONE or DIFFSAL_ACT_RELU. */
 int diffsal_up2_conv_commute(const void* c_ext, const void* tap_border, const float* scale, const float* shift, void* out,
                              int N, int h, int w, int C, int act, int dtype, diffsal_stream_t stream);
-/* the same, writing ONLY the 3-pixel border ring of `out` (for diffsal_conv_wino4_ex with ext.up2_c) */
+/* the same, writing ONLY the 3-pixel border ring of `out` (for diffsal_conv_wino4 with ext.up2_c) */
 int diffsal_up2_conv_commute_ring(const void* c_ext, const void* tap_border, const float* scale, const float* shift, void* out,
                              int N, int h, int w, int C, int act, int dtype, diffsal_stream_t stream);
 /* Up to four independent convolutions / plain products (own descriptor, operands and output; bias + activation epilogue

@@ -78,7 +78,7 @@ def test_reader_refuses_other_forms(text):
 
 def test_whole_header():
     d = _cdecl.parse(open(_build.HEADER).read())
-    assert len(d.prototypes) == len(declared_symbols()) >= 156
+    assert len(d.prototypes) == len(declared_symbols()) >= 153      # 158 before the F(2x2) path and two forwarding entry points left
     assert list(_lib.SIGNATURES) == list(d.prototypes)      # header order
     structs = dict.fromkeys(d.structs)
     for name, (res, args) in d.prototypes.items():
@@ -98,7 +98,7 @@ def test_pinned_signatures():
         "diffsal_attention_general_bwd": (c_i, [c_f] * 12 + [c_sz] + [c_f, c_sz] + [c_f] * 4 + [c_i] * 7 + [c_f] * 4
                                           + [c_fl, c_i, c_f]),
         "diffsal_dropout": (c_i, [c_f, c_f, c_sz, c_fl, C.c_uint64, c_f]),
-        "diffsal_conv_wino4_ex": (c_i, [desc] + [c_f] * 9 + [c_sz, ext, c_i, c_f]),
+        "diffsal_conv_wino4": (c_i, [desc] + [c_f] * 9 + [c_sz, ext, c_i, c_f]),
         "diffsal_resize_sum": (c_i, [c_f, c_f, c_f, c_i, c_f, c_i, c_i, c_i, c_i, c_i, c_f]),
         "diffsal_conv_igemm_group": (c_i, [c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_sz, c_f]),
         "diffsal_tapsum_bwd_ws_bytes": (C.c_long, [c_i, c_i, c_i, c_i]),
@@ -107,6 +107,11 @@ def test_pinned_signatures():
     }
     for name, sig in expected.items():
         assert _lib.SIGNATURES[name] == sig, name
+    # one F(4x4) entry point with 14 parameters; the F(2x2) path and the forwarding entry points are gone
+    assert len(_lib.SIGNATURES["diffsal_conv_wino4"][1]) == 14
+    for gone in ("diffsal_conv_wino", "diffsal_conv_wino_supported", "diffsal_conv_wino_ws_bytes", "diffsal_conv_wino4_ex",
+                 "diffsal_conv_wino4_stages"):
+        assert gone not in _lib.SIGNATURES, gone
 
 
 def test_struct_layouts():
@@ -131,14 +136,15 @@ def test_struct_layouts():
 
 
 def test_constants():
-    assert _lib.ABI_VERSION == 52
+    assert _lib.ABI_VERSION == 53
     assert (_lib.ACT_NONE, _lib.ACT_RELU, _lib.ACT_GELU, _lib.ACT_SIGMOID, _lib.ACT_GELU_GRAD) == (0, 1, 2, 3, 5)
     assert (ops.ACT_NONE, ops.ACT_RELU, ops.ACT_GELU, ops.ACT_SIGMOID, ops.ACT_GELU_GRAD) == (0, 1, 2, 3, 5)
     assert (_lib.PREC_FP32, _lib.PREC_BF16X3) == (0, 1)
     assert (_lib.F32, _lib.BF16, _lib.F16) == (0, 1, 2)
-    assert (_lib.WS_GROUPNORM, _lib.WS_CONV_IGEMM, _lib.WS_CONV_WINO, _lib.WS_CONV_WINO4, _lib.WS_CONV_WINO4_STATS,
+    assert (_lib.WS_GROUPNORM, _lib.WS_CONV_IGEMM, _lib.WS_CONV_WINO4, _lib.WS_CONV_WINO4_STATS,
             _lib.WS_CONV_WGRAD, _lib.WS_WGRAD_SEGMENTED, _lib.WS_TAPSUM_BWD, _lib.WS_SALIENCY_METRICS, _lib.WS_ATTENTION_TAIL,
-            _lib.WS_ATTENTION_BWD_QTAIL, _lib.WS_ATTENTION_BWD_DS) == tuple(range(12))
+            _lib.WS_ATTENTION_BWD_QTAIL, _lib.WS_ATTENTION_BWD_DS) == (0, 1) + tuple(range(3, 12))      # 2: retired with F(2x2)
+    assert "DIFFSAL_WS_CONV_WINO" not in _lib.K
     assert (ops.EVAL_JUDD, ops.EVAL_BORJI, ops.EVAL_SAUC, ops.EVAL_CC, ops.EVAL_NSS, ops.EVAL_SIM, ops.EVAL_JITTER) == (
         1, 2, 4, 8, 16, 32, 64)
     assert (ops.FILTER_BILINEAR, ops.FILTER_BICUBIC) == (0, 1)

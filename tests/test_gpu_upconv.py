@@ -44,7 +44,7 @@ def test_up2_conv_commute_matches_interpolate_then_conv(case, tuning):
     ref = ref.relu()
     wd = wt.to(DEV)
     tapw = wd.permute(2, 3, 0, 1).reshape(9 * Cout, Cin).contiguous()
-    got = ops.up2_conv3x3_d2(z.to(DEV), ops.pack_conv_weight(wd), ops.WinoWeights(wd), tapw, scale=scale.to(DEV), shift=shift.to(DEV),
+    got = ops.up2_conv3x3_d2(z.to(DEV), ops.pack_conv_weight(wd), ops.pack_wino4_weight(wd), tapw, scale=scale.to(DEV), shift=shift.to(DEV),
                              act=ops.ACT_RELU)
     err = (got.double().cpu() - ref).abs().max().item() / ref.abs().max().item()
     # the tap path it replaces
@@ -57,7 +57,7 @@ def test_up2_conv_commute_matches_interpolate_then_conv(case, tuning):
     # without Winograd (direct kernel on the extended grid): same construction, exact-fp32 products
     tuning.set("DIFFSAL_FORCE_WINOGRAD", None)
     tuning.set("DIFFSAL_NO_WINOGRAD", 1)
-    got_d = ops.up2_conv3x3_d2(z.to(DEV), ops.pack_conv_weight(wd), ops.WinoWeights(wd), tapw, scale=scale.to(DEV), shift=shift.to(DEV),
+    got_d = ops.up2_conv3x3_d2(z.to(DEV), ops.pack_conv_weight(wd), ops.pack_wino4_weight(wd), tapw, scale=scale.to(DEV), shift=shift.to(DEV),
                                act=ops.ACT_RELU)
     err_d = (got_d.double().cpu() - ref).abs().max().item() / ref.abs().max().item()
     print(f"commuted, direct kernel {err_d:.2e}")
@@ -125,7 +125,7 @@ def test_second_upembed_convolution_reads_the_source_resolution_result(case, tun
     w1d, w2d = w1.to(DEV), w2.to(DEV)
     tapw = w1d.permute(2, 3, 0, 1).reshape(9 * Cc, Cin).contiguous()
     kw1 = dict(scale=s1.to(DEV), shift=h1.to(DEV), act=ops.ACT_RELU)
-    ww1, u2 = ops.WinoWeights(w1d), ops.pack_wino4_weight(w2d)
+    ww1, u2 = ops.pack_wino4_weight(w1d), ops.pack_wino4_weight(w2d)
     # two-step form
     a1 = ops.up2_conv3x3_d2(z.to(DEV), ops.pack_conv_weight(w1d), ww1, tapw, **kw1)
     a2, _, _ = ops.conv3x3_wino4_ex(a1, u2, scale=s2.to(DEV), shift=h2.to(DEV), act=ops.ACT_RELU, residual=skip.to(DEV), dil=2, tag="K12")

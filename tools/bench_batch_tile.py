@@ -16,7 +16,7 @@ SHAPES = [("res1.conv2", 4, 28, 48, 384, 384, 1), ("res2.conv1", 4, 14, 24, 384,
 for name, N, H, W, Ci, Co, d in SHAPES:
     x = torch.randn(N, H, W, Ci, device="cuda")
     w = torch.randn(Co, Ci, 3, 3, device="cuda") * 0.05
-    wp, ww = ops.pack_conv_weight(w), ops.WinoWeights(w)
+    wp, ww = ops.pack_conv_weight(w), ops.pack_wino4_weight(w)
     kw = dict(kh=3, kw=3, pad=(d, d), dil=(d, d))
     _lib.set_tuning("DIFFSAL_FORCE_WINOGRAD", 1)
     res = {}

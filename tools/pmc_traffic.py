@@ -34,7 +34,7 @@ def main():
     build = sys.argv[5] if len(sys.argv) > 5 else "build n/a"
     launches = sys.argv[6] if len(sys.argv) > 6 else None
     fam = (["igemm_kernel", "igemm_linear_kernel", "splitk_reduce_kernel", "lin_stream_kernel", "mlp_block_kernel", "tapsum_kernel",
-            "block_front_kernel", "wino_gemm_kernel", "wino_input_kernel", "wino_reduce_kernel", "gemm_dma_kernel",
+            "block_front_kernel", "gemm_dma_kernel",
             "gemm_dma_reduce_kernel"] if prec == "fp32" else
            ["igemm16_kernel", "igemm16_linear_kernel", "splitk16_reduce_kernel", "conv16_halo_kernel", "conv16_dma_kernel", "gemm16_dma2_kernel", "block16_kernel",
             "block_front_kernel", "gemm_dma_kernel", "gemm_dma_reduce_kernel"])

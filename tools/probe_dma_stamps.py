@@ -17,7 +17,7 @@ if mode == "wino":
     N, H, W, Ci, Co, d = map(int, sys.argv[2:8]) if len(sys.argv) > 7 else (36, 56, 96, 96, 96, 2)
     x = torch.randn(N, H, W, Ci, device="cuda")
     w = torch.randn(Co, Ci, 3, 3, device="cuda") * 0.05
-    wp, ww = ops.pack_conv_weight(w), ops.WinoWeights(w)
+    wp, ww = ops.pack_conv_weight(w), ops.pack_wino4_weight(w)
     _lib.set_tuning("DIFFSAL_FORCE_WINOGRAD", 1)
     run = lambda: ops.conv_igemm(x, wp, wino=ww, kh=3, kw=3, pad=(d, d), dil=(d, d))
 else:
