@@ -16,16 +16,27 @@ in numpy:
 ``examples_resize``.  The centring and zero padding are index arithmetic on the video's waveform; no padded excerpt exists in
 memory.
 
-**16 kHz input only.**  The reference resamples other rates with ``resampy`` first; that is not built, and a ``sample_rate`` other
-than 16000 raises: resample when the file is loaded.  ``audio_type`` "spec" and "ori" of the reference are not built either.
+**Input at another rate** (the reference's audio-visual sets: ``max_audio_Fs = 22050``).  The reference reads a file at its native
+rate, tabulates ``starts`` / ``ends`` at that rate and hands the padded buffer of ``window`` native-rate samples to
+``waveform_to_examples(audioexcer, sample_rate=Fs)``, which calls ``resampy.resample(data, Fs, 16000)`` on it
+(R/datasets/torchvggish/vggish_input.py:52-53): per clip, in float64, after the padding.  ``resample="kaiser_best"`` (resampy's
+default filter; or ``"kaiser_fast"``, or a ``(half_window, num_table)`` pair) does that on the device: ``resample_excerpts`` is one
+more launch in front of ``logmel``, resampy 0.4.2's interpolation loop with every float64 operation in the library's order, so its
+output equals a NumPy restatement of the loop bit for bit (include/diffsal.h states it; tests/_audio_resample_ref.py restates it).
+Only the samples the frames need are resampled; ``num_frames`` / ``num_examples`` / ``frames_needed`` are taken of
+``resampled_length(window, sample_rate)``: 25600 samples, 158 frames and exactly nine examples for the 35280-sample window at
+22050 Hz.  Resampling the whole file once when it is loaded is *not* the same computation: the excerpt table lives at the native
+rate, the filter sees the zero padding at the excerpt's edges, and the length is ``int(window * 16000 / Fs)``.  Without
+``resample=`` a ``sample_rate`` other than 16000 raises, as it always did.  ``audio_type`` "spec" and "ori" of the reference are
+not built.
 
 Each of ``starts`` / ``ends`` / ``wav_len`` / ``video`` / ``exists`` given on the host (a sequence, a numpy array, a CPU tensor)
 is range-checked here and uploaded; a clip longer than the window raises, as the reference's broadcast does, whenever ``starts``,
 ``ends``, ``wav_len`` and ``video`` are all on the host (or absent).  An argument given as a GPU tensor is used as it is, with no
 host copy and no synchronisation; with all of them on the GPU the call can be captured in a graph.  What could not be checked the
 kernel makes safe: it clamps the way numpy slicing does and centre-crops a clip longer than the window.  The first call on a
-device uploads the kernel's tables from host memory, which a capture does not allow: call once (or ``warm(device)``) before
-capturing.  The resize is the plain bilinear form, also for ``h`` or ``w`` below 64: a torchvision whose tensor ``Resize``
+device uploads the kernel's tables from host memory, which a capture does not allow: call once (or ``warm(device)``; with
+``sample_rate=`` and ``resample=`` for the resampling tables, which are kept per device, rates and filter) before capturing.  The resize is the plain bilinear form, also for ``h`` or ``w`` below 64: a torchvision whose tensor ``Resize``
 defaults to ``antialias=True`` gives other values when it shrinks an axis (for an upscale the two forms are the same filter).
 GPU only: a CPU ``wav`` raises.
 """
@@ -165,20 +176,103 @@ def device_tables() -> np.ndarray:
     return t
 
 
+# resampy 0.4.2's stored filters as sinc_window(num_zeros, precision, rolloff) with a Kaiser window of the given beta designs them
+RESAMPLE_FILTERS = {"kaiser_best": (64, 9, 0.9475937167399596, 14.769656459379492),
+                    "kaiser_fast": (16, 9, 0.85, 8.555504641634386)}
+
+
+def resample_filter(name: str = "kaiser_best") -> Tuple[np.ndarray, int]:
+    """``(half_window, num_table)`` of resampy's ``kaiser_best`` / ``kaiser_fast``: the right half of a Kaiser-windowed sinc,
+    float64, ``num_table = 2 ** precision`` entries per zero crossing and ``num_zeros * num_table + 1`` entries in all
+    (resampy.filters.sinc_window, in its operation order)."""
+    try:
+        num_zeros, precision, rolloff, beta = RESAMPLE_FILTERS[name]
+    except (KeyError, TypeError):
+        raise ValueError(f"audio_input: resample filter {name!r} is not one of {sorted(RESAMPLE_FILTERS)}") from None
+    num_table = 2 ** precision
+    n = num_table * num_zeros
+    sinc_win = rolloff * np.sinc(rolloff * np.linspace(0, num_zeros, num=n + 1, endpoint=True))
+    taper = np.kaiser(2 * n + 1, beta)[n:]
+    return taper * sinc_win, num_table
+
+
+def resampled_length(n: int, sr_orig: int, sr_new: int = SAMPLE_RATE) -> int:
+    """Samples ``resampy.resample`` returns for ``n`` input samples: ``int(n * sr_new / sr_orig)``."""
+    return int(int(n) * int(sr_new) / int(sr_orig))
+
+
+def resample_table(half_window: np.ndarray, num_table: int, sr_orig: int, sr_new: int = SAMPLE_RATE) -> np.ndarray:
+    """The float64 ``[nwin, 2]`` table ``diffsal_resample_excerpts`` reads: ``(win[j], delta[j])`` with ``win`` the half window,
+    multiplied by ``sr_new / sr_orig`` when that is below one, and ``delta = diff(win)`` with a final zero -- the values
+    resampy.core.resample forms, so a tap is one 16-byte load."""
+    win = np.array(half_window, dtype=np.float64).reshape(-1)
+    ratio = float(sr_new) / sr_orig
+    if ratio < 1:
+        win = ratio * win
+    delta = np.diff(win, append=win[-1])
+    return np.ascontiguousarray(np.stack([win, delta], axis=1))
+
+
 _TABLES = {}
+_UNIT = {}
+
+
+def _dev_key(device: torch.device):
+    return (device.type, device.index if device.index is not None else torch.cuda.current_device())
 
 
 def _tables(device: torch.device) -> Tensor:
-    key = (device.type, device.index if device.index is not None else torch.cuda.current_device())
+    key = _dev_key(device)
     t = _TABLES.get(key)
     if t is None:
         t = _TABLES[key] = torch.from_numpy(device_tables()).to(device)
     return t
 
 
-def warm(device) -> None:
-    """Build and upload the kernel's tables for ``device`` now (otherwise the first call does it)."""
-    _tables(torch.device(device))
+def _resample_tables(device: torch.device, sr_orig: int, sr_new: int, filt) -> Tuple[Tensor, int]:
+    """``([nwin, 2] float64 on the device, num_table)``; a named filter's table is kept per (device, rates, filter), a caller's own
+    ``(half_window, num_table)`` pair is built and uploaded on every call."""
+    if isinstance(filt, str):
+        key = _dev_key(device) + (int(sr_orig), int(sr_new), filt)
+        hit = _TABLES.get(key)
+        if hit is None:
+            hw, num_table = resample_filter(filt)
+            hit = _TABLES[key] = (torch.from_numpy(resample_table(hw, num_table, sr_orig, sr_new)).to(device), num_table)
+        return hit
+    try:
+        hw, num_table = filt
+        hw = np.asarray(hw, dtype=np.float64)
+        num_table = int(num_table)
+    except (TypeError, ValueError):
+        raise ValueError(f"audio_input: filter must be one of {sorted(RESAMPLE_FILTERS)} or a (half_window, num_table) pair") from None
+    if hw.ndim != 1 or hw.size < 2 or num_table < 1:
+        raise ValueError(f"audio_input: a filter pair is (half_window [nwin >= 2], num_table >= 1), got {hw.shape}, {num_table}")
+    return torch.from_numpy(resample_table(hw, num_table, sr_orig, sr_new)).to(device), num_table
+
+
+def _unit_clips(device: torch.device, B: int) -> Tuple[Tensor, Tensor, Tensor]:
+    """``starts`` (zeros), ``ends`` (2^31 - 2: clamped to the row's length) and ``video`` (0, 1, ..) for ``B`` clips that are each
+    one whole row of a [B, n] wave: what ``logmel`` is given after ``resample_excerpts``.  One int32 [3, N] tensor per device."""
+    key = _dev_key(device)
+    t = _UNIT.get(key)
+    if t is None or t.shape[1] < B:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"audio_input: the index table for {B} resampled clips is not on the device yet and a capture cannot "
+                               f"upload it: call warm(device, sample_rate=..., resample=..., clips={B}) first")
+        N = max(1024, 1 << (int(B) - 1).bit_length())
+        host = np.stack([np.zeros(N, dtype=np.int32), np.full(N, 2 ** 31 - 2, dtype=np.int32), np.arange(N, dtype=np.int32)])
+        t = _UNIT[key] = torch.from_numpy(host).to(device)
+    return t[0, :B], t[1, :B], t[2, :B]
+
+
+def warm(device, *, sample_rate: Optional[int] = None, resample=None, sr_new: int = SAMPLE_RATE, clips: int = 1) -> None:
+    """Build and upload the kernel's tables for ``device`` now (otherwise the first call does it); with ``sample_rate`` and
+    ``resample`` also the resampling table of those rates and that filter and the index table for ``clips`` clips."""
+    device = torch.device(device)
+    _tables(device)
+    if resample is not None and sample_rate is not None and int(sample_rate) != sr_new:
+        _resample_tables(device, _rate(sample_rate), sr_new, resample)
+        _unit_clips(device, clips)
 
 
 _WAV_DTYPES = dict(zip((torch.int16, torch.float32, torch.float64), _lib.constants("WAV_", "I16 F32 F64")))
@@ -261,52 +355,107 @@ def _clip_args(wav: Tensor, starts, ends, window, wav_len, video, exists):
             up(video, vi, torch.int32, "video", B), up(exists, ex, torch.uint8, "exists", B))
 
 
-def _check_rate(sample_rate):
-    if int(sample_rate) != SAMPLE_RATE or sample_rate != int(sample_rate):
-        raise ValueError(f"audio_input: sample_rate {sample_rate} is not {SAMPLE_RATE}; resampling is not part of this front end: "
-                         "resample on load")
+def _rate(sample_rate) -> int:
+    if sample_rate != int(sample_rate) or int(sample_rate) < 1:
+        raise ValueError(f"audio_input: sample_rate {sample_rate} is not a positive integer")
+    return int(sample_rate)
+
+
+def _check_rate(sample_rate, resample=None) -> bool:
+    """True if the call resamples: ``resample`` given and a rate other than 16000.  Another rate without ``resample`` raises."""
+    if sample_rate == SAMPLE_RATE:
+        return False
+    if resample is None:
+        raise ValueError(f"audio_input: sample_rate {sample_rate} is not {SAMPLE_RATE}; resampling is not part of this front end unless "
+                         "it is asked for: resample on load, or pass resample=\"kaiser_best\" for the reference's per-clip resampy step")
+    _rate(sample_rate)
+    return True
+
+
+def resample_excerpts(wav: Tensor, starts, ends, *, window: int, sample_rate: int, sr_new: int = SAMPLE_RATE, filter="kaiser_best",
+                      wav_len=None, video=None, samples: Optional[int] = None) -> Tensor:
+    """Per clip what ``resampy.resample(audioexcer, sample_rate, sr_new)`` returns for the excerpt ``wav[starts[b] : ends[b] + 1]``
+    centred in ``window`` zero samples: ``[B, n]`` float64 with ``n = resampled_length(window, sample_rate, sr_new)``, or its first
+    ``samples`` columns.  ``filter`` is "kaiser_best", "kaiser_fast" or a ``(half_window, num_table)`` pair such as the library's
+    own stored table.  Bit-equal to the restatement of resampy 0.4.2's loop in include/diffsal.h, whatever the batch."""
+    sr_orig, sr_new = _rate(sample_rate), _rate(sr_new)
+    if sr_orig == sr_new:
+        raise ValueError(f"audio_input: resample_excerpts from {sr_orig} Hz to {sr_new} Hz: the reference does not resample there")
+    window = int(window)
+    n_out = resampled_length(window, sr_orig, sr_new)
+    n = n_out if samples is None else int(samples)
+    if window < 1 or not 1 <= n <= n_out:
+        raise ValueError(f"audio_input: {n} samples asked of a window of {window} at {sr_orig} Hz, which gives {n_out} at {sr_new} Hz")
+    w2 = _wav2(wav, wav_len, video)
+    B, s, e, ln, vi, _ = _clip_args(w2, starts, ends, window, wav_len, video, None)
+    table, num_table = _resample_tables(w2.device, sr_orig, sr_new, filter)
+    return ops.resample_excerpts(w2, _WAV_DTYPES[w2.dtype], ln, vi, s, e, B, window, sr_orig, sr_new, table, num_table, n)
+
+
+def _resampled_logmel(w2: Tensor, B, s, e, ln, vi, window: int, sample_rate, resample, n_frames: int, out_f64: bool) -> Tensor:
+    """``resample_excerpts`` for the ``400 + 160 (n_frames - 1)`` samples the frames read, then ``logmel`` on that [B, n] float64
+    wave: one "video" per clip, the whole row as its excerpt, a window of n samples (frame f reads samples 160 f .. 160 f + 399 of
+    the resampled buffer whatever follows them)."""
+    n = STFT_WINDOW + STFT_HOP * (n_frames - 1)
+    table, num_table = _resample_tables(w2.device, int(sample_rate), SAMPLE_RATE, resample)
+    zeros, last, iota = _unit_clips(w2.device, B)
+    y = ops.resample_excerpts(w2, _WAV_DTYPES[w2.dtype], ln, vi, s, e, B, window, int(sample_rate), SAMPLE_RATE, table, num_table, n)
+    return ops.logmel(y, _WAV_DTYPES[torch.float64], None, iota, zeros, last, B, n, n_frames, _tables(w2.device), out_f64=out_f64)
 
 
 def log_mel(wav: Tensor, starts, ends, *, window: int = DEFAULT_WINDOW, wav_len=None, video=None, dtype: torch.dtype = torch.float32,
-            sample_rate: int = SAMPLE_RATE, frames: Optional[int] = None) -> Tensor:
+            sample_rate: int = SAMPLE_RATE, frames: Optional[int] = None, resample=None) -> Tensor:
     """Log-mel spectrogram ``[B, F, 64]`` of each clip's excerpt ``wav[starts[b] : ends[b] + 1]`` centred in ``window`` zero
     samples, computed in float64; ``F = num_frames(window)`` or the first ``frames`` of them.  float32, or with
-    ``dtype=torch.float64`` the value before the rounding (what the tests compare)."""
-    _check_rate(sample_rate)
+    ``dtype=torch.float64`` the value before the rounding (what the tests compare).  With ``resample=`` and a ``sample_rate`` other
+    than 16000 the padded excerpt is resampled first and ``F = num_frames(resampled_length(window, sample_rate))``."""
+    resampling = _check_rate(sample_rate, resample)
     if dtype not in (torch.float32, torch.float64):
         raise ValueError(f"audio_input: dtype must be float32 or float64, got {dtype}")
     window = int(window)
-    F = num_frames(window)
+    n_out = resampled_length(window, sample_rate) if resampling else window
+    F = num_frames(n_out)
     if F < 1:
-        raise ValueError(f"audio_input: a window of {window} samples is shorter than one frame of {STFT_WINDOW}")
-    F = F if frames is None else int(frames)
+        raise ValueError(f"audio_input: a window of {n_out} samples is shorter than one frame of {STFT_WINDOW}")
+    if frames is not None:
+        if resampling and not 1 <= int(frames) <= F:
+            raise ValueError(f"audio_input: {frames} frames asked of a window that holds {F}")
+        F = int(frames)
     w2 = _wav2(wav, wav_len, video)
     B, s, e, ln, vi, _ = _clip_args(w2, starts, ends, window, wav_len, video, None)
+    if resampling:
+        return _resampled_logmel(w2, B, s, e, ln, vi, window, sample_rate, resample, F, dtype == torch.float64)
     return ops.logmel(w2, _WAV_DTYPES[w2.dtype], ln, vi, s, e, B, window, F, _tables(w2.device), out_f64=dtype == torch.float64)
 
 
 def clip_audio(wav: Tensor, starts, ends, *, size=(112, 192), window: int = DEFAULT_WINDOW, exists=None,
-               sample_rate: int = SAMPLE_RATE, wav_len=None, video=None) -> Tensor:
+               sample_rate: int = SAMPLE_RATE, wav_len=None, video=None, resample=None) -> Tensor:
     """The reference's ``data['audio']`` for a batch of clips, ``[B, 1, 9, h, w]`` float32 with ``size = (h, w)`` (half the
     frame size): nine examples of 64 log-mel frames x 64 bands each, bilinearly resized as ``F.interpolate(mode="bilinear",
-    align_corners=False)`` does in float32.  Clips with ``exists[b]`` false are zeros."""
-    _check_rate(sample_rate)
+    align_corners=False)`` does in float32.  Clips with ``exists[b]`` false are zeros.  With ``resample=`` and a ``sample_rate``
+    other than 16000, ``starts`` / ``ends`` / ``window`` are at ``sample_rate`` and the padded excerpt is resampled first (three
+    launches)."""
+    resampling = _check_rate(sample_rate, resample)
     window = int(window)
-    Fn = frames_needed(window)
+    n_out = resampled_length(window, sample_rate) if resampling else window
+    Fn = frames_needed(n_out)
     try:
         h, w = (int(v) for v in size)
     except (TypeError, ValueError):
         raise ValueError(f"audio_input: size must be (h, w), got {size!r}") from None
     w2 = _wav2(wav, wav_len, video)
     B, s, e, ln, vi, ex = _clip_args(w2, starts, ends, window, wav_len, video, exists)
-    lm = ops.logmel(w2, _WAV_DTYPES[w2.dtype], ln, vi, s, e, B, window, Fn, _tables(w2.device), out_f64=False)
-    return ops.audio_examples(lm, ex, num_examples(window), h, w)
+    if resampling:
+        lm = _resampled_logmel(w2, B, s, e, ln, vi, window, sample_rate, resample, Fn, False)
+    else:
+        lm = ops.logmel(w2, _WAV_DTYPES[w2.dtype], ln, vi, s, e, B, window, Fn, _tables(w2.device), out_f64=False)
+    return ops.audio_examples(lm, ex, num_examples(n_out), h, w)
 
 
 def examples(wav: Tensor, starts, ends, *, window: int = DEFAULT_WINDOW, exists=None, sample_rate: int = SAMPLE_RATE, wav_len=None,
-             video=None) -> Tensor:
+             video=None, resample=None) -> Tensor:
     """What ``get_mel_feature`` returns per clip, ``[B, 9, 1, 64, 64]`` float32, contiguous: the nine examples before the resize
     (``clip_audio`` at 64 x 64, where the resize is the identity; the two singleton axes trade places without a copy)."""
     out = clip_audio(wav, starts, ends, size=(EXAMPLE_FRAMES, NUM_MEL_BINS), window=window, exists=exists, sample_rate=sample_rate,
-                     wav_len=wav_len, video=video)
+                     wav_len=wav_len, video=video, resample=resample)
     return out.view(out.shape[0], NUM_EXAMPLES, 1, EXAMPLE_FRAMES, NUM_MEL_BINS)

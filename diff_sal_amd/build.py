@@ -11,7 +11,8 @@ SOURCES = ["igemm.hip", "igemm16.hip", "lin_stream.hip", "wgrad.hip", "backward.
 # headers every translation unit may include: a change rebuilds them all
 SHARED_HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_family.h"), HEADER]
 # headers only one translation unit includes: a change rebuilds that unit alone
-OWN_HEADERS = {"jpeg_export.hip": ["jpeg_core.h"], "jpeg_decode.hip": ["jpeg_core.h", "jpeg_decode_core.h"]}
+OWN_HEADERS = {"jpeg_export.hip": ["jpeg_core.h"], "jpeg_decode.hip": ["jpeg_core.h", "jpeg_decode_core.h"],
+               "audio_input.hip": ["audio_resample.h"]}
 
 
 def _hipcc():

@@ -1,18 +1,25 @@
 // From PCM samples to the audio tensor forward_vggish reads: the host pipeline of R/datasets/saliency_db.py:449-497 (get_mel_feature),
 // R/datasets/torchvggish/vggish_input.py:30-82 (waveform_to_examples), R/datasets/torchvggish/mel_features.py:71-223 (log-mel) and
 // R/datasets/saliency_db.py:303-305,351-354 (resize and stack).  include/diffsal.h ("audio front end") states the arithmetic; two
-// launches, both on the caller's stream:
+// launches, three for input at another rate than 16 kHz, all on the caller's stream:
 //   logmel           per (clip, 8 frames): the 1520 samples the frames span, read straight from the video's waveform (the centring
 //                    and the zero padding of the excerpt are index arithmetic) and kept in LDS as fp64; re / im of the 235 bins that
 //                    carry mel weight as a direct DFT of length 400 against the host-built basis hann[n] (cos, sin)(2 pi n k / 512);
 //                    magnitudes to LDS; 64 banded mel sums of at most 17 terms; log(x + 0.01); one rounding to fp32
 //   examples_resize  per output pixel: the example index map, then the bilinear resize in torch's fp32 arithmetic
+//   resample_excerpts (opt-in, in front of logmel for input at another rate) per (clip, 256 outputs): resampy's band-limited sinc
+//                    interpolation of the zero-padded, centred excerpt (csrc/audio_resample.h holds the arithmetic, shared with
+//                    tools/resample_host_check.cpp).  The span of the padded buffer the tile reads (at 22050 -> 16000: 353 + 2 x 88
+//                    samples) goes to LDS once, as fp64, zeros by index; a thread owns one output and walks its left wing, then its
+//                    right wing, one 16-byte (win, delta) load from the L2-resident table and one LDS read per tap, every
+//                    operation rounded on its own.  A tile whose span misses the excerpt writes zeros without reading the table.
 // Transform form: a direct DFT in plain fp64 FMA, not an FFT.  K is 400 (the window, not the padded 512), 235 of 257 bins are
 // needed and no bit reversal or twiddle bookkeeping exists; a thread owns 2 bins x 8 frames (32 accumulators) and walks n in
 // ascending order, so each sum has one fixed order whatever the batch.  Per n a thread reads 2 basis pairs (16 bytes each,
 // coalesced over bins, 1.6 MB in all: L2-resident) and 8 samples that every lane of the workgroup shares (LDS broadcasts).
 // No atomics, no allocation, no synchronisation: two calls give the same bits and a call can be captured in a graph.
 #include "common.h"
+#include "audio_resample.h"
 
 namespace diffsal {
 
@@ -139,6 +146,38 @@ __global__ __launch_bounds__(256) void ai_examples_resize_kernel(const float* __
   out[idx] = ai_lerp(wy0, t0, wy1, t1);
 }
 
+template <typename T>
+__global__ __launch_bounds__(resample::kTile) void ai_resample_kernel(const T* __restrict__ wav, long Lmax, int V, const long* __restrict__ wav_len,
+                                                                      const int* __restrict__ video, const int* __restrict__ starts,
+                                                                      const int* __restrict__ ends, int window, resample::Plan plan,
+                                                                      const double2* __restrict__ table, int nwin, int num_table,
+                                                                      int n_samples, double* __restrict__ out) {
+  extern __shared__ double rs_xs[];      // plan.max_span samples
+  const int b = blockIdx.y;
+  const int t0 = blockIdx.x * resample::kTile, t = t0 + threadIdx.x;
+  const int t1 = t0 + resample::kTile - 1 < n_samples - 1 ? t0 + resample::kTile - 1 : n_samples - 1;
+  int vid = video ? video[b] : 0;
+  vid = vid < 0 ? 0 : (vid >= V ? V - 1 : vid);
+  const resample::Excerpt e = resample::excerpt(starts[b], ends[b], wav_len ? wav_len[vid] : Lmax, Lmax, window);
+  int base, span;
+  resample::tile_span(t0, t1, plan.inc, plan.wing, base, span);
+  span = span < plan.max_span ? span : plan.max_span;      // the launch's LDS; max_span bounds every tile (tools/resample_host_check.cpp walks them)
+  double* o = out + static_cast<long>(b) * n_samples;
+  // the part of the excerpt inside the window is positions max(off, 0) .. min(off + v, window) - 1
+  const long first = e.off > 0 ? e.off : 0, last = (e.off + e.v < window ? e.off + e.v : window) - 1;
+  if (last < base || first >= base + span || last < first) {      // every sample the tile reads is a zero of the padding
+    if (t < n_samples) o[t] = 0.0;
+    return;
+  }
+  const T* src = wav + static_cast<long>(vid) * Lmax;
+  for (int i = threadIdx.x; i < span; i += resample::kTile) {
+    const long j = resample::source_index(e, base + i, window);
+    rs_xs[i] = j >= 0 ? ai_sample<T>(src, j) : 0.0;
+  }
+  __syncthreads();
+  if (t < n_samples) o[t] = resample::output(t, rs_xs, base, table, nwin, num_table, plan.scale, plan.inc, plan.step, window);
+}
+
 static inline int ai_frames(long window) { return window >= AI_WIN ? static_cast<int>(1 + (window - AI_WIN) / AI_HOP) : 0; }
 static inline int ai_examples(long window) { const int F = ai_frames(window); return F >= AI_EX_FRAMES ? 1 + (F - AI_EX_FRAMES) / AI_EX_HOP : 0; }
 
@@ -181,6 +220,52 @@ extern "C" int diffsal_logmel(const void* wav, int wav_dtype, int V, long Lmax, 
   else if (wav_dtype == DIFFSAL_WAV_F32) ai_logmel_launch<float>(grid, s, wav, Lmax, V, wav_len, video, starts, ends, window, n_frames, tables, out, out_f64);
   else ai_logmel_launch<double>(grid, s, wav, Lmax, V, wav_len, video, starts, ends, window, n_frames, tables, out, out_f64);
   return check_launch("logmel");
+}
+
+extern "C" long diffsal_resample_length(long n, int sr_orig, int sr_new) {
+  if (n < 0 || n > (1L << 31) || sr_orig < 1 || sr_new < 1) return -1;
+  return resample::out_len(n, sr_orig, sr_new);
+}
+
+extern "C" int diffsal_resample_excerpts(const void* wav, int wav_dtype, int V, long Lmax, const long* wav_len, const int* video,
+                                         const int* starts, const int* ends, int B, int window, int sr_orig, int sr_new, const double* table,
+                                         int nwin, int num_table, int n_samples, double* out, diffsal_stream_t stream) {
+  DS_REQUIRE(sr_orig > 0 && sr_new > 0, DIFFSAL_E_ARG, "resample_excerpts: rates %d -> %d must be positive", sr_orig, sr_new);
+  DS_REQUIRE(sr_orig != sr_new, DIFFSAL_E_ARG, "resample_excerpts: rates %d -> %d are equal (the reference does not resample there)", sr_orig,
+             sr_new);
+  DS_REQUIRE(wav_dtype == DIFFSAL_WAV_I16 || wav_dtype == DIFFSAL_WAV_F32 || wav_dtype == DIFFSAL_WAV_F64, DIFFSAL_E_ARG,
+             "resample_excerpts: wav_dtype %d (DIFFSAL_WAV_I16, DIFFSAL_WAV_F32 or DIFFSAL_WAV_F64)", wav_dtype);
+  DS_REQUIRE(B > 0 && B <= 65535 && V > 0 && Lmax > 0 && Lmax < (1L << 31), DIFFSAL_E_SHAPE,
+             "resample_excerpts: bad shape B=%d (1..65535) V=%d Lmax=%ld (1..2^31-1)", B, V, Lmax);
+  DS_REQUIRE(window >= 1 && window <= (1 << 24), DIFFSAL_E_SHAPE, "resample_excerpts: window of %d samples (1..2^24)", window);
+  DS_REQUIRE(nwin >= 2 && nwin <= (1 << 24) && num_table >= 1 && num_table <= (1 << 20), DIFFSAL_E_SHAPE,
+             "resample_excerpts: table of %d entries (2..2^24), %d per zero crossing (1..2^20)", nwin, num_table);
+  const resample::Plan plan = resample::plan(sr_orig, sr_new, nwin, num_table);
+  DS_REQUIRE(plan.step >= 1 && plan.wing >= 1, DIFFSAL_E_SHAPE,
+             "resample_excerpts: %d -> %d with %d table entries per zero crossing steps %d entries per tap through a table of %d", sr_orig, sr_new,
+             num_table, plan.step, nwin);
+  DS_REQUIRE(plan.max_span <= resample::kMaxSpan, DIFFSAL_E_SHAPE,
+             "resample_excerpts: %d -> %d with this table reads %d input samples per %d outputs, more than the %d a workgroup stages", sr_orig,
+             sr_new, plan.max_span, resample::kTile, resample::kMaxSpan);
+  const long n_out = resample::out_len(window, sr_orig, sr_new);
+  DS_REQUIRE(n_samples >= 1 && n_samples <= n_out, DIFFSAL_E_SHAPE, "resample_excerpts: %d samples asked of a window that gives %ld", n_samples,
+             n_out);
+  DS_REQUIRE(wav && starts && ends && table && out, DIFFSAL_E_ARG, "resample_excerpts: null argument");
+  DS_REQUIRE(aligned16(table), DIFFSAL_E_ARG, "resample_excerpts: table must be 16-byte aligned");
+  const dim3 grid((n_samples + resample::kTile - 1) / resample::kTile, B), block(resample::kTile);
+  const size_t lds = static_cast<size_t>(plan.max_span) * sizeof(double);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const double2* tab = reinterpret_cast<const double2*>(table);
+  if (wav_dtype == DIFFSAL_WAV_I16)
+    hipLaunchKernelGGL(ai_resample_kernel<short>, grid, block, lds, s, static_cast<const short*>(wav), Lmax, V, wav_len, video, starts, ends, window,
+                       plan, tab, nwin, num_table, n_samples, out);
+  else if (wav_dtype == DIFFSAL_WAV_F32)
+    hipLaunchKernelGGL(ai_resample_kernel<float>, grid, block, lds, s, static_cast<const float*>(wav), Lmax, V, wav_len, video, starts, ends, window,
+                       plan, tab, nwin, num_table, n_samples, out);
+  else
+    hipLaunchKernelGGL(ai_resample_kernel<double>, grid, block, lds, s, static_cast<const double*>(wav), Lmax, V, wav_len, video, starts, ends,
+                       window, plan, tab, nwin, num_table, n_samples, out);
+  return check_launch("resample_excerpts");
 }
 
 extern "C" int diffsal_audio_examples(const float* logmel, const unsigned char* exists, int B, int n_frames, int n_examples, int h, int w,

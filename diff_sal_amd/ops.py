@@ -2069,6 +2069,26 @@ def logmel(wav: Tensor, wav_dtype: int, wav_len: Optional[Tensor], video: Option
     return out
 
 
+def resample_excerpts(wav: Tensor, wav_dtype: int, wav_len: Optional[Tensor], video: Optional[Tensor], starts: Tensor, ends: Tensor, B: int,
+                      window: int, sr_orig: int, sr_new: int, table: Tensor, num_table: int, n_samples: int) -> Tensor:
+    """``diffsal_resample_excerpts`` (include/diffsal.h, "audio front end") on wav [V, Lmax] at ``sr_orig`` Hz -> [B, n_samples]
+    fp64: the head of each clip's zero-padded, centred excerpt resampled to ``sr_new`` Hz as resampy does.  ``table`` is the fp64
+    [nwin, 2] table of ``audio_input.resample_table`` on the device."""
+    lib = _lib.load()
+    V, Lmax = wav.shape
+    if not table.is_cuda or table.dtype != torch.float64 or table.dim() != 2 or table.shape[1] != 2 or not table.is_contiguous():
+        raise ValueError(f"resample_excerpts: table must be a contiguous float64 GPU tensor [nwin, 2], got {table.dtype} {tuple(table.shape)}")
+    nwin = table.shape[0]
+    out = torch.empty((B, max(int(n_samples), 0)), device=wav.device, dtype=torch.float64)
+    step = max(1, int(min(1.0, float(sr_new) / sr_orig) * num_table)) if sr_orig > 0 and sr_new > 0 else 1
+    with _prof("audio_input", 4.0 * 2 * (nwin // step) * B * n_samples, _nb(wav, out)):
+        _lib.check(lib.diffsal_resample_excerpts(wav.data_ptr(), wav_dtype, V, Lmax, None if wav_len is None else wav_len.data_ptr(),
+                                                 None if video is None else video.data_ptr(), starts.data_ptr(), ends.data_ptr(), B,
+                                                 int(window), int(sr_orig), int(sr_new), table.data_ptr(), nwin, int(num_table),
+                                                 int(n_samples), out.data_ptr(), _stream()), "resample_excerpts")
+    return out
+
+
 def audio_examples(lm: Tensor, exists: Optional[Tensor], n_examples: int, h: int, w: int) -> Tensor:
     """``diffsal_audio_examples`` on log-mel [B, F, 64] fp32 -> [B, 1, 9, h, w] fp32: the nine examples, bilinearly resized."""
     lib = _lib.load()

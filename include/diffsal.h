@@ -934,7 +934,10 @@ int diffsal_jpeg_decode(const unsigned char* bytes, long nbytes, const void* fil
  * zero buffer of `window` samples and calls R/datasets/torchvggish/vggish_input.py:30-82 (waveform_to_examples), which frames
  * the log-mel spectrogram of R/datasets/torchvggish/mel_features.py:71-223 into examples; get_mel_feature repeats them to nine
  * and R/datasets/saliency_db.py:303-305,351-354 resizes each to half the frame size and stacks them.
- * Input at 16000 Hz only: the reference's resampy step is not built and any other sample_rate is DIFFSAL_E_ARG.
+ * diffsal_logmel takes input at 16000 Hz only and any other sample_rate is DIFFSAL_E_ARG there.  The reference reads a file at its
+ * native rate, tabulates starts / ends at that rate and, per clip, resamples the padded buffer to 16000 Hz with resampy
+ * (R/datasets/torchvggish/vggish_input.py:52-53): that step is diffsal_resample_excerpts, an opt-in launch in front of
+ * diffsal_logmel, whose output [B][n_samples] fp64 is diffsal_logmel's wav with V = B, video[b] = b and window = n_samples.
  *
  * diffsal_logmel: wav [V][Lmax] of wav_dtype (int16 is divided by 32768, exactly; fp32; fp64), wav_len [V] valid samples per
  * video (NULL: Lmax), video [B] the video of each clip (NULL: 0), starts / ends [B] -> out [B][n_frames][64], fp32 (out_f64 = 0)
@@ -964,7 +967,33 @@ int diffsal_jpeg_decode(const unsigned char* bytes, long nbytes, const void* fil
  *     the plain form, with no anti-aliasing filter, for every h and w: for an upscale that is also what the antialiased form
  *     computes; for h or w below 64 a torchvision whose tensor Resize defaults to antialias=True gives other values
  *   a clip with exists[b] == 0 is zeros (the reference returns zeros, not log(0.01), for a video without audio)
- * Both calls: every sum has a fixed order, results are bit-reproducible and a clip's result does not depend on the batch it is
+ *
+ * diffsal_resample_excerpts: wav, wav_dtype, V, Lmax, wav_len, video, starts, ends, B as for diffsal_logmel, at sr_orig Hz ->
+ * out [B][n_samples] fp64: the first n_samples <= int(window * sr_new / sr_orig) (= diffsal_resample_length) samples of what
+ * resampy 0.4.2 (resampy.core.resample, resampy.interp._resample_loop) returns for the clip's padded buffer x[0 .. window - 1]
+ * (lo, v, off as above; x is never written to memory; the accumulation is fp64 for every wav_dtype, as the reference's buffer is):
+ *   ratio = fp64(sr_new) / sr_orig;  scale = min(1, ratio);  inc = 1 / ratio;  step = int(scale * num_table)   (truncated: 371 at
+ *                                                                              22050 -> 16000; the library's behaviour, kept)
+ *   output t:  time = t * inc;  m = int(time);  frac = scale * (time - m)
+ *              f = frac * num_table;  o = int(f);  eta = f - o
+ *              for i = 0 .. min(m + 1, (nwin - o) / step) - 1:           y += (win[o + i step] + eta * delta[o + i step]) * x[m - i]
+ *              frac = scale - frac;  f = frac * num_table;  o = int(f);  eta = f - o
+ *              for k = 0 .. min(window - m - 1, (nwin - o) / step) - 1:  y += (win[o + k step] + eta * delta[o + k step]) * x[m + k + 1]
+ * Every operation is one fp64 operation rounded to nearest, product then sum, nothing fused (the library is numba without
+ * fast-math), in exactly this order: the left wing in ascending i, then the right wing in ascending k.  The result is therefore a
+ * function of the inputs alone and equals a NumPy restatement of these lines bit for bit.  A tile of outputs that reads nothing
+ * but padding is written as zeros without the sums (w * 0 is a signed zero and y + a signed zero is y: the bits are the same).
+ * `table`: [nwin][2] fp64 on the device, 16-byte aligned, built by the caller in fp64: (win[j], delta[j]) with win the filter's
+ * half window, num_table entries per zero crossing, multiplied by ratio if ratio < 1, and delta[j] = win[j + 1] - win[j],
+ * delta[nwin - 1] = 0.  The kernel does not depend on the filter's design.  resampy's kaiser_best is
+ *   win[j] = r sinc(r j / 512) kaiser(2 * 32768 + 1, beta)[32768 + j],  j = 0 .. 32768  (nwin 32769, num_table 512),
+ *   r = 0.9475937167399596, beta = 14.769656459379492;  kaiser_fast: 16 zero crossings (nwin 8193), r = 0.85, beta = 8.555504641634386
+ * DIFFSAL_E_ARG: a rate below 1, sr_orig == sr_new (the reference does not resample there), a bad wav_dtype, a null or
+ * misaligned pointer.  DIFFSAL_E_SHAPE: n_samples outside 1 .. int(window * sr_new / sr_orig), nwin < 2, step < 1 or > nwin, a
+ * tile of 256 outputs that reads more than 8192 inputs (255 * inc + 2 + 2 (nwin / step)).
+ * diffsal_resample_length: int(n * sr_new / sr_orig), the product in integers, one fp64 division, truncated; -1 for a bad argument.
+ *
+ * All calls: every sum has a fixed order, results are bit-reproducible and a clip's result does not depend on the batch it is
  * in.  No atomics, no allocation, no synchronisation, graph-safe.  All argument checks precede the launch. */
 #define DIFFSAL_WAV_I16 0
 #define DIFFSAL_WAV_F32 1
@@ -975,6 +1004,10 @@ int diffsal_logmel(const void* wav, int wav_dtype, int V, long Lmax, const long*
                    diffsal_stream_t stream);
 int diffsal_audio_examples(const float* logmel, const unsigned char* exists, int B, int n_frames, int n_examples, int h, int w,
                            float* out, diffsal_stream_t stream);
+long diffsal_resample_length(long n, int sr_orig, int sr_new);
+int diffsal_resample_excerpts(const void* wav, int wav_dtype, int V, long Lmax, const long* wav_len, const int* video, const int* starts,
+                              const int* ends, int B, int window, int sr_orig, int sr_new, const double* table, int nwin, int num_table,
+                              int n_samples, double* out, diffsal_stream_t stream);
 
 /* ---- video front end: decoded uint8 frames in device memory -> the clip tensor [B][3][T][h][w] MViT reads -----------
  * What the reference does per clip on the host with Pillow: R/datasets/saliency_db.py:29-36 (pil_loader) resizes every frame to
