@@ -2054,6 +2054,27 @@ def jpeg_decode(packed: Tensor, files: Tensor, segments: Tensor, max_file_seg: i
     return out, status
 
 
+def png_decode(packed: Tensor, files: Tensor, N: int, H: int, W: int, color_type: int, bit_depth: int, mode_l: bool):
+    """``diffsal_png_decode`` (include/diffsal.h, "PNG decode"): packed uint8 [nbytes] (a multiple of 16), files uint8 [N, 784] ->
+    (frames uint8 [N, H, W, 3] or [N, H, W], status int32 [N])."""
+    lib = _lib.load()
+    for t, what in ((packed, "packed"), (files, "files")):
+        if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
+            raise ValueError(f"png_decode: {what} must be a contiguous uint8 GPU tensor, got {t.dtype} {t.device}")
+    if files.shape != (N, 784):
+        raise ValueError(f"png_decode: files {tuple(files.shape)} (want [{N}, 784])")
+    nws = lib.diffsal_png_decode_ws_bytes(N, H, W, color_type, bit_depth)
+    if nws == 0:
+        raise ValueError(f"png_decode: N={N}, {H} x {W}, colour type {color_type} at {bit_depth} bits: outside what the decode takes")
+    out = torch.empty((N, H, W) if mode_l else (N, H, W, 3), device=packed.device, dtype=torch.uint8)
+    status = torch.empty((N,), device=packed.device, dtype=torch.int32)
+    ws = torch.empty((nws // 8,), device=packed.device, dtype=torch.float64)
+    with _prof("metrics", 0.0, _nb(packed, out) + 2 * nws):
+        _lib.check(lib.diffsal_png_decode(packed.data_ptr(), packed.numel(), files.data_ptr(), N, H, W, color_type, bit_depth,
+                                          1 if mode_l else 0, out.data_ptr(), status.data_ptr(), ws.data_ptr(), nws, _stream()), "png_decode")
+    return out, status
+
+
 def logmel(wav: Tensor, wav_dtype: int, wav_len: Optional[Tensor], video: Optional[Tensor], starts: Tensor, ends: Tensor, B: int,
            window: int, n_frames: int, tables: Tensor, *, out_f64: bool = False, sample_rate: int = 16000) -> Tensor:
     """``diffsal_logmel`` (include/diffsal.h, "audio front end") on wav [V, Lmax] -> log-mel [B, n_frames, 64] fp32 (fp64 with

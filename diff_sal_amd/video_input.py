@@ -20,8 +20,8 @@ horizontal and the vertical pass), and ``ToTensor`` / ``Normalize`` see only 256
 **bit-equal** to the reference's, not merely close.  The coefficient tables are built here in float64 as Pillow builds them
 (``resample_table``); the look-up tables are built with the reference's own torch CPU operations (``normalize_table``).
 
-JPEG decoding with ``convert('RGB' | 'L')`` is ``jpeg.decode`` / ``jpeg.decode_files``, whose output is the ``frames`` taken here; PNG
-decoding stays with the caller.  Only the bilinear and bicubic filters are built; all
+JPEG decoding with ``convert('RGB' | 'L')`` is ``jpeg.decode`` / ``jpeg.decode_files``, whose output is the ``frames`` taken here; the
+visual sets' PNG frames and maps are decoded the same way by ``png.decode`` / ``png.decode_files``.  Only the bilinear and bicubic filters are built; all
 frames of a call share one source size.  Indices given on the host (a sequence, a numpy array, a CPU tensor) are range-checked
 here and uploaded; a GPU tensor is used as it is, with no host copy and no synchronisation (the kernel clamps what could not be
 checked), so the call can be captured in a graph.  The first call for a size, filter or normalisation uploads its tables from

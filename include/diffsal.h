@@ -928,6 +928,52 @@ int diffsal_jpeg_decode(const unsigned char* bytes, long nbytes, const void* fil
                         int N, int H, int W, int ncomp, int hs, int vs, int mode_l, unsigned char* out, int* status, void* ws,
                         size_t ws_bytes, diffsal_stream_t stream);
 
+/* ---- PNG decode: the frame and map files of the visual sets -> the uint8 frames Pillow returns -----------
+ * R/datasets/dhf1k_data.py:78, R/datasets/ucf_dataset.py:68 and R/datasets/holly2wood_dataset.py:72 read every frame '%d.png' with
+ * Image.open(f).convert('RGB'); R/datasets/meta_data.py:49-57 reads the annotation maps '%04d.png' with .convert('L');
+ * R/compute_metrics.py:9-14 reads the .png files of maps/ and fixation/ back.  Every step is integer arithmetic and the result here is
+ * bit-equal to Pillow 12.2.  Taken: non-interlaced files of bit depth 8 with colour type 0, 2, 3, 4 or 6 (Pillow's L, RGB, P, LA,
+ * RGBA) and of depth 1, 2 or 4 with colour type 0 or 3; everything else is refused by the caller's parser before a launch.
+ *   (a) inflate   RFC 1950 / 1951: the IDAT payloads end to end are one zlib stream (32 K window, no dictionary); stored, fixed and
+ *                 dynamic blocks; its output is H rows of 1 + row_bytes bytes, row_bytes = ceil(W * channels * depth / 8)
+ *   (b) filter    PNG 9.2: the first byte of a row is its filter, 0 None, 1 Sub, 2 Up, 3 Average (floor((a + b) / 2)), 4 Paeth
+ *                 (p = a + b - c; the nearest of a, b, c, ties in that order); a: the byte one pixel to the left (one byte below 8
+ *                 bits), b: above, c: above left; bytes outside the image are 0; sums modulo 256
+ *   (c) samples   8 bits: as they are.  1, 2, 4 bits: most significant first in a byte; grey values times 255, 85, 17; a palette
+ *                 index selects its PLTE entry (a short PLTE is padded with zeros)
+ *   (d) RGB       grey: R = G = B = value; alpha is dropped; tRNS is ignored for every type
+ *   (e) L         grey: the value.  RGB, RGBA and palette entries: (19595 R + 38470 G + 7471 B + 0x8000) >> 16
+ * diffsal_png_decode: N files of one size H x W, colour type and bit depth, all in device memory:
+ *   bytes     the files' zlib streams, each starting at a multiple of 16, padded with zeros to nbytes, a multiple of 16 below
+ *             2^31; 16-byte aligned
+ *   files     N records of 784 bytes: uint32 off, len (the stream in `bytes`), 2 unused; uint8 pal[768]: PLTE, zero-padded
+ *   out       [N][H][W][3] bytes (mode_l = 0) or [N][H][W] (mode_l = 1), indexed in 64 bits
+ *   status    int32 [N]: 0 clean, else the OR of the DIFFSAL_PNG_* bits below.  DIFFSAL_PNG_LONG alone leaves the pixels intact;
+ *             with any other bit the pixels of that file are unspecified (they lie inside its frame and are the same in every
+ *             call), and the other files of the call are unaffected.  DIFFSAL_PNG_SHORT is stricter than Pillow, which returns
+ *             such a file without a word
+ *   ws        >= diffsal_png_decode_ws_bytes(N, H, W, color_type, bit_depth) bytes, 16-byte aligned: 16 bytes of state per file,
+ *             then per file its filtered scanlines, H * (1 + row_bytes) bytes padded to 16.  Every byte read is written first
+ * For any contents of bytes and files no kernel reads outside them or writes outside out, status and ws: stream reads are clamped
+ * to [off, off + len) inside nbytes, region writes to the file's region, and every loop is bounded by N, H, W or by the stream's
+ * bits (every symbol consumes at least one).  Chunk CRCs are not looked at (they never reach the device); Adler-32 is verified.
+ * Launches: inflate, then unfilter + convert + Adler-32; a wave per file in both.  W <= 8192.  Bit-reproducible; a file's pixels
+ * do not depend on the batch it is in.  No allocation, no synchronisation, no host copy, graph-safe; all argument checks precede
+ * the first launch (DIFFSAL_E_ARG / DIFFSAL_E_SHAPE with a message).  ws_bytes: 0 for a bad argument. */
+#define DIFFSAL_PNG_BAD_BLOCK 1
+#define DIFFSAL_PNG_BAD_STORED 2
+#define DIFFSAL_PNG_BAD_LENGTHS 4
+#define DIFFSAL_PNG_BAD_SYMBOL 8
+#define DIFFSAL_PNG_BAD_DISTANCE 16
+#define DIFFSAL_PNG_NO_INPUT 32
+#define DIFFSAL_PNG_SHORT 64
+#define DIFFSAL_PNG_LONG 128
+#define DIFFSAL_PNG_BAD_FILTER 256
+#define DIFFSAL_PNG_BAD_ADLER 512
+size_t diffsal_png_decode_ws_bytes(int N, int H, int W, int color_type, int bit_depth);
+int diffsal_png_decode(const void* bytes, long nbytes, const void* files, int N, int H, int W, int color_type, int bit_depth,
+                       int mode_l, void* out, void* status, void* ws, size_t ws_bytes, diffsal_stream_t stream);
+
 /* ---- audio front end: PCM samples in device memory -> the audio tensor [B][1][9][h][w] forward_vggish reads -----------
  * What the reference does per clip on the host in numpy: R/datasets/saliency_db.py:449-497 (get_mel_feature) cuts
  * wav[starts[a] : ends[b] + 1] out of the video's waveform (the table of R/datasets/saliency_db.py:208-222), centres it in a
@@ -1015,7 +1061,7 @@ int diffsal_resample_excerpts(const void* wav, int wav_dtype, int V, long Lmax, 
  * and Normalize(mean, std); :382-394 stacks and permutes the frames.  R/datasets/meta_data.py:27-35 and
  * R/datasets/dhf1k_data.py:72-81 run transforms.Resize on the PIL image (bilinear), ToTensor and Normalize.  The targets
  * (saliency_db.py:298-301 target_transform, meta_data.py:32-35 sal_transform) are the same resize of an 'L' image and / 255.
- * JPEG decoding with convert('RGB' | 'L') is diffsal_jpeg_decode ("JPEG decode"); PNG decoding stays with the caller.
+ * JPEG decoding with convert('RGB' | 'L') is diffsal_jpeg_decode ("JPEG decode"), PNG decoding is diffsal_png_decode ("PNG decode").
  *
  * diffsal_resample_u8: in [N][H0][W0][C] bytes, C = 1 or 3 -> out [N][H1][W1][C] bytes: one Image.resize of Pillow's 8-bit path
  * (ImagingResample), bit for bit.  The coefficients are the caller's, built in float64 as precompute_coeffs builds them, per
