@@ -7,12 +7,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libdiffsal_hip.so")
 HEADER = os.path.join(os.path.dirname(HERE), "include", "diffsal.h")      # the C ABI: compiled into the library, read by _lib.py
-SOURCES = ["igemm.hip", "igemm16.hip", "lin_stream.hip", "wgrad.hip", "backward.hip", "optim.hip", "pack.hip", "norm.hip", "misc.hip", "metrics.hip", "eval_metrics.hip", "postprocess.hip", "jpeg_export.hip", "jpeg_decode.hip", "png_decode.hip", "audio_input.hip", "video_input.hip", "attention.hip", "attn_fold.hip", "mvit.hip", "mvit_pool.hip", "block16.hip", "conv16_halo.hip", "conv16_dma.hip", "gemm16_dma.hip", "attn16_mfma.hip", "tapsum.hip", "tblock.hip", "gemm_dma.hip", "wino4.hip", "upconv.hip"]
+SOURCES = ["igemm.hip", "igemm16.hip", "lin_stream.hip", "wgrad.hip", "backward.hip", "optim.hip", "pack.hip", "norm.hip", "misc.hip", "metrics.hip", "eval_metrics.hip", "postprocess.hip", "jpeg_export.hip", "jpeg_decode.hip", "png_decode.hip", "png_encode.hip", "audio_input.hip", "video_input.hip", "attention.hip", "attn_fold.hip", "mvit.hip", "mvit_pool.hip", "block16.hip", "conv16_halo.hip", "conv16_dma.hip", "gemm16_dma.hip", "attn16_mfma.hip", "tapsum.hip", "tblock.hip", "gemm_dma.hip", "wino4.hip", "upconv.hip"]
 # headers every translation unit may include: a change rebuilds them all
 SHARED_HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_family.h"), HEADER]
 # headers only one translation unit includes: a change rebuilds that unit alone
 OWN_HEADERS = {"jpeg_export.hip": ["jpeg_core.h"], "jpeg_decode.hip": ["jpeg_core.h", "jpeg_decode_core.h"],
-               "png_decode.hip": ["png_decode_core.h"], "audio_input.hip": ["audio_resample.h"]}
+               "png_decode.hip": ["png_decode_core.h"], "png_encode.hip": ["png_encode_core.h"],
+               "audio_input.hip": ["audio_resample.h"]}
 
 
 def _hipcc():

@@ -2075,6 +2075,34 @@ def png_decode(packed: Tensor, files: Tensor, N: int, H: int, W: int, color_type
     return out, status
 
 
+def png_capacity(h: int, w: int) -> int:
+    """``diffsal_png_encode_capacity``: the bytes no PNG file of an h x w map can exceed, a multiple of 16 (host arithmetic)."""
+    cap = _lib.load().diffsal_png_encode_capacity(int(h), int(w))
+    if cap <= 0:
+        raise ValueError(f"png_capacity: {h} x {w} (height 1..65535, width 1..8192)")
+    return cap
+
+
+def png_encode(u8: Tensor):
+    """``diffsal_png_encode`` (include/diffsal.h, "PNG export") on u8 [B, h, w] uint8 -> (data [B, cap] uint8, lengths [B] int32):
+    image b's file is ``data[b, :lengths[b]]``."""
+    lib = _lib.load()
+    if not u8.is_cuda or u8.dtype != torch.uint8 or not u8.is_contiguous() or u8.dim() != 3 or u8.numel() == 0:
+        raise ValueError(f"png_encode: expected a non-empty contiguous uint8 GPU tensor [B, h, w], got {u8.dtype} {u8.device} {tuple(u8.shape)}")
+    B, h, w = u8.shape
+    nws = lib.diffsal_png_encode_ws_bytes(B, h, w)
+    if nws == 0:
+        raise ValueError(f"png_encode: B={B}, {h} x {w}: outside what the export takes (B 1..65535, height 1..65535, width 1..8192)")
+    cap = png_capacity(h, w)
+    data = torch.empty((B, cap), device=u8.device, dtype=torch.uint8)
+    lengths = torch.empty((B,), device=u8.device, dtype=torch.int32)
+    ws = torch.empty((nws // 8,), device=u8.device, dtype=torch.float64)
+    with _prof("metrics", 0.0, _nb(u8, data) + 2 * nws):
+        _lib.check(lib.diffsal_png_encode(u8.data_ptr(), B, h, w, data.data_ptr(), cap, lengths.data_ptr(), ws.data_ptr(), nws, _stream()),
+                   "png_encode")
+    return data, lengths
+
+
 def logmel(wav: Tensor, wav_dtype: int, wav_len: Optional[Tensor], video: Optional[Tensor], starts: Tensor, ends: Tensor, B: int,
            window: int, n_frames: int, tables: Tensor, *, out_f64: bool = False, sample_rate: int = 16000) -> Tensor:
     """``diffsal_logmel`` (include/diffsal.h, "audio front end") on wav [V, Lmax] -> log-mel [B, n_frames, 64] fp32 (fp64 with

@@ -9,10 +9,19 @@ each file on one thread; R/compute_metrics.py:9-14 reads the ``maps`` and ``fixa
   (``parse_file``, ``pack``); inflate, the filters, sample unpacking, the palette and the conversion to ``RGB`` / ``L`` run on the
   device, and no pixel exists on the host.
 
+The other direction, the reference's export for these sets (csrc/png_encode.hip, arithmetic in include/diffsal.h "PNG export"):
+R/diffusion_trainer.py:898-935 (``save_img``) writes every prediction as ``<video>/<frame>.png``.
+
+* ``encode`` gives the complete 8-bit greyscale files of a batch in device memory, ``save_predictions`` writes them; only finished
+  file bytes travel to the host.  The files are not Pillow's bytes: they are valid PNGs that every decoder reads back to exactly the
+  input pixels, and their bytes are a function of the pixels alone (tests/_png_encode_ref.py restates them).
+  ``postprocess.save_predictions`` is the host path through Pillow, unchanged and still the default there.
+
 GPU only: CPU tensors raise.
 """
 from __future__ import annotations
 
+import os
 from typing import Sequence
 
 import numpy as np
@@ -209,3 +218,58 @@ def decode_files(paths: Sequence, mode: str = "RGB", device=None, strict: bool =
         with open(p, "rb") as f:
             data.append(f.read())
     return decode(data, mode=mode, device=device, strict=strict)
+
+
+# ---- export: 8-bit maps -> complete .png files (csrc/png_encode.hip, include/diffsal.h "PNG export") ----
+def _maps(u8: Tensor, what: str = "u8") -> Tensor:
+    """[B, 1, H, W] or [B, H, W] uint8 GPU tensor -> contiguous [B, H, W]"""
+    if not isinstance(u8, Tensor) or not u8.is_cuda:
+        raise RuntimeError(f"diff_sal_amd png runs on the GPU only (no CPU fallback); {what} is on "
+                           f"{getattr(u8, 'device', type(u8).__name__)}")
+    if u8.dtype != torch.uint8:
+        raise ValueError(f"png: {what} must be uint8 (postprocess.to_uint8 gives it), got {u8.dtype}")
+    if u8.dim() == 4 and u8.shape[1] == 1:
+        u8 = u8[:, 0]
+    if u8.dim() != 3 or u8.numel() == 0:
+        raise ValueError(f"png: {what} must be a non-empty [B, 1, H, W] or [B, H, W], got {tuple(u8.shape)}")
+    if u8.shape[0] > 65535 or u8.shape[1] > 65535 or u8.shape[2] > MAX_WIDTH:
+        raise ValueError(f"png: {tuple(u8.shape)}: at most 65535 maps of at most 65535 rows and {MAX_WIDTH} columns (what decode takes)")
+    return u8.contiguous()
+
+
+def capacity(h: int, w: int) -> int:
+    """The bytes no file of an ``h x w`` map exceeds: the width of ``encode``'s rows, a multiple of 16."""
+    return ops.png_capacity(h, w)
+
+
+def encode(u8: Tensor):
+    """The ``.png`` file of every map of ``u8`` (uint8 ``[B, H, W]`` or ``[B, 1, H, W]``): ``(data uint8 [B, cap], lengths int32
+    [B])`` on the device, map ``b``'s file being ``data[b, :lengths[b]]`` (zeros behind it).  8-bit greyscale, one IDAT; a decoder
+    reads back exactly ``u8``.  No host copy, no synchronisation: capturable."""
+    return ops.png_encode(_maps(u8))
+
+
+def save_predictions(pred: Tensor, video_ids: Sequence, frame_ids: Sequence, root: str):
+    """The reference's ``save_img`` for the visual sets: ``<root>/<video id>/<frame id>.png`` holding
+    ``encode(postprocess.to_uint8(pred))``'s bytes.  One host copy of ``lengths``, then one of the used part of ``data``: nothing
+    else leaves the device.  The pixels a decoder reads from these files are those of ``postprocess.save_predictions``'s files;
+    the bytes are not.  Returns the paths written."""
+    from . import postprocess
+
+    u8 = postprocess.to_uint8(pred)
+    frame_ids = [int(f) for f in (frame_ids.reshape(-1).tolist() if isinstance(frame_ids, Tensor) else frame_ids)]
+    video_ids = list(video_ids)
+    if not (u8.shape[0] == len(video_ids) == len(frame_ids)):
+        raise ValueError(f"postprocess: {u8.shape[0]} predictions, {len(video_ids)} video ids, {len(frame_ids)} frame ids")
+    data, lengths = encode(u8)
+    n = lengths.cpu().numpy()
+    host = data[:, :int(n.max())].cpu().numpy()      # the rows cut at the longest file: a few per cent of their capacity
+    paths = []
+    for row, length, vid, fid in zip(host, n, video_ids, frame_ids):
+        d = os.path.join(root, str(vid))
+        os.makedirs(d, exist_ok=True)
+        path = os.path.join(d, f"{fid}.png")
+        with open(path, "wb") as f:
+            f.write(row[:int(length)].tobytes())
+        paths.append(path)
+    return paths

@@ -18,7 +18,8 @@ before that rounding.  Two things could not be run where this module was written
 * the reference's JPEG path.  For the audio-visual sets it writes ``pred_sal_%06d.jpg`` with ``cv2.imwrite``.  That export is integer
   arithmetic throughout and lives in ``diff_sal_amd.jpeg`` (files and read-back pixels, held to Pillow byte for byte; its docstring
   says what rests on reading OpenCV's sources): ``protocol_metrics(..., quantize="jpeg")`` scores the map a decoder reads back from
-  that file, ``jpeg.save_predictions`` writes the files.  ``save_predictions`` here writes PNG only, in the layout of the visual sets.
+  that file, ``jpeg.save_predictions`` writes the files.  ``save_predictions`` here writes PNG only, in the layout of the visual sets,
+  through Pillow on the host; ``png.save_predictions`` writes the same layout from files encoded on the device (``png.encode``).
 
 Deliberate definition: a flat prediction (max == min; ``normalize_data`` divides by zero there) quantises to all zeros.
 GPU only: CPU tensors raise.
@@ -145,7 +146,9 @@ def protocol_metrics(pred: Tensor, fix: Optional[Tensor], gt: Optional[Tensor] =
 
 def save_predictions(pred: Tensor, video_ids: Sequence, frame_ids: Sequence, root: str, *, fmt: str = "png"):
     """The reference's ``save_img`` for the visual sets: ``<root>/<video id>/<frame id>.png`` holding ``to_uint8``'s bytes as an
-    8-bit greyscale PNG.  Only the bytes travel to the host.  Returns the paths written."""
+    8-bit greyscale PNG.  Only the bytes travel to the host, where Pillow encodes one file after the other;
+    ``diff_sal_amd.png.save_predictions`` encodes on the device and writes the same layout (the same pixels, other file bytes).
+    Returns the paths written."""
     if fmt != "png":
         raise ValueError(f"postprocess: fmt {fmt!r} is not offered (the reference's JPEG for the audio-visual sets is lossy: "
                          "a map written that way is not this one; diff_sal_amd.jpeg.save_predictions writes those files); use 'png'")

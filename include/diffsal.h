@@ -974,6 +974,58 @@ size_t diffsal_png_decode_ws_bytes(int N, int H, int W, int color_type, int bit_
 int diffsal_png_decode(const void* bytes, long nbytes, const void* files, int N, int H, int W, int color_type, int bit_depth,
                        int mode_l, void* out, void* status, void* ws, size_t ws_bytes, diffsal_stream_t stream);
 
+/* ---- PNG export: the 8-bit maps of the visual sets -> complete .png files -----------
+ * For DHF1K, UCF-Sports and Hollywood-2 R/diffusion_trainer.py:898-935 (save_img) writes '<video>/<frame>.png'.  u8 = the bytes of
+ * diffsal_map_to_u8, [B][H][W], 1 <= B <= 65535, 1 <= H <= 65535, 1 <= W <= 8192 (what "PNG decode" takes); anything else is
+ * DIFFSAL_E_SHAPE.  The files are not Pillow's bytes: they are valid PNGs that decode to exactly the input, and their bytes are a
+ * function of the pixels alone (tests/_png_encode_ref.py restates them in NumPy), whatever the launch shape, the order of the
+ * atomics, the batch or the buffers' earlier contents.  Integer work throughout.
+ *   file       the 8-byte signature; IHDR (W, H big-endian, depth 8, colour type 0, compression 0, filter 0, interlace 0); one
+ *              IDAT; IEND.  Chunk CRC-32s are correct.  The file has 57 + len(IDAT payload) bytes
+ *   IDAT       78 01; one deflate stream; the Adler-32, big-endian, of the filtered scanlines
+ *   scanlines  H rows of 1 + W bytes: the filter type, then the filtered bytes.  For every row all five filters (PNG 9.2) are
+ *              computed from the raw pixels (a: left, b: above, c: above left, 0 outside the image); the one kept has the least sum
+ *              of min(v, 256 - v) over its W bytes, a tie goes to the lowest type
+ *   segments   the H * (W + 1) bytes in pieces of 16384 (the last may be shorter), each exactly one block with dynamic codes
+ *              (BTYPE 2), BFINAL on the last only; blocks follow each other bit by bit; the last byte is padded with zero bits
+ *   tokens     distance 1 only.  At position p of a segment, r = the count of consecutive positions q >= p inside the segment whose
+ *              byte equals the stream byte in front of it (which may lie in the segment before, never in front of the stream).
+ *              r >= 3: a match of length min(r, 258) at distance 1, advance by it; else the literal, advance by one.  A run thus
+ *              falls into pieces of 258 from its start and a rest of 1 or 2 is literals.  The block ends with symbol 256
+ *   lengths    of a code from symbol counts with limit L (15: literal/length, 286 symbols; 7: code lengths, 19 symbols): the
+ *              symbols with a count take part (symbols 0 and 1 too if fewer than two have one), in ascending order of (count,
+ *              symbol).  Huffman's tree by the two-queue method, a leaf before an internal node of equal weight, gives the
+ *              number of codes per length.  If a length exceeds L: all above L are counted at L; then, until the Kraft sum in
+ *              units of 2^-L is 2^L: one code less at L, and at the largest length i < L that has a code one code less and two
+ *              more at i + 1 (each round lowers the sum by exactly one unit).  The lengths are handed out along the order, the
+ *              longest to the rarest.  The code is complete: Kraft sum exactly 1.  Codes are canonical (RFC 1951 3.2.2)
+ *   distance   one code: symbol 0 with length 1 (HDIST = 0), sent in every block; a match spends one 0 bit on it
+ *   header     HLIT = up to the last literal/length symbol with a length (at least 257).  The HLIT lengths and the distance length
+ *              are one sequence, run-length coded: a run of zeros in pieces of 138 (symbol 18) while 11 or more are left, then
+ *              17 for 3..10, else zeros one by one; another value once, then 16 in pieces of 6 while 3 or more are left, then the
+ *              value itself.  HCLEN trimmed to the last code-length symbol with a length in the order 16 17 18 0 8 7 9 ...
+ * diffsal_png_encode: data [B][cap] bytes, 16-byte aligned, cap a multiple of 16 and >= diffsal_png_encode_capacity(H, W); image b's
+ * file is data[b][0 .. lengths[b]), lengths int32 [B]; the bytes behind a file are zero.
+ * Capacity is a bound, not an estimate.  Every token spends at most 15 bits per stream byte it covers (a literal 15; a match at most
+ * 15 + 5 + 1 for three bytes or more).  A block adds its header, at most 3 + 14 + 3 * 19 + 287 * (7 + 7) = 4092 bits (287 lengths,
+ * each at most one code-length symbol of 7 bits and 7 extra bits), and an end symbol of at most 15 bits.  With S = H * (W + 1) and
+ * n = ceil(S / 16384):  m = ceil((15 S + 4107 n) / 8) bytes of deflate stream, and
+ *   diffsal_png_encode_capacity(H, W) = (63 + m) rounded up to 16      (63 = 57 + zlib's header and Adler-32; below 2^31)
+ * so that every image's row of data starts on a 16-byte boundary.  ws >= diffsal_png_encode_ws_bytes(B, H, W) bytes, 16-byte
+ * aligned, every array sized from the same geometry: the scanlines (S padded to 64) and a 16-bit token record per stream byte,
+ * per segment 256 bit offsets, 288 codes, 128 header words, 16 bytes of sums and a 64-bit bit offset, per image a 64-bit bit
+ * count.  Every byte read is written first.  No kernel writes outside data[b][0 .. cap), lengths or ws for any pixels, and every
+ * loop is bounded by the geometry or a segment's size.
+ * Launches: a clear of data (hipMemsetAsync on `stream`, every call); filter (a wave per row); segment (a workgroup per segment:
+ * tokens, histogram, codes, header, bit counts, Adler-32 sums); frame (a workgroup per image: scan of the bit counts, everything
+ * but the stream and IDAT's CRC); pack (integer atomicOr into the shared words: order-independent); crc (partial CRCs of 64
+ * bytes combined by multiplication by x^(8 n) mod P).  No allocation, no synchronisation, no host copy, graph-safe; all argument
+ * checks precede the first launch (DIFFSAL_E_ARG / DIFFSAL_E_SHAPE with a message).  capacity, ws_bytes: 0 for a bad argument. */
+long diffsal_png_encode_capacity(int H, int W);
+size_t diffsal_png_encode_ws_bytes(int B, int H, int W);
+int diffsal_png_encode(const void* u8, int B, int H, int W, void* data, long cap, void* lengths, void* ws, size_t ws_bytes,
+                       diffsal_stream_t stream);
+
 /* ---- audio front end: PCM samples in device memory -> the audio tensor [B][1][9][h][w] forward_vggish reads -----------
  * What the reference does per clip on the host in numpy: R/datasets/saliency_db.py:449-497 (get_mel_feature) cuts
  * wav[starts[a] : ends[b] + 1] out of the video's waveform (the table of R/datasets/saliency_db.py:208-222), centres it in a
