@@ -89,6 +89,23 @@ __device__ __forceinline__ float group_max(float v) {
   return group_reduce<WIDTH>(v, [](float a, float b) { return fmaxf(a, b); });
 }
 
+// exclusive scan of one value per thread over a workgroup of THREADS; the workgroup's total through `total`.  sh: THREADS words
+template <int THREADS>
+__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* sh, uint32_t& total) {
+  const int t = threadIdx.x;
+  __syncthreads();      // sh may still be read from the round before
+  sh[t] = v;
+  __syncthreads();
+  for (int o = 1; o < THREADS; o <<= 1) {
+    const uint32_t add = t >= o ? sh[t - o] : 0u;
+    __syncthreads();
+    sh[t] += add;
+    __syncthreads();
+  }
+  total = sh[THREADS - 1];
+  return sh[t] - v;
+}
+
 // x sigmoid(x) with e = exp(-|x|) <= 1: x / (1 + e) for x >= 0 (the plain form, bit for bit), x e / (1 + e) below.  The plain form
 // x / (1 + exp(-x)) overflows its exponential below x = -88.7 and returns 0 where the value, down to 2e-37, is still a normal float.
 __device__ __forceinline__ float swishf(float x) {

@@ -33,22 +33,6 @@ __device__ __forceinline__ void load_huff(uint32_t* ac, uint32_t* dc) {
   __syncthreads();
 }
 
-// exclusive scan of one value per thread over the workgroup; returns the workgroup's total through `total`.  sh: kThreads words
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* sh, uint32_t& total) {
-  const int t = threadIdx.x;
-  __syncthreads();      // sh may still be read from the round before
-  sh[t] = v;
-  __syncthreads();
-  for (int o = 1; o < kThreads; o <<= 1) {
-    const uint32_t add = t >= o ? sh[t - o] : 0u;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  total = sh[kThreads - 1];
-  return sh[t] - v;
-}
-
 // ENC: coefficients and AC bit counts to the workspace; REC: the read-back pixels to recon.  vec: w % 8 == 0 and 8-byte aligned bases
 template <bool ENC, bool REC>
 __global__ __launch_bounds__(kThreads) void jpeg_block_kernel(const unsigned char* __restrict__ in, int h, int w, int bw, long nblk, QTab q,
@@ -133,7 +117,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_offsets_kernel(const short* __r
       bits += acbits[static_cast<long>(b) * nblk + blk];
     }
     uint32_t sum;
-    const uint32_t before = block_exclusive_scan(bits, sh, sum);
+    const uint32_t before = block_exclusive_scan<kThreads>(bits, sh, sum);
     if (blk < nblk) bitoff[static_cast<long>(b) * nblk + blk] = carry + before;
     carry += sum;
   }
@@ -192,7 +176,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_count_kernel(const uint32_t* __
   int n;
   const uint32_t ff = stuff_load(stream + static_cast<long>(b) * words, chunk * kStuffChunk + static_cast<long>(threadIdx.x) * kStuffBytes, nbytes, tb, by, n);
   uint32_t sum;
-  block_exclusive_scan(ff, sh, sum);
+  block_exclusive_scan<kThreads>(ff, sh, sum);
   if (threadIdx.x == 0) ffcount[static_cast<long>(b) * chunks + chunk] = sum;
 }
 
@@ -209,7 +193,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_frame_kernel(const uint32_t* __
     const long c = base + threadIdx.x;
     const uint32_t v = c < used ? ffcount[static_cast<long>(b) * chunks + c] : 0u;
     uint32_t sum;
-    const uint32_t before = block_exclusive_scan(v, sh, sum);
+    const uint32_t before = block_exclusive_scan<kThreads>(v, sh, sum);
     if (c < used) ffoff[static_cast<long>(b) * chunks + c] = carry + before;
     carry += sum;
   }
@@ -236,7 +220,7 @@ __global__ __launch_bounds__(kThreads) void jpeg_stuff_kernel(const uint32_t* __
   const long first = chunk * kStuffChunk + static_cast<long>(threadIdx.x) * kStuffBytes;
   const uint32_t ff = stuff_load(stream + static_cast<long>(b) * words, first, nbytes, tb, by, n);
   uint32_t sum;
-  const uint32_t before = block_exclusive_scan(ff, sh, sum);
+  const uint32_t before = block_exclusive_scan<kThreads>(ff, sh, sum);
   // byte i lands at header + i + (FF bytes in front of it) <= header + 2 nbytes - 1, its 00 one further: inside cap
   unsigned char* o = out + static_cast<long>(b) * cap + kHeaderBytes + first + ffoff[static_cast<long>(b) * chunks + chunk] + before;
 #pragma unroll

@@ -24,22 +24,6 @@ namespace pnge {
 
 __constant__ CrcTables kCrcDev = make_crc_tables();
 
-// exclusive scan of one value per thread over the workgroup; the workgroup's total through `total`.  sh: kThreads words
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* sh, uint32_t& total) {
-  const int t = threadIdx.x;
-  __syncthreads();      // sh may still be read from the round before
-  sh[t] = v;
-  __syncthreads();
-  for (int o = 1; o < kThreads; o <<= 1) {
-    const uint32_t add = t >= o ? sh[t - o] : 0u;
-    __syncthreads();
-    sh[t] += add;
-    __syncthreads();
-  }
-  total = sh[kThreads - 1];
-  return sh[t] - v;
-}
-
 __global__ __launch_bounds__(kRowLanes) void png_filter_kernel(const uint8_t* __restrict__ in, int H, int W, long region, uint8_t* __restrict__ filt) {
   const int row = blockIdx.x, b = blockIdx.y, lane = threadIdx.x;
   const uint8_t* rp = in + (static_cast<long>(b) * H + row) * W;
@@ -124,7 +108,7 @@ __global__ __launch_bounds__(kThreads) void png_segment_kernel(const uint8_t* __
     if (tv != kNone) mine += token_bits(tv, s.code);
   }
   uint32_t sum;
-  const uint32_t in_front = block_exclusive_scan(mine, s.scan, sum);      // at most 16384 * 21
+  const uint32_t in_front = block_exclusive_scan<kThreads>(mine, s.scan, sum);      // at most 16384 * 21
   chunkoff[sidx * kThreads + t] = s.header_bits + in_front;
   if (t == 0) info[sidx] = SegInfo{s.header_bits, s.header_bits + sum + (s.code[256] & 15u), s.adler_a % kAdlerMod, s.adler_b % kAdlerMod};
 }
@@ -144,13 +128,13 @@ __global__ __launch_bounds__(kThreads) void png_frame_kernel(const SegInfo* __re
     const long left = l.S - sg * kSegment;
     const uint32_t n = have ? static_cast<uint32_t>(left < kSegment ? left : kSegment) : 0u;
     uint32_t sum, a_sum, c_sum;
-    const uint32_t in_front = block_exclusive_scan(si.total_bits, sh, sum);      // a block has below 2^18.3 bits: the sum fits
+    const uint32_t in_front = block_exclusive_scan<kThreads>(si.total_bits, sh, sum);      // a block has below 2^18.3 bits: the sum fits
     if (have) segoff[static_cast<long>(b) * l.nseg + sg] = carry + in_front;
     carry += sum;
-    const uint32_t a_front = block_exclusive_scan(si.adler_a, sh, a_sum);
+    const uint32_t a_front = block_exclusive_scan<kThreads>(si.adler_a, sh, a_sum);
     const uint32_t a_here = (a_carry + a_front) % kAdlerMod;      // a where the segment starts
     const uint32_t c = static_cast<uint32_t>((si.adler_b + static_cast<unsigned long long>(n) * a_here) % kAdlerMod);
-    (void)block_exclusive_scan(c, sh, c_sum);
+    (void)block_exclusive_scan<kThreads>(c, sh, c_sum);
     b_sum = (b_sum + c_sum) % kAdlerMod;
     a_carry = (a_carry + a_sum) % kAdlerMod;
   }

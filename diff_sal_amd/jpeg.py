@@ -31,13 +31,12 @@ GPU only: CPU tensors raise.
 """
 from __future__ import annotations
 
-import os
 from typing import Sequence
 
 import numpy as np
 import torch
 
-from . import ops
+from . import _image_files, ops
 
 Tensor = torch.Tensor
 
@@ -61,20 +60,9 @@ def quant_table(quality: int = 95) -> np.ndarray:
     return np.clip((np.asarray(_BASE_Q, dtype=np.int64) * s + 50) // 100, 1, 255)
 
 
-def _maps(u8: Tensor, what: str = "u8") -> Tensor:
-    """[B, 1, H, W] or [B, H, W] uint8 GPU tensor -> contiguous [B, H, W]"""
-    if not isinstance(u8, Tensor) or not u8.is_cuda:
-        raise RuntimeError(f"diff_sal_amd jpeg runs on the GPU only (no CPU fallback); {what} is on "
-                           f"{getattr(u8, 'device', type(u8).__name__)}")
-    if u8.dtype != torch.uint8:
-        raise ValueError(f"jpeg: {what} must be uint8 (postprocess.to_uint8 gives it), got {u8.dtype}")
-    if u8.dim() == 4 and u8.shape[1] == 1:
-        u8 = u8[:, 0]
-    if u8.dim() != 3 or u8.numel() == 0:
-        raise ValueError(f"jpeg: {what} must be a non-empty [B, 1, H, W] or [B, H, W], got {tuple(u8.shape)}")
-    if max(u8.shape[1:]) > 65535:
-        raise ValueError(f"jpeg: {tuple(u8.shape[1:])}: a JPEG axis holds at most 65535 pixels")
-    return u8.contiguous()
+def _limit(shape):
+    if max(shape[1:]) > 65535:
+        return f"{shape[1:]}: a JPEG axis holds at most 65535 pixels"
 
 
 def capacity(h: int, w: int) -> int:
@@ -87,13 +75,13 @@ def encode(u8: Tensor, quality: int = 95, return_decoded: bool = False):
     image ``b``'s file being ``data[b, :lengths[b]]`` (the bytes behind it are undefined).  ``return_decoded=True`` adds what a
     decoder reads back from those files, uint8 ``[B, H, W]``.  No host copy, no synchronisation: capturable."""
     q = _quality(quality)
-    data, lengths, recon = ops.jpeg_encode(_maps(u8), q, want_recon=bool(return_decoded))
+    data, lengths, recon = ops.jpeg_encode(_image_files._maps(u8, "jpeg", _limit), q, want_recon=bool(return_decoded))
     return (data, lengths, recon) if return_decoded else (data, lengths)
 
 
 def roundtrip(u8: Tensor, quality: int = 95) -> Tensor:
     """What a decoder reads back from ``encode(u8, quality)``'s files, uint8 ``[B, H, W]``, without making them: one launch."""
-    return ops.jpeg_roundtrip(_maps(u8), _quality(quality))
+    return ops.jpeg_roundtrip(_image_files._maps(u8, "jpeg", _limit), _quality(quality))
 
 
 # ---- decode: the data sets' frame files -> the uint8 frames Pillow returns (csrc/jpeg_decode.hip, include/diffsal.h "JPEG decode") ----
@@ -319,25 +307,12 @@ def decode(files: Sequence, mode: str = "RGB", device=None, strict: bool = True)
     ``(frames, status)`` without synchronising.  The pixels of a file with non-zero status are unspecified (libjpeg's error recovery
     is not reproduced); the other files of the batch are unaffected.  One file without restart markers is one lane's serial work:
     the parallelism is across files and restart intervals."""
-    if mode not in ("RGB", "L"):
-        raise ValueError(f"jpeg.decode: mode must be 'RGB' or 'L', got {mode!r}")
-    dev = torch.device("cuda" if device is None else device)
-    files = files if isinstance(files, Tensor) else list(files)
-    if dev.type != "cuda" or isinstance(files, Tensor) or any(isinstance(f, Tensor) for f in files):
-        raise RuntimeError(f"diff_sal_amd jpeg runs on the GPU only (no CPU fallback); decode takes the files' bytes and a GPU device, got "
-                           f"{'a tensor' if dev.type == 'cuda' else dev}")
-    p = pack(files)
-    buf = torch.from_numpy(p["host"]).to(dev)
-    N, nseg, desc_at, seg_at = p["N"], p["nseg"], p["desc_at"], p["seg_at"]
-    frames, status = ops.jpeg_decode(buf[:desc_at], buf[desc_at:seg_at].view(N, FILE_DTYPE.itemsize), buf[seg_at:].view(torch.int32).view(nseg, 4),
-                                     p["max_file_seg"], N, p["H"], p["W"], p["ncomp"], p["hs"], p["vs"], mode == "L")
-    if not strict:
-        return frames, status
-    bad = status.cpu().numpy()
-    if bad.any():
-        names = "; ".join(f"file {i}: " + ", ".join(t for b, t in STATUS_BITS.items() if bad[i] & b) for i in np.flatnonzero(bad)[:8])
-        raise ValueError(f"jpeg.decode: {int((bad != 0).sum())} of {N} files are damaged inside their scan ({names})")
-    return frames
+    def run(packed, records, tail, p):
+        return ops.jpeg_decode(packed, records, tail.view(torch.int32).view(p["nseg"], 4), p["max_file_seg"], p["N"], p["H"], p["W"],
+                               p["ncomp"], p["hs"], p["vs"], mode == "L")
+
+    return _image_files.decode(files, mode, device, strict, codec="jpeg", pack=pack, file_dtype=FILE_DTYPE, status_bits=STATUS_BITS,
+                               noun="scan", run=run)
 
 
 def pack(files: Sequence) -> dict:
@@ -345,25 +320,19 @@ def pack(files: Sequence) -> dict:
     the files back to back, zero-padded to ``desc_at`` (a multiple of 16) | ``N`` FILE_DTYPE records up to ``seg_at`` | ``nseg``
     int32 rows (file, begin, end, first MCU).  Also returns ``N``, ``nseg``, ``max_file_seg`` and the shared geometry ``H``, ``W``,
     ``ncomp``, ``hs``, ``vs``.  Raises ValueError naming the file's position and the reason."""
-    files = list(files)
-    if not files:
-        raise ValueError("jpeg.decode: an empty list of files")
-    parsed, head = [], None
-    for i, f in enumerate(files):
+    head = [None]      # the header the file before carried
+
+    def parse(f, i):
         if not isinstance(f, (bytes, bytearray, memoryview)):
-            raise ValueError(f"jpeg.decode: file {i}: expected bytes, bytearray or memoryview, got {type(f).__name__}")
-        try:
-            one, head = _parse(f, head)
-            parsed.append(one)
-        except _Refused as e:
-            raise ValueError(f"jpeg.decode: file {i}: {e}") from None
-        a, b = parsed[0], parsed[-1]
-        if any(a[k] != b[k] for k in ("H", "W", "ncomp", "hs", "vs")):
-            raise ValueError(f"jpeg.decode: file {i}: {b['W']} x {b['H']}, {b['ncomp']} components, luma {b['hs']}x{b['vs']} where file 0 has "
-                             f"{a['W']} x {a['H']}, {a['ncomp']}, {a['hs']}x{a['vs']}: the files of a call share size and sampling")
+            raise _Refused(f"expected bytes, bytearray or memoryview, got {type(f).__name__}")
+        one, head[0] = _parse(f, head[0])
+        return one
+
+    files, parsed = _image_files.parse_files(
+        files, "jpeg", parse, _Refused, ("H", "W", "ncomp", "hs", "vs"),
+        lambda a, b: f"{b['W']} x {b['H']}, {b['ncomp']} components, luma {b['hs']}x{b['vs']} where file 0 has "
+                     f"{a['W']} x {a['H']}, {a['ncomp']}, {a['hs']}x{a['vs']}: the files of a call share size and sampling")
     N, g = len(files), parsed[0]
-    if N > 65535:
-        raise ValueError(f"jpeg.decode: {N} files in one call (at most 65535)")
     sizes = np.array([len(memoryview(f).cast("B")) for f in files], dtype=np.int64)
     starts = np.concatenate([[0], np.cumsum(sizes)[:-1]])
     nbytes = (int(sizes.sum()) + 15) & ~15
@@ -390,13 +359,7 @@ def pack(files: Sequence) -> dict:
                 H=g["H"], W=g["W"], ncomp=g["ncomp"], hs=g["hs"], vs=g["vs"])
 
 
-def decode_files(paths: Sequence, mode: str = "RGB", device=None, strict: bool = True):
-    """``decode`` of the files at ``paths``."""
-    data = []
-    for p in paths:
-        with open(p, "rb") as f:
-            data.append(f.read())
-    return decode(data, mode=mode, device=device, strict=strict)
+decode_files = _image_files.file_decoder(decode)
 
 
 def save_predictions(pred: Tensor, video_ids: Sequence, frame_ids: Sequence, root: str, quality: int = 95):
@@ -408,19 +371,6 @@ def save_predictions(pred: Tensor, video_ids: Sequence, frame_ids: Sequence, roo
 
     q = _quality(quality)
     u8 = postprocess.to_uint8(pred)
-    frame_ids = [int(f) for f in (frame_ids.reshape(-1).tolist() if isinstance(frame_ids, Tensor) else frame_ids)]
-    video_ids = list(video_ids)
-    if not (u8.shape[0] == len(video_ids) == len(frame_ids)):
-        raise ValueError(f"jpeg: {u8.shape[0]} predictions, {len(video_ids)} video ids, {len(frame_ids)} frame ids")
-    data, lengths = encode(u8, q)
-    n = lengths.cpu().numpy()
-    host = data[:, :int(n.max())].cpu().numpy()      # the rows cut at the longest file: a few per cent of their capacity
-    paths = []
-    for row, length, vid, fid in zip(host, n, video_ids, frame_ids):
-        d = os.path.join(root, str(vid))
-        os.makedirs(d, exist_ok=True)
-        path = os.path.join(d, f"pred_sal_{fid:06d}.jpg")
-        with open(path, "wb") as f:
-            f.write(row[:int(length)].tobytes())
-        paths.append(path)
-    return paths
+    video_ids, frame_ids = _image_files.checked_ids(u8.shape[0], video_ids, frame_ids, "jpeg")
+    rows, lengths = _image_files.host_rows(*encode(u8, q))
+    return _image_files.write_files(rows, lengths, _image_files.prediction_paths(root, video_ids, frame_ids, "pred_sal_{:06d}.jpg"))

@@ -78,6 +78,11 @@ def _nb(*ts) -> float:
     return float(sum(t.numel() * t.element_size() for t in ts if t is not None))
 
 
+def _ws_f64(nbytes: int, device) -> Tensor:
+    """a byte workspace of ``nbytes`` (16 at the least, so that it always has an address), typed fp64 for the kernels' partial sums"""
+    return torch.empty((max(nbytes, 16) // 8,), device=device, dtype=torch.float64)
+
+
 GEMM_PRECISIONS = {"fp32": _lib.PREC_FP32, "bf16x3": _lib.PREC_BF16X3}
 
 # The arithmetic of the implicit-GEMM kernel is a PER-CALL field of diffsal_conv_desc (the library holds no mode).  On
@@ -1213,7 +1218,7 @@ def colsum(dy: Tensor, seg_rows: Optional[int] = None) -> Tensor:
     seg = M if seg_rows is None else seg_rows
     out = torch.empty((M // seg, Cc), device=dy.device, dtype=torch.float32)
     nws = (M // seg) * 512 * Cc * 8
-    ws = torch.empty((nws // 8,), device=dy.device, dtype=torch.float64)
+    ws = _ws_f64(nws, dy.device)
     _lib.check(lib.diffsal_colsum(_p(dy), _p(out), M, Cc, seg, ws.data_ptr(), nws, _stream()), "colsum")
     return out
 
@@ -1881,7 +1886,7 @@ def saliency_metrics(pred: Tensor, gt: Tensor, keep_ws: bool = False):
     n = pred.numel() // B
     p, g = pred.contiguous().float(), gt.contiguous().float()
     nws = lib.diffsal_saliency_metrics_ws_bytes(B)
-    ws = torch.empty((nws // 8,), device=pred.device, dtype=torch.float64)
+    ws = _ws_f64(nws, pred.device)
     per = torch.empty((B, 4), device=pred.device, dtype=torch.float32)
     mean = torch.empty((4,), device=pred.device, dtype=torch.float32)
     with _prof("metrics", 0.0, 2 * _nb(p, g)):
@@ -1934,7 +1939,7 @@ def eval_metrics(pred: Tensor, fix: Optional[Tensor], gt: Optional[Tensor], othe
         raise ValueError(f"eval_metrics: {ids.numel()} ids for {B} images")
     sweeps = bool(terms & (EVAL_BORJI | EVAL_SAUC))
     nws = lib.diffsal_eval_metrics_ws_bytes(B, n, int(terms), int(n_rep) if sweeps else 0)
-    ws = torch.empty((max(nws, 16) // 8,), device=pred.device, dtype=torch.float64)
+    ws = _ws_f64(nws, pred.device)
     out = torch.full((6, B), float("nan"), device=pred.device, dtype=torch.float64)
     with _prof("metrics", 0.0, _nb(pred, fix, gt, other)):
         _lib.check(lib.diffsal_eval_metrics(_p(pred), _u8(fix, "fix", pred.shape), _p(gt), _u8(other, "other", pred.shape), B, n,
@@ -1956,7 +1961,7 @@ def map_to_u8(pred: Tensor, *, want_u8: bool = True, want_float: bool = False):
     u8 = torch.empty((B, n), device=pred.device, dtype=torch.uint8) if want_u8 else None
     f = torch.empty((B, n), device=pred.device, dtype=torch.float32) if want_float else None
     nws = lib.diffsal_map_to_u8_ws_bytes(B, n)
-    ws = torch.empty((max(nws, 16) // 8,), device=pred.device, dtype=torch.float64)
+    ws = _ws_f64(nws, pred.device)
     with _prof("metrics", 0.0, 2 * _nb(pred) + _nb(u8, f)):
         _lib.check(lib.diffsal_map_to_u8(_p(pred), B, n, None if u8 is None else u8.data_ptr(), _p(f), ws.data_ptr(), nws, _stream()),
                    "map_to_u8")
@@ -1983,17 +1988,28 @@ def map_resize(x: Tensor, H: int, W: int, *, order: int = 3, clip: bool = True, 
     H, W, order, clip = int(H), int(W), int(order), 1 if clip else 0
     out = torch.empty((B, H, W) if H > 0 and W > 0 else (0,), device=x.device, dtype=torch.float64 if out_f64 else torch.float32)
     nws = lib.diffsal_map_resize_ws_bytes(B, h, w, order, clip)
-    ws = torch.empty((max(nws, 16) // 8,), device=x.device, dtype=torch.float64)
+    ws = _ws_f64(nws, x.device)
     with _prof("metrics", 0.0, _nb(x, out)):
         _lib.check(lib.diffsal_map_resize(_p(x), B, h, w, H, W, order, clip, 1 if out_f64 else 0, out.data_ptr(), ws.data_ptr(), nws,
                                           _stream()), "map_resize")
     return out
 
 
-def _jpeg_u8(u8: Tensor, what: str):
+def _u8_maps(u8: Tensor, what: str):
     if not u8.is_cuda or u8.dtype != torch.uint8 or not u8.is_contiguous() or u8.dim() != 3 or u8.numel() == 0:
         raise ValueError(f"{what}: expected a non-empty contiguous uint8 GPU tensor [B, h, w], got {u8.dtype} {u8.device} {tuple(u8.shape)}")
     return u8.shape
+
+
+def _gpu_tensor(t: Tensor, dtype, what: str) -> None:
+    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"{what} must be a contiguous {str(dtype)[6:]} GPU tensor, got {t.dtype} {t.device}")
+
+
+def _decode_buffers(N: int, H: int, W: int, mode_l: bool, nws: int, device):
+    """what both file decodes write: (frames uint8 [N, H, W] or [N, H, W, 3], status int32 [N], workspace)"""
+    return (torch.empty((N, H, W) if mode_l else (N, H, W, 3), device=device, dtype=torch.uint8),
+            torch.empty((N,), device=device, dtype=torch.int32), _ws_f64(nws, device))
 
 
 def jpeg_capacity(h: int, w: int) -> int:
@@ -2008,13 +2024,13 @@ def jpeg_encode(u8: Tensor, quality: int = 95, *, want_recon: bool = False):
     """``diffsal_jpeg_encode`` (include/diffsal.h, "JPEG export") on u8 [B, h, w] uint8 -> (data [B, cap] uint8, lengths [B] int32,
     recon [B, h, w] uint8 or None): image b's file is ``data[b, :lengths[b]]``."""
     lib = _lib.load()
-    B, h, w = _jpeg_u8(u8, "jpeg_encode")
+    B, h, w = _u8_maps(u8, "jpeg_encode")
     cap = jpeg_capacity(h, w)
     data = torch.empty((B, cap), device=u8.device, dtype=torch.uint8)
     lengths = torch.empty((B,), device=u8.device, dtype=torch.int32)
     recon = torch.empty((B, h, w), device=u8.device, dtype=torch.uint8) if want_recon else None
     nws = lib.diffsal_jpeg_encode_ws_bytes(B, h, w)
-    ws = torch.empty((max(nws, 16) // 8,), device=u8.device, dtype=torch.float64)
+    ws = _ws_f64(nws, u8.device)
     with _prof("metrics", 0.0, _nb(u8, recon) + 2 * nws):
         _lib.check(lib.diffsal_jpeg_encode(u8.data_ptr(), B, h, w, int(quality), data.data_ptr(), cap, lengths.data_ptr(),
                                            None if recon is None else recon.data_ptr(), ws.data_ptr(), nws, _stream()), "jpeg_encode")
@@ -2024,7 +2040,7 @@ def jpeg_encode(u8: Tensor, quality: int = 95, *, want_recon: bool = False):
 def jpeg_roundtrip(u8: Tensor, quality: int = 95) -> Tensor:
     """``diffsal_jpeg_roundtrip``: the pixels a libjpeg decoder reads back from the file of each image, uint8 [B, h, w], one launch."""
     lib = _lib.load()
-    B, h, w = _jpeg_u8(u8, "jpeg_roundtrip")
+    B, h, w = _u8_maps(u8, "jpeg_roundtrip")
     recon = torch.empty((B, h, w), device=u8.device, dtype=torch.uint8)
     with _prof("metrics", 0.0, _nb(u8, recon)):
         _lib.check(lib.diffsal_jpeg_roundtrip(u8.data_ptr(), B, h, w, int(quality), recon.data_ptr(), _stream()), "jpeg_roundtrip")
@@ -2037,16 +2053,13 @@ def jpeg_decode(packed: Tensor, files: Tensor, segments: Tensor, max_file_seg: i
     segments int32 [nseg, 4] -> (frames uint8 [N, H, W, 3] or [N, H, W], status int32 [N])."""
     lib = _lib.load()
     for t, dt, what in ((packed, torch.uint8, "packed"), (files, torch.uint8, "files"), (segments, torch.int32, "segments")):
-        if not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-            raise ValueError(f"jpeg_decode: {what} must be a contiguous {dt} GPU tensor, got {t.dtype} {t.device}")
+        _gpu_tensor(t, dt, f"jpeg_decode: {what}")
     if files.shape != (N, 1392) or segments.dim() != 2 or segments.shape[1] != 4:
         raise ValueError(f"jpeg_decode: files {tuple(files.shape)} (want [{N}, 1392]), segments {tuple(segments.shape)} (want [nseg, 4])")
     nws = lib.diffsal_jpeg_decode_ws_bytes(N, H, W, ncomp, hs, vs)
     if nws == 0:
         raise ValueError(f"jpeg_decode: N={N}, {H} x {W}, {ncomp} components, luma sampling {hs} x {vs}: outside what the decode takes")
-    out = torch.empty((N, H, W) if mode_l else (N, H, W, 3), device=packed.device, dtype=torch.uint8)
-    status = torch.empty((N,), device=packed.device, dtype=torch.int32)
-    ws = torch.empty((nws // 8,), device=packed.device, dtype=torch.float64)
+    out, status, ws = _decode_buffers(N, H, W, mode_l, nws, packed.device)
     with _prof("metrics", 0.0, _nb(packed, out) + 2 * nws):
         _lib.check(lib.diffsal_jpeg_decode(packed.data_ptr(), packed.numel(), files.data_ptr(), segments.data_ptr(), segments.shape[0],
                                            int(max_file_seg), N, H, W, ncomp, hs, vs, 1 if mode_l else 0, out.data_ptr(), status.data_ptr(),
@@ -2059,16 +2072,13 @@ def png_decode(packed: Tensor, files: Tensor, N: int, H: int, W: int, color_type
     (frames uint8 [N, H, W, 3] or [N, H, W], status int32 [N])."""
     lib = _lib.load()
     for t, what in ((packed, "packed"), (files, "files")):
-        if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
-            raise ValueError(f"png_decode: {what} must be a contiguous uint8 GPU tensor, got {t.dtype} {t.device}")
+        _gpu_tensor(t, torch.uint8, f"png_decode: {what}")
     if files.shape != (N, 784):
         raise ValueError(f"png_decode: files {tuple(files.shape)} (want [{N}, 784])")
     nws = lib.diffsal_png_decode_ws_bytes(N, H, W, color_type, bit_depth)
     if nws == 0:
         raise ValueError(f"png_decode: N={N}, {H} x {W}, colour type {color_type} at {bit_depth} bits: outside what the decode takes")
-    out = torch.empty((N, H, W) if mode_l else (N, H, W, 3), device=packed.device, dtype=torch.uint8)
-    status = torch.empty((N,), device=packed.device, dtype=torch.int32)
-    ws = torch.empty((nws // 8,), device=packed.device, dtype=torch.float64)
+    out, status, ws = _decode_buffers(N, H, W, mode_l, nws, packed.device)
     with _prof("metrics", 0.0, _nb(packed, out) + 2 * nws):
         _lib.check(lib.diffsal_png_decode(packed.data_ptr(), packed.numel(), files.data_ptr(), N, H, W, color_type, bit_depth,
                                           1 if mode_l else 0, out.data_ptr(), status.data_ptr(), ws.data_ptr(), nws, _stream()), "png_decode")
@@ -2087,16 +2097,14 @@ def png_encode(u8: Tensor):
     """``diffsal_png_encode`` (include/diffsal.h, "PNG export") on u8 [B, h, w] uint8 -> (data [B, cap] uint8, lengths [B] int32):
     image b's file is ``data[b, :lengths[b]]``."""
     lib = _lib.load()
-    if not u8.is_cuda or u8.dtype != torch.uint8 or not u8.is_contiguous() or u8.dim() != 3 or u8.numel() == 0:
-        raise ValueError(f"png_encode: expected a non-empty contiguous uint8 GPU tensor [B, h, w], got {u8.dtype} {u8.device} {tuple(u8.shape)}")
-    B, h, w = u8.shape
+    B, h, w = _u8_maps(u8, "png_encode")
     nws = lib.diffsal_png_encode_ws_bytes(B, h, w)
     if nws == 0:
         raise ValueError(f"png_encode: B={B}, {h} x {w}: outside what the export takes (B 1..65535, height 1..65535, width 1..8192)")
     cap = png_capacity(h, w)
     data = torch.empty((B, cap), device=u8.device, dtype=torch.uint8)
     lengths = torch.empty((B,), device=u8.device, dtype=torch.int32)
-    ws = torch.empty((nws // 8,), device=u8.device, dtype=torch.float64)
+    ws = _ws_f64(nws, u8.device)
     with _prof("metrics", 0.0, _nb(u8, data) + 2 * nws):
         _lib.check(lib.diffsal_png_encode(u8.data_ptr(), B, h, w, data.data_ptr(), cap, lengths.data_ptr(), ws.data_ptr(), nws, _stream()),
                    "png_encode")

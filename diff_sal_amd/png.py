@@ -21,13 +21,12 @@ GPU only: CPU tensors raise.
 """
 from __future__ import annotations
 
-import os
 from typing import Sequence
 
 import numpy as np
 import torch
 
-from . import ops
+from . import _image_files, ops
 
 Tensor = torch.Tensor
 
@@ -141,22 +140,11 @@ def pack(files: Sequence) -> dict:
     files' zlib streams, each starting at a multiple of 16 and zero-padded, up to ``desc_at`` | ``N`` FILE_DTYPE records.  Also
     returns ``N`` and the shared geometry ``H``, ``W``, ``color_type``, ``bit_depth``.  Raises ValueError naming the file's position
     and the reason."""
-    files = list(files)
-    if not files:
-        raise ValueError("png.decode: an empty list of files")
-    parsed = []
-    for i, f in enumerate(files):
-        try:
-            parsed.append(_parse(_bytes_of(f, i)))
-        except _Refused as e:
-            raise ValueError(f"png.decode: file {i}: {e}") from None
-        a, b = parsed[0], parsed[-1]
-        if any(a[k] != b[k] for k in ("H", "W", "color_type", "bit_depth")):
-            raise ValueError(f"png.decode: file {i}: {b['W']} x {b['H']}, colour type {b['color_type']}, {b['bit_depth']} bits where file 0 has "
-                             f"{a['W']} x {a['H']}, {a['color_type']}, {a['bit_depth']}: the files of a call share size, colour type and depth")
+    files, parsed = _image_files.parse_files(
+        files, "png", lambda f, i: _parse(_bytes_of(f, i)), _Refused, ("H", "W", "color_type", "bit_depth"),
+        lambda a, b: f"{b['W']} x {b['H']}, colour type {b['color_type']}, {b['bit_depth']} bits where file 0 has "
+                     f"{a['W']} x {a['H']}, {a['color_type']}, {a['bit_depth']}: the files of a call share size, colour type and depth")
     N, g = len(files), parsed[0]
-    if N > 65535:
-        raise ValueError(f"png.decode: {N} files in one call (at most 65535)")
     sizes = np.array([p["stream"].size for p in parsed], dtype=np.int64)
     padded = (sizes + 15) & ~15
     starts = np.concatenate([[0], np.cumsum(padded)[:-1]])
@@ -190,51 +178,20 @@ def decode(files: Sequence, mode: str = "RGB", device=None, strict: bool = True)
     64); this is stricter than Pillow, which returns such a file silently with the missing rows left blank.  A stream that carries
     more (128) still delivers its pixels.  With any other bit the file's pixels are unspecified; the other files of the batch are
     unaffected.  One file is one wave's work: the parallelism is across files."""
-    if mode not in ("RGB", "L"):
-        raise ValueError(f"png.decode: mode must be 'RGB' or 'L', got {mode!r}")
-    dev = torch.device("cuda" if device is None else device)
-    files = files if isinstance(files, Tensor) else list(files)
-    if dev.type != "cuda" or isinstance(files, Tensor) or any(isinstance(f, Tensor) for f in files):
-        raise RuntimeError(f"diff_sal_amd png runs on the GPU only (no CPU fallback); decode takes the files' bytes and a GPU device, got "
-                           f"{'a tensor' if dev.type == 'cuda' else dev}")
-    p = pack(files)
-    buf = torch.from_numpy(p["host"]).to(dev)
-    N, desc_at = p["N"], p["desc_at"]
-    frames, status = ops.png_decode(buf[:desc_at], buf[desc_at:].view(N, FILE_DTYPE.itemsize), N, p["H"], p["W"], p["color_type"], p["bit_depth"],
-                                    mode == "L")
-    if not strict:
-        return frames, status
-    bad = status.cpu().numpy()
-    if bad.any():
-        names = "; ".join(f"file {i}: " + ", ".join(t for b, t in STATUS_BITS.items() if bad[i] & b) for i in np.flatnonzero(bad)[:8])
-        raise ValueError(f"png.decode: {int((bad != 0).sum())} of {N} files are damaged inside their stream ({names})")
-    return frames
+    def run(packed, records, tail, p):
+        return ops.png_decode(packed, records, p["N"], p["H"], p["W"], p["color_type"], p["bit_depth"], mode == "L")
+
+    return _image_files.decode(files, mode, device, strict, codec="png", pack=pack, file_dtype=FILE_DTYPE, status_bits=STATUS_BITS,
+                               noun="stream", run=run)
 
 
-def decode_files(paths: Sequence, mode: str = "RGB", device=None, strict: bool = True):
-    """``decode`` of the files at ``paths``."""
-    data = []
-    for p in paths:
-        with open(p, "rb") as f:
-            data.append(f.read())
-    return decode(data, mode=mode, device=device, strict=strict)
+decode_files = _image_files.file_decoder(decode)
 
 
 # ---- export: 8-bit maps -> complete .png files (csrc/png_encode.hip, include/diffsal.h "PNG export") ----
-def _maps(u8: Tensor, what: str = "u8") -> Tensor:
-    """[B, 1, H, W] or [B, H, W] uint8 GPU tensor -> contiguous [B, H, W]"""
-    if not isinstance(u8, Tensor) or not u8.is_cuda:
-        raise RuntimeError(f"diff_sal_amd png runs on the GPU only (no CPU fallback); {what} is on "
-                           f"{getattr(u8, 'device', type(u8).__name__)}")
-    if u8.dtype != torch.uint8:
-        raise ValueError(f"png: {what} must be uint8 (postprocess.to_uint8 gives it), got {u8.dtype}")
-    if u8.dim() == 4 and u8.shape[1] == 1:
-        u8 = u8[:, 0]
-    if u8.dim() != 3 or u8.numel() == 0:
-        raise ValueError(f"png: {what} must be a non-empty [B, 1, H, W] or [B, H, W], got {tuple(u8.shape)}")
-    if u8.shape[0] > 65535 or u8.shape[1] > 65535 or u8.shape[2] > MAX_WIDTH:
-        raise ValueError(f"png: {tuple(u8.shape)}: at most 65535 maps of at most 65535 rows and {MAX_WIDTH} columns (what decode takes)")
-    return u8.contiguous()
+def _limit(shape):
+    if shape[0] > 65535 or shape[1] > 65535 or shape[2] > MAX_WIDTH:
+        return f"{shape}: at most 65535 maps of at most 65535 rows and {MAX_WIDTH} columns (what decode takes)"
 
 
 def capacity(h: int, w: int) -> int:
@@ -246,7 +203,7 @@ def encode(u8: Tensor):
     """The ``.png`` file of every map of ``u8`` (uint8 ``[B, H, W]`` or ``[B, 1, H, W]``): ``(data uint8 [B, cap], lengths int32
     [B])`` on the device, map ``b``'s file being ``data[b, :lengths[b]]`` (zeros behind it).  8-bit greyscale, one IDAT; a decoder
     reads back exactly ``u8``.  No host copy, no synchronisation: capturable."""
-    return ops.png_encode(_maps(u8))
+    return ops.png_encode(_image_files._maps(u8, "png", _limit))
 
 
 def save_predictions(pred: Tensor, video_ids: Sequence, frame_ids: Sequence, root: str):
@@ -257,19 +214,6 @@ def save_predictions(pred: Tensor, video_ids: Sequence, frame_ids: Sequence, roo
     from . import postprocess
 
     u8 = postprocess.to_uint8(pred)
-    frame_ids = [int(f) for f in (frame_ids.reshape(-1).tolist() if isinstance(frame_ids, Tensor) else frame_ids)]
-    video_ids = list(video_ids)
-    if not (u8.shape[0] == len(video_ids) == len(frame_ids)):
-        raise ValueError(f"postprocess: {u8.shape[0]} predictions, {len(video_ids)} video ids, {len(frame_ids)} frame ids")
-    data, lengths = encode(u8)
-    n = lengths.cpu().numpy()
-    host = data[:, :int(n.max())].cpu().numpy()      # the rows cut at the longest file: a few per cent of their capacity
-    paths = []
-    for row, length, vid, fid in zip(host, n, video_ids, frame_ids):
-        d = os.path.join(root, str(vid))
-        os.makedirs(d, exist_ok=True)
-        path = os.path.join(d, f"{fid}.png")
-        with open(path, "wb") as f:
-            f.write(row[:int(length)].tobytes())
-        paths.append(path)
-    return paths
+    video_ids, frame_ids = _image_files.checked_ids(u8.shape[0], video_ids, frame_ids, "png")
+    rows, lengths = _image_files.host_rows(*encode(u8))
+    return _image_files.write_files(rows, lengths, _image_files.prediction_paths(root, video_ids, frame_ids, "{}.png"))

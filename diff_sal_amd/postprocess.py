@@ -31,6 +31,7 @@ from typing import Dict, Optional, Sequence, Tuple
 
 import torch
 
+from . import _image_files
 from . import eval_metrics as _em
 from . import ops
 
@@ -155,16 +156,9 @@ def save_predictions(pred: Tensor, video_ids: Sequence, frame_ids: Sequence, roo
     from PIL import Image
 
     u8 = to_uint8(pred)
-    frame_ids = [int(f) for f in (frame_ids.reshape(-1).tolist() if isinstance(frame_ids, Tensor) else frame_ids)]
-    video_ids = list(video_ids)
-    if not (u8.shape[0] == len(video_ids) == len(frame_ids)):
-        raise ValueError(f"postprocess: {u8.shape[0]} predictions, {len(video_ids)} video ids, {len(frame_ids)} frame ids")
-    host = u8.cpu().numpy()
-    paths = []
-    for img, vid, fid in zip(host, video_ids, frame_ids):
-        d = os.path.join(root, str(vid))
-        os.makedirs(d, exist_ok=True)
-        path = os.path.join(d, f"{fid}.png")
+    video_ids, frame_ids = _image_files.checked_ids(u8.shape[0], video_ids, frame_ids, "postprocess")
+    paths = _image_files.prediction_paths(root, video_ids, frame_ids, "{}.png")
+    for img, path in zip(u8.cpu().numpy(), paths):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
         Image.fromarray(img).save(path, format="PNG")      # 2-D uint8: mode "L"
-        paths.append(path)
     return paths
