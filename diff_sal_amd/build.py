@@ -13,7 +13,7 @@ SHARED_HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "gemm_famil
 # headers only one translation unit includes: a change rebuilds that unit alone
 OWN_HEADERS = {"jpeg_export.hip": ["jpeg_core.h"], "jpeg_decode.hip": ["jpeg_core.h", "jpeg_decode_core.h"],
                "png_decode.hip": ["png_decode_core.h"], "png_encode.hip": ["png_encode_core.h"],
-               "audio_input.hip": ["audio_resample.h"]}
+               "audio_input.hip": ["audio_resample.h"], "postprocess.hip": ["postprocess_gauss.h"]}
 
 
 def _hipcc():

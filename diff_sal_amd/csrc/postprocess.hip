@@ -14,9 +14,14 @@
 // summed from the far taps inwards in Horner form: no serial chain along a line, a fixed order per coefficient.  A workgroup
 // first copies its stretch of the line, extended by 34 mirrored samples on both sides (the index folded by modulo: the period
 // 2(n - 1) may be shorter than 34), to LDS; the tap loop then has no index arithmetic.
+//   map_resize_aa  minmax (clip only) on the UNFILTERED source; gauss_y, gauss_x (each only where its axis shrinks): the
+//                  anti-aliasing Gaussian, fp32 -> fp32 through fp64 sums (csrc/postprocess_gauss.h); then coef_x, coef_y, interp
+//                  as above, reading the filtered map
+//   map_gauss      gauss_y, gauss_x alone
 // min / max are exact in any order, every sum has a fixed order: two calls give the same bits.  No floating-point atomics, no
 // allocation, no synchronisation; what a launch reads from an earlier one it reads behind a kernel boundary.
 #include "common.h"
+#include "postprocess_gauss.h"
 
 namespace diffsal {
 
@@ -31,12 +36,13 @@ struct PpWs {
   float* part;       // [B][C][2] min / max per chunk (clip)
   double* t1;        // [B][h][w] prefiltered along x (order 3)
   double* coef;      // [B][h][w] spline coefficients (order 3)
+  float* g[2];       // `gauss` arrays [B][h][w]: the map after the Gaussian pass along y, then along x
   size_t bytes;
 };
 
 static inline long pp_chunks(long n) { return (n + PP_CHUNK - 1) / PP_CHUNK; }
 
-static PpWs pp_layout(void* base, int B, long n, bool part, bool cubic) {
+static PpWs pp_layout(void* base, int B, long n, bool part, bool cubic, int gauss = 0) {
   PpWs w;
   char* p = static_cast<char*>(base);
   size_t off = 0;
@@ -44,17 +50,13 @@ static PpWs pp_layout(void* base, int B, long n, bool part, bool cubic) {
   w.part = part ? reinterpret_cast<float*>(take(static_cast<size_t>(B) * pp_chunks(n) * 2 * 4)) : nullptr;
   w.t1 = cubic ? reinterpret_cast<double*>(take(static_cast<size_t>(B) * n * 8)) : nullptr;
   w.coef = cubic ? reinterpret_cast<double*>(take(static_cast<size_t>(B) * n * 8)) : nullptr;
+  for (int i = 0; i < 2; ++i) w.g[i] = i < gauss ? reinterpret_cast<float*>(take(static_cast<size_t>(B) * n * 4)) : nullptr;
   w.bytes = off;
   return w;
 }
 
-// whole-sample mirror extension: period 2(n - 1), n >= 2; any integer j
-__device__ __forceinline__ int pp_mirror(int j, int n) {
-  const int p = 2 * (n - 1);
-  j %= p;
-  if (j < 0) j += p;
-  return j > n - 1 ? p - j : j;
-}
+// whole-sample mirror extension: period 2(n - 1), n >= 2; any integer j (one definition, shared with the host check)
+__device__ __forceinline__ int pp_mirror(int j, int n) { return gauss::mirror(j, n); }
 
 // min and max over the workgroup (blockDim.x a multiple of 64, at most 256); sh holds 8 floats
 __device__ __forceinline__ void pp_block_minmax(float& mn, float& mx, float* sh) {
@@ -194,6 +196,51 @@ __global__ __launch_bounds__(256) void pp_coef_y_kernel(const double* __restrict
   }
 }
 
+// The anti-aliasing Gaussian's weights of one axis, centre first, passed by value as a kernel argument: no device allocation, no
+// copy, capturable.  Entries above the radius are zero.
+struct PpGaussW {
+  double g[gauss::kMaxRadius + 1];
+};
+
+// Gaussian along x: workgroup = kSeg consecutive samples of one row; the row segment with r mirrored samples on both sides in LDS
+__global__ __launch_bounds__(gauss::kSeg) void pp_gauss_x_kernel(const float* __restrict__ in, float* __restrict__ out, int h, int w, int r,
+                                                            const PpGaussW wt) {
+  __shared__ float ext[gauss::kSeg + 2 * gauss::kMaxRadius];
+  __shared__ double g[gauss::kMaxRadius + 1];
+  const int x0 = blockIdx.x * gauss::kSeg, y = blockIdx.y, b = blockIdx.z;
+  const long ro = (static_cast<long>(b) * h + y) * w;
+  const float* row = in + ro;
+  for (int j = threadIdx.x; j < gauss::kSeg + 2 * r; j += gauss::kSeg) ext[j] = row[gauss::mirror(x0 - r + j, w)];
+  if (static_cast<int>(threadIdx.x) <= r) g[threadIdx.x] = wt.g[threadIdx.x];
+  __syncthreads();
+  const int x = x0 + threadIdx.x;
+  if (x >= w) return;
+  out[ro + x] = gauss::sample(ext + threadIdx.x + r, 1, r, g);
+}
+
+// Gaussian along y: workgroup = a tile of kTX columns x kTY rows; kTY + 2 r rows of input in LDS (at most 40 960 bytes);
+// 256 threads = 64 columns x 4 row groups
+__global__ __launch_bounds__(256) void pp_gauss_y_kernel(const float* __restrict__ in, float* __restrict__ out, int h, int w, int r,
+                                                         const PpGaussW wt) {
+  __shared__ float tile[gauss::kTY + 2 * gauss::kMaxRadius][gauss::kTX];
+  __shared__ double g[gauss::kMaxRadius + 1];
+  const int tx = threadIdx.x & 63, tg = threadIdx.x >> 6;
+  const int x = blockIdx.x * gauss::kTX + tx, y0 = blockIdx.y * gauss::kTY, b = blockIdx.z;
+  const long io = static_cast<long>(b) * h * w;
+  for (int rr = tg; rr < gauss::kTY + 2 * r; rr += 4) {
+    const int yy = gauss::mirror(y0 - r + rr, h);
+    tile[rr][tx] = x < w ? in[io + static_cast<long>(yy) * w + x] : 0.0f;
+  }
+  if (static_cast<int>(threadIdx.x) <= r) g[threadIdx.x] = wt.g[threadIdx.x];
+  __syncthreads();
+  if (x >= w) return;
+  for (int ly = tg; ly < gauss::kTY; ly += 4) {
+    const int y = y0 + ly;
+    if (y >= h) break;
+    out[io + static_cast<long>(y) * w + x] = gauss::sample(&tile[ly + r][tx], gauss::kTX, r, g);
+  }
+}
+
 // six times the cubic B-spline: 4 - 6 t^2 + 3 |t|^3 for |t| < 1, (2 - |t|)^3 for |t| < 2, else 0; the two factors 1 / 6 of a
 // pixel's separable sum are taken out of it as one division by 36
 __device__ __forceinline__ double pp_beta3x6(double t) {
@@ -313,18 +360,14 @@ extern "C" size_t diffsal_map_resize_ws_bytes(int B, int h, int w, int order, in
   return pp_layout(nullptr, B, static_cast<long>(h) * w, clip != 0, order == 3).bytes;
 }
 
-extern "C" int diffsal_map_resize(const float* in, int B, int h, int w, int H, int W, int order, int clip, int out_f64, void* out,
-                                  void* ws, size_t ws_bytes, diffsal_stream_t stream) {
-  int rc = pp_resize_args(B, h, w, H, W, order, clip, out_f64);
-  if (rc) return rc;
-  const bool cubic = order == 3;
-  DS_REQUIRE(in && out && (ws || !(clip || cubic)), DIFFSAL_E_ARG, "map_resize: null argument");
+// The launches of a resize behind the argument checks: the clip's range is `range`'s (the map as it came), the spline reads `in`
+// (the same map, or the one the anti-aliasing Gaussian made of it)
+static int pp_resize_launches(const float* range, const float* in, int B, int h, int w, int H, int W, bool cubic, int clip, int out_f64,
+                              void* out, const PpWs& ww, hipStream_t s) {
+  int rc;
   const long n = static_cast<long>(h) * w;
-  const PpWs ww = pp_layout(ws, B, n, clip != 0, cubic);
-  DS_REQUIRE(ww.bytes == 0 || (ws_bytes >= ww.bytes && aligned16(ws)), DIFFSAL_E_ARG, "map_resize: workspace too small or misaligned");
-  hipStream_t s = static_cast<hipStream_t>(stream);
   const long C = pp_chunks(n);
-  if (clip && (rc = pp_minmax_launch(in, ww.part, B, n, s, "map_resize(minmax)"))) return rc;
+  if (clip && (rc = pp_minmax_launch(range, ww.part, B, n, s, "map_resize(minmax)"))) return rc;
   if (cubic) {
     hipLaunchKernelGGL(pp_coef_x_kernel, dim3((w + PP_SEG - 1) / PP_SEG, h, B), dim3(PP_SEG), 0, s, in, ww.t1, h, w);
     if ((rc = check_launch("map_resize(coef_x)"))) return rc;
@@ -343,4 +386,104 @@ extern "C" int diffsal_map_resize(const float* in, int B, int h, int w, int H, i
   else
     hipLaunchKernelGGL((pp_interp_kernel<1, float, float>), grid, dim3(256), 0, s, in, part, static_cast<float*>(out), h, w, H, W, ry, rx, C);
   return check_launch("map_resize(interp)");
+}
+
+extern "C" int diffsal_map_resize(const float* in, int B, int h, int w, int H, int W, int order, int clip, int out_f64, void* out,
+                                  void* ws, size_t ws_bytes, diffsal_stream_t stream) {
+  int rc = pp_resize_args(B, h, w, H, W, order, clip, out_f64);
+  if (rc) return rc;
+  const bool cubic = order == 3;
+  DS_REQUIRE(in && out && (ws || !(clip || cubic)), DIFFSAL_E_ARG, "map_resize: null argument");
+  const PpWs ww = pp_layout(ws, B, static_cast<long>(h) * w, clip != 0, cubic);
+  DS_REQUIRE(ww.bytes == 0 || (ws_bytes >= ww.bytes && aligned16(ws)), DIFFSAL_E_ARG, "map_resize: workspace too small or misaligned");
+  return pp_resize_launches(in, in, B, h, w, H, W, cubic, clip, out_f64, out, ww, static_cast<hipStream_t>(stream));
+}
+
+// ---- the anti-aliasing Gaussian in front of a downscale ----
+static int pp_gauss_args(const char* what, int B, int h, int w, const double* wy, int ry, const double* wx, int rx) {
+  DS_REQUIRE(B > 0 && B <= 65535, DIFFSAL_E_SHAPE, "%s: B=%d (1..65535)", what, B);
+  DS_REQUIRE(h >= 2 && w >= 2 && h <= PP_MAX_DIM && w <= PP_MAX_DIM, DIFFSAL_E_SHAPE,
+             "%s: source %d x %d: the mirror boundary needs at least 2 samples per axis, an axis has at most %d", what, h, w, PP_MAX_DIM);
+  DS_REQUIRE(ry >= 0 && rx >= 0, DIFFSAL_E_ARG, "%s: negative radius (%d, %d)", what, ry, rx);
+  DS_REQUIRE(ry <= gauss::kMaxRadius && rx <= gauss::kMaxRadius, DIFFSAL_E_SHAPE,
+             "%s: radius (%d, %d) above %d: the anti-aliasing Gaussian is built for sigma < 16, a downscale factor below 33", what, ry, rx,
+             gauss::kMaxRadius);
+  DS_REQUIRE((ry == 0 || wy) && (rx == 0 || wx), DIFFSAL_E_ARG, "%s: a radius above 0 without its weights", what);
+  return DIFFSAL_OK;
+}
+
+static PpGaussW pp_gauss_weights(const double* g, int r) {
+  PpGaussW k = {};
+  for (int i = 0; i <= r; ++i) k.g[i] = g ? g[i] : 1.0;
+  return k;
+}
+
+// the passes of the Gaussian, y first: in -> ... -> the returned map, which is `in` itself when neither axis has a radius, else t[0]
+// (one pass) or t[1] (two passes: t[0] holds the map between them)
+static int pp_gauss_launches(const float* in, int B, int h, int w, const double* wy, int ry, const double* wx, int rx, float* const t[2],
+                             hipStream_t s, const char* what_y, const char* what_x, const float** result) {
+  int rc;
+  const float* cur = in;
+  int next = 0;
+  if (ry > 0) {
+    hipLaunchKernelGGL(pp_gauss_y_kernel, dim3((w + gauss::kTX - 1) / gauss::kTX, (h + gauss::kTY - 1) / gauss::kTY, B), dim3(256), 0, s, cur, t[next], h, w, ry,
+                       pp_gauss_weights(wy, ry));
+    if ((rc = check_launch(what_y))) return rc;
+    cur = t[next++];
+  }
+  if (rx > 0) {
+    hipLaunchKernelGGL(pp_gauss_x_kernel, dim3((w + gauss::kSeg - 1) / gauss::kSeg, h, B), dim3(gauss::kSeg), 0, s, cur, t[next], h, w, rx,
+                       pp_gauss_weights(wx, rx));
+    if ((rc = check_launch(what_x))) return rc;
+    cur = t[next++];
+  }
+  *result = cur;
+  return DIFFSAL_OK;
+}
+
+extern "C" size_t diffsal_map_gauss_ws_bytes(int B, int h, int w) {
+  if (B <= 0 || h <= 0 || w <= 0) return 0;
+  return pp_layout(nullptr, B, static_cast<long>(h) * w, false, false, 1).bytes;
+}
+
+extern "C" int diffsal_map_gauss(const float* in, int B, int h, int w, const double* wy, int ry, const double* wx, int rx, float* out,
+                                 void* ws, size_t ws_bytes, diffsal_stream_t stream) {
+  int rc = pp_gauss_args("map_gauss", B, h, w, wy, ry, wx, rx);
+  if (rc) return rc;
+  const bool both = ry > 0 && rx > 0;
+  DS_REQUIRE(in && out && in != out && (ws || !both), DIFFSAL_E_ARG, "map_gauss: null argument, or out is in");
+  const PpWs ww = pp_layout(ws, B, static_cast<long>(h) * w, false, false, 1);
+  DS_REQUIRE(!both || (ws_bytes >= ww.bytes && aligned16(ws)), DIFFSAL_E_ARG, "map_gauss: workspace too small or misaligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (ry == 0 && rx == 0) {      // no axis shrinks: the identity, as one pass of weight 1 (x * 1.0 is exact)
+    hipLaunchKernelGGL(pp_gauss_x_kernel, dim3((w + gauss::kSeg - 1) / gauss::kSeg, h, B), dim3(gauss::kSeg), 0, s, in, out, h, w, 0,
+                       pp_gauss_weights(nullptr, 0));
+    return check_launch("map_gauss(copy)");
+  }
+  const float* res;
+  float* const t[2] = {both ? ww.g[0] : out, out};
+  return pp_gauss_launches(in, B, h, w, wy, ry, wx, rx, t, s, "map_gauss(gauss_y)", "map_gauss(gauss_x)", &res);
+}
+
+extern "C" size_t diffsal_map_resize_aa_ws_bytes(int B, int h, int w, int order, int clip) {
+  if (B <= 0 || h <= 0 || w <= 0 || (order != 1 && order != 3)) return 0;
+  return pp_layout(nullptr, B, static_cast<long>(h) * w, clip != 0, order == 3, 2).bytes;
+}
+
+extern "C" int diffsal_map_resize_aa(const float* in, int B, int h, int w, int H, int W, int order, int clip, int out_f64, const double* wy,
+                                     int ry, const double* wx, int rx, void* out, void* ws, size_t ws_bytes, diffsal_stream_t stream) {
+  DS_REQUIRE(order == 1 || order == 3, DIFFSAL_E_ARG, "map_resize_aa: order %d (1 or 3)", order);
+  DS_REQUIRE((clip == 0 || clip == 1) && (out_f64 == 0 || out_f64 == 1), DIFFSAL_E_ARG, "map_resize_aa: clip and out_f64 are 0 or 1");
+  int rc = pp_gauss_args("map_resize_aa", B, h, w, wy, ry, wx, rx);
+  if (rc) return rc;
+  DS_REQUIRE(H >= 1 && W >= 1 && H <= PP_MAX_DIM && W <= PP_MAX_DIM, DIFFSAL_E_SHAPE, "map_resize_aa: target %d x %d (1..%d per axis)", H, W,
+             PP_MAX_DIM);
+  const bool cubic = order == 3;
+  DS_REQUIRE(in && out && ws, DIFFSAL_E_ARG, "map_resize_aa: null argument");
+  const PpWs ww = pp_layout(ws, B, static_cast<long>(h) * w, clip != 0, cubic, 2);
+  DS_REQUIRE(ws_bytes >= ww.bytes && aligned16(ws), DIFFSAL_E_ARG, "map_resize_aa: workspace too small or misaligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const float* filtered;
+  if ((rc = pp_gauss_launches(in, B, h, w, wy, ry, wx, rx, ww.g, s, "map_resize_aa(gauss_y)", "map_resize_aa(gauss_x)", &filtered))) return rc;
+  return pp_resize_launches(in, filtered, B, h, w, H, W, cubic, clip, out_f64, out, ww, s);
 }

@@ -1995,6 +1995,51 @@ def map_resize(x: Tensor, H: int, W: int, *, order: int = 3, clip: bool = True, 
     return out
 
 
+def _gauss_weights(g, what: str):
+    """one axis' weights (centre first; None = no pass) -> (ctypes array of doubles or None, radius)"""
+    if g is None:
+        return None, 0
+    g = [float(v) for v in g]
+    if not g:
+        raise ValueError(f"{what}: an empty weight table (None means no pass)")
+    return (C.c_double * len(g))(*g), len(g) - 1
+
+
+def map_gauss(x: Tensor, wy, wx) -> Tensor:
+    """``diffsal_map_gauss`` on x [B, h, w] fp32 -> [B, h, w] fp32: the anti-aliasing Gaussian with the host weight tables ``wy``
+    (along rows) and ``wx`` (centre first, ``postprocess.gaussian_weights``; None = no pass on that axis)."""
+    lib = _lib.load()
+    if x.dim() != 3:
+        raise ValueError(f"map_gauss: x must be [B, h, w], got {tuple(x.shape)}")
+    B, h, w = x.shape
+    (gy, ry), (gx, rx) = _gauss_weights(wy, "map_gauss"), _gauss_weights(wx, "map_gauss")
+    out = torch.empty((B, h, w), device=x.device, dtype=torch.float32)
+    nws = lib.diffsal_map_gauss_ws_bytes(B, h, w)
+    ws = _ws_f64(nws, x.device)
+    with _prof("metrics", 0.0, _nb(x, out)):
+        _lib.check(lib.diffsal_map_gauss(_p(x), B, h, w, gy, ry, gx, rx, _p(out), ws.data_ptr(), nws, _stream()), "map_gauss")
+    return out
+
+
+def map_resize_aa(x: Tensor, H: int, W: int, wy, wx, *, order: int = 3, clip: bool = True, out_f64: bool = False) -> Tensor:
+    """``diffsal_map_resize_aa`` on x [B, h, w] fp32 -> [B, H, W] fp32 (fp64 with ``out_f64``): ``map_gauss`` with ``wy`` / ``wx``,
+    then the spline resize of the filtered map to any size, clipped to the range of ``x`` itself.  Without weights it is
+    ``map_resize``'s arithmetic."""
+    lib = _lib.load()
+    if x.dim() != 3:
+        raise ValueError(f"map_resize_aa: x must be [B, h, w], got {tuple(x.shape)}")
+    B, h, w = x.shape
+    H, W, order, clip = int(H), int(W), int(order), 1 if clip else 0
+    (gy, ry), (gx, rx) = _gauss_weights(wy, "map_resize_aa"), _gauss_weights(wx, "map_resize_aa")
+    out = torch.empty((B, H, W) if H > 0 and W > 0 else (0,), device=x.device, dtype=torch.float64 if out_f64 else torch.float32)
+    nws = lib.diffsal_map_resize_aa_ws_bytes(B, h, w, order, clip)
+    ws = _ws_f64(nws, x.device)
+    with _prof("metrics", 0.0, _nb(x, out)):
+        _lib.check(lib.diffsal_map_resize_aa(_p(x), B, h, w, H, W, order, clip, 1 if out_f64 else 0, gy, ry, gx, rx, out.data_ptr(),
+                                             ws.data_ptr(), nws, _stream()), "map_resize_aa")
+    return out
+
+
 def _u8_maps(u8: Tensor, what: str):
     if not u8.is_cuda or u8.dtype != torch.uint8 or not u8.is_contiguous() or u8.dim() != 3 or u8.numel() == 0:
         raise ValueError(f"{what}: expected a non-empty contiguous uint8 GPU tensor [B, h, w], got {u8.dtype} {u8.device} {tuple(u8.shape)}")

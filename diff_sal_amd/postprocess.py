@@ -13,8 +13,11 @@ post-processing").  The reference scores what it wrote to disk, not the tensor t
 float32 input, clamps to the input's range (``clip``) and rounds once to float32; the tests hold it to scipy 1.15 to 1e-12
 before that rounding.  Two things could not be run where this module was written and rest on reading the sources:
 
-* skimage itself.  The claim is that skimage (>= 0.19) executes exactly that zoom call for an upscale and then clips.  A
-  downscale (where skimage adds an anti-aliasing Gaussian first) is not built and raises.
+* skimage itself.  The claim is that skimage (>= 0.19) executes exactly that zoom call for an upscale and then clips, and that
+  for a target shorter than the map on some axis it first runs ``scipy.ndimage.gaussian_filter(map, sigma, mode='mirror')`` with
+  ``sigma = max(0, (in / out - 1) / 2)`` per axis, zooms the filtered map and clips to the range of the map as it came.  That
+  downscale is opt-in: ``resize(..., anti_aliasing=True)``, ``antialias`` for the Gaussian alone (held bit-equal to scipy's
+  float32 result), ``gaussian_weights`` for its table; without the keyword a downscale raises as before.
 * the reference's JPEG path.  For the audio-visual sets it writes ``pred_sal_%06d.jpg`` with ``cv2.imwrite``.  That export is integer
   arithmetic throughout and lives in ``diff_sal_amd.jpeg`` (files and read-back pixels, held to Pillow byte for byte; its docstring
   says what rests on reading OpenCV's sources): ``protocol_metrics(..., quantize="jpeg")`` scores the map a decoder reads back from
@@ -29,6 +32,7 @@ from __future__ import annotations
 import os
 from typing import Dict, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from . import _image_files
@@ -76,26 +80,77 @@ def _size(size) -> Tuple[int, int]:
     return H, W
 
 
-def resize(map: Tensor, size, *, order: int = 3, clip: bool = True, dtype: torch.dtype = torch.float32) -> Tensor:
-    """Spline resize of ``[B, H, W]`` maps to ``size = (H', W')`` (neither axis shorter than the input's): ``order`` 3 (cubic
-    B-spline) or 1 (linear), mirror boundary, ``clip`` to each image's input range.  float32; ``dtype=torch.float64`` returns the
-    value before the last rounding (what the tests compare with scipy)."""
+MAX_RADIUS = 64      # the anti-aliasing Gaussian's radius the kernels take (include/diffsal.h): sigma < 16, a factor below 33
+
+
+def gaussian_weights(in_size: int, out_size: int) -> Optional[np.ndarray]:
+    """The anti-aliasing Gaussian of one axis that goes from ``in_size`` to ``out_size`` samples, as skimage (>= 0.19) sets it and
+    ``scipy.ndimage.gaussian_filter`` tabulates it: ``sigma = max(0, (in_size / out_size - 1) / 2)``, radius ``r = int(4 sigma +
+    0.5)``, ``exp(-0.5 / sigma^2 * k^2)`` for ``k = -r .. r`` in float64, divided by their sum.  Returns the ``r + 1`` weights from
+    the centre outwards (float64), or None where the axis does not shrink (``sigma <= 1e-15``: scipy skips the axis).  Computed with
+    NumPy as scipy does: one ulp in a weight changes output bits."""
+    in_size, out_size = int(in_size), int(out_size)
+    if in_size < 1 or out_size < 1:
+        raise ValueError(f"postprocess: gaussian_weights needs sizes of at least 1, got {in_size} -> {out_size}")
+    sigma = max(0.0, (in_size / out_size - 1) / 2)
+    if not sigma > 1e-15:
+        return None
+    r = int(4.0 * sigma + 0.5)
+    if r > MAX_RADIUS:
+        raise ValueError(f"postprocess: {in_size} -> {out_size} is a downscale by a factor of {in_size / out_size:.4g}: its anti-aliasing "
+                         f"Gaussian has radius {r}, above the {MAX_RADIUS} (a factor below 33) the kernels are built for")
+    x = np.arange(-r, r + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return np.ascontiguousarray(phi[r:])
+
+
+def _weights(m: Tensor, H: int, W: int):
+    if H < 1 or W < 1:
+        raise ValueError(f"postprocess: size must be at least 1 x 1, got {(H, W)}")
+    return gaussian_weights(m.shape[1], H), gaussian_weights(m.shape[2], W)
+
+
+def antialias(map: Tensor, size) -> Tensor:
+    """The Gaussian stage of an anti-aliased ``resize`` of ``[B, h, w]`` maps to ``size``, alone: what
+    ``scipy.ndimage.gaussian_filter(map, sigma, mode='mirror')`` returns for the float32 map with ``gaussian_weights``' sigma per
+    axis, bit for bit (rows first, float64 sums, one rounding to float32 per axis).  An axis that does not shrink is left as it
+    is.  float32 ``[B, h, w]``."""
+    m = _map3(map, "map")
+    wy, wx = _weights(m, *_size(size))
+    return ops.map_gauss(m.float().contiguous(), wy, wx)
+
+
+def resize(map: Tensor, size, *, order: int = 3, clip: bool = True, dtype: torch.dtype = torch.float32,
+           anti_aliasing: bool = False) -> Tensor:
+    """Spline resize of ``[B, H, W]`` maps to ``size = (H', W')``: ``order`` 3 (cubic B-spline) or 1 (linear), mirror boundary,
+    ``clip`` to each image's input range.  float32; ``dtype=torch.float64`` returns the value before the last rounding (what the
+    tests compare with scipy).  By default neither axis may be shorter than the input's: a downscale raises.
+    ``anti_aliasing=True`` takes any size of at least 1 x 1 and follows skimage's default rule: if and only if some axis
+    shrinks, the map first passes the Gaussian of ``antialias`` (on the shrinking axes), the spline reads the filtered float32 map,
+    and the clip keeps the range of the map as it came.  Where no axis shrinks the result is the default call's, bit for bit."""
     m = _map3(map, "map")
     if dtype not in (torch.float32, torch.float64):
         raise ValueError(f"postprocess: dtype must be float32 or float64, got {dtype}")
     H, W = _size(size)
+    if anti_aliasing not in (True, False):
+        raise ValueError(f"postprocess: anti_aliasing must be True or False, got {anti_aliasing!r}")
+    if anti_aliasing and (H < m.shape[1] or W < m.shape[2]):
+        wy, wx = _weights(m, H, W)
+        return ops.map_resize_aa(m.float().contiguous(), H, W, wy, wx, order=order, clip=clip, out_f64=dtype == torch.float64)
     if H < m.shape[1] or W < m.shape[2]:
-        raise ValueError(f"postprocess: resize {tuple(m.shape[1:])} -> {(H, W)} shrinks an axis; a downscale (skimage's anti-aliasing "
-                         "path) is not built")
+        raise ValueError(f"postprocess: resize {tuple(m.shape[1:])} -> {(H, W)} shrinks an axis; a downscale needs skimage's "
+                         "anti-aliasing path: pass anti_aliasing=True")
     return ops.map_resize(m.float().contiguous(), H, W, order=order, clip=clip, out_f64=dtype == torch.float64)
 
 
 def protocol_metrics(pred: Tensor, fix: Optional[Tensor], gt: Optional[Tensor] = None, other: Optional[Tensor] = None, *,
-                     quantize=True, **benchmark_metrics_kwargs) -> Dict[str, Tensor]:
+                     quantize=True, anti_aliasing: bool = False, **benchmark_metrics_kwargs) -> Dict[str, Tensor]:
     """The benchmark's numbers for the sampler's maps: quantise -> / 255 -> resize to the annotations' resolution when it differs
     -> ``eval_metrics.benchmark_metrics`` (whose keyword arguments pass through).  ``quantize="jpeg"`` is the audio-visual sets'
     protocol: quantise -> the pixels read back from the JPEG file of that map (``jpeg.roundtrip``, quality 95) -> / 255 -> the rest
-    alike.  ``fix``, ``gt`` and ``other`` share one resolution, at least the prediction's on both axes.  As in the reference, the map NSS scores is resized with order 1 and the
+    alike.  ``fix``, ``gt`` and ``other`` share one resolution, at least the prediction's on both axes unless ``anti_aliasing=True``,
+    which ``resize`` then gets (annotations shorter than the prediction on some axis: skimage's Gaussian first).  As in the reference, the map NSS scores is resized with order 1 and the
     map of the other metrics with order 3: when both kinds are asked for and the shapes differ, ``benchmark_metrics`` runs twice.
     ``quantize=False`` scores the float map as it is.  ``{name: [B] float64}``; no host copy, no synchronisation: capturable."""
     p = _map3(pred, "pred")
@@ -139,9 +194,9 @@ def protocol_metrics(pred: Tensor, fix: Optional[Tensor], gt: Optional[Tensor] =
     res: Dict[str, Tensor] = {}
     cubic = tuple(k for k in _em.METRICS if k in want and k != "nss")
     if cubic:
-        res.update(_em.benchmark_metrics(resize(p, target[1:], order=3), fix, gt, other, metrics=cubic, **kw))
+        res.update(_em.benchmark_metrics(resize(p, target[1:], order=3, anti_aliasing=anti_aliasing), fix, gt, other, metrics=cubic, **kw))
     if "nss" in want:
-        res.update(_em.benchmark_metrics(resize(p, target[1:], order=1), fix, metrics=("nss",)))
+        res.update(_em.benchmark_metrics(resize(p, target[1:], order=1, anti_aliasing=anti_aliasing), fix, metrics=("nss",)))
     return {k: res[k] for k in _em.METRICS if k in res}
 
 

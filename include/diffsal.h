@@ -819,12 +819,34 @@ int diffsal_eval_metrics(const float* pred, const unsigned char* fix, const floa
  *                      cubic overshoots)
  * This is scipy.ndimage.zoom(in, (H/h, W/w), order=order, mode='mirror', grid_mode=True), which skimage (>= 0.19) runs for an
  * upscale before it clips.  An output axis shorter than the input is DIFFSAL_E_SHAPE (skimage adds an anti-aliasing Gaussian
- * there; not built), so is an input axis shorter than 2 or any axis above 32768; equal length is allowed (the same formula).
+ * there: diffsal_map_resize_aa, below), so is an input axis shorter than 2 or any axis above 32768; equal length is allowed (the same formula).
  * order other than 1 or 3: DIFFSAL_E_ARG.  All argument checks precede the first launch.
  * ws >= diffsal_map_resize_ws_bytes(B, h, w, order, clip) bytes, 16-byte aligned: order 3 keeps two [B][h][w] fp64 arrays
  * (88 MB at B = 64, 224 x 384), clip a few KB; order 1 without clip needs none (ws may be NULL).
  * min / max are exact and every sum has a fixed order: results are bit-reproducible and an image's result does not depend on
- * the batch it is in.  No floating-point atomics, no allocation, no synchronisation, graph-safe. */
+ * the batch it is in.  No floating-point atomics, no allocation, no synchronisation, graph-safe.
+ *
+ * diffsal_map_resize_aa: the same resize at ANY target size H, W >= 1, with the anti-aliasing Gaussian skimage (>= 0.19, its
+ * default anti_aliasing rule) runs over the map first on every axis that shrinks.  For a target (H, W) with H < h or W < w:
+ *   sigma    = (max(0, (h / H - 1) / 2), max(0, (w / W - 1) / 2))
+ *   filtered = scipy.ndimage.gaussian_filter(in, sigma, mode='mirror')          fp32 in, fp32 out
+ *   out      = scipy.ndimage.zoom(filtered, (H / h, W / w), order=order, mode='mirror', grid_mode=True)
+ *   clip = 1   clamps to [min, max] of the UNFILTERED in
+ * The caller computes the weights on the host and passes them: wy / wx point at ry + 1 / rx + 1 doubles in HOST memory, centre
+ * first; they are copied into the launches' arguments (no device allocation, no copy: graph-safe).  Per axis with sigma > 1e-15
+ *   r = int(4 sigma + 0.5);  g[k] = exp(-0.5 / sigma^2 * k^2), k = -r .. r, in fp64 with numpy.exp, divided by their sum
+ * (diff_sal_amd.postprocess.gaussian_weights; one ulp in a weight changes output bits).  A radius of 0 means no pass on that axis
+ * (the pointer is then not read and may be NULL); a radius above 64 (sigma >= 16, a factor of 33) is DIFFSAL_E_SHAPE.
+ * One output sample of a pass, in fp64 with every operation rounded on its own (no fused multiply-add), then ONE rounding to fp32:
+ *   acc = x[i] * g[0];  for k = r, r - 1, ..., 1:  acc = acc + (x[mirror(i - k)] + x[mirror(i + k)]) * g[k]
+ * with the mirror of diffsal_map_resize (folded as often as r > n - 1 needs).  Axis 0 (rows) first; the pass along axis 1 reads
+ * the fp32 result of the first.  This is scipy's correlate1d for a symmetric kernel, operation for operation: the filtered map
+ * is bit-equal to scipy 1.15's.  With both radii 0 the result is diffsal_map_resize's bit for bit where that function takes the
+ * shape.  Other checks as diffsal_map_resize (source axes 2..32768, target axes 1..32768), all before the first launch.
+ * ws >= diffsal_map_resize_aa_ws_bytes(B, h, w, order, clip) bytes, 16-byte aligned, never NULL: diffsal_map_resize's layout plus
+ * two [B][h][w] fp32 arrays.
+ * diffsal_map_gauss: the Gaussian stage alone, in [B][h][w] fp32 -> out [B][h][w] fp32 (out != in; both radii 0: a copy).
+ * ws >= diffsal_map_gauss_ws_bytes(B, h, w) bytes (one [B][h][w] fp32 array), read only when both radii are above 0. */
 size_t diffsal_map_to_u8_ws_bytes(int B, long n);
 int diffsal_map_to_u8(const float* pred, int B, long n, unsigned char* u8, float* f, void* ws, size_t ws_bytes,
                       diffsal_stream_t stream);
@@ -832,6 +854,12 @@ int diffsal_map_from_u8(const unsigned char* u8, long total, float* f, diffsal_s
 size_t diffsal_map_resize_ws_bytes(int B, int h, int w, int order, int clip);
 int diffsal_map_resize(const float* in, int B, int h, int w, int H, int W, int order, int clip, int out_f64, void* out, void* ws,
                        size_t ws_bytes, diffsal_stream_t stream);
+size_t diffsal_map_resize_aa_ws_bytes(int B, int h, int w, int order, int clip);
+int diffsal_map_resize_aa(const float* in, int B, int h, int w, int H, int W, int order, int clip, int out_f64, const double* wy,
+                          int ry, const double* wx, int rx, void* out, void* ws, size_t ws_bytes, diffsal_stream_t stream);
+size_t diffsal_map_gauss_ws_bytes(int B, int h, int w);
+int diffsal_map_gauss(const float* in, int B, int h, int w, const double* wy, int ry, const double* wx, int rx, float* out, void* ws,
+                      size_t ws_bytes, diffsal_stream_t stream);
 
 /* ---- JPEG export: the 8-bit maps of the audio-visual sets -> the files the reference writes, and what it reads back -----------
  * For AVAD, Coutrot, DIEM, ETMD and SumMe R/diffusion_trainer.py:898-935 (save_img, av_data=True) writes pred_sal_%06d.jpg with

@@ -6,7 +6,9 @@ device and covers the whole Python entry point (output and workspace allocation 
 the bytes that must cross HBM once (input read once, output written once) over the bandwidth a float4 copy reaches on the MI355X
 (6.29 TB/s measured, of 8 TB/s peak), and the time as a multiple of that floor.  The kernels move more than the floor's bytes
 (the export reads its input twice, order 3 keeps two float64 arrays of the input's size between its passes), most of it through
-the caches.  Prints one JSON line.
+the caches.  A downscale leg follows (resize(..., anti_aliasing=True), orders 1 and 3 with the clip, and antialias alone) at
+two targets: 180 x 320, where both Gaussian radii are 0 and the call is the plain zoom, and 100 x 120 (radii 2 and 4), where both
+Gaussian passes run.  Prints one JSON line.
 usage: python tools/bench_postprocess.py [B h w H W]"""
 import json
 import os
@@ -57,4 +59,12 @@ res = {
     "resize_order1": entry(lambda: pp.resize(m, (H, W), order=1), B * (h * w + H * W) * 4),
     "resize_order3": entry(lambda: pp.resize(m, (H, W), order=3), B * (h * w + H * W) * 4),
 }
+for Hd, Wd in ((180, 320), (100, 120)):
+    once = B * (h * w + Hd * Wd) * 4
+    res[f"downscale_{Hd}x{Wd}"] = {
+        "radii": [0 if g is None else len(g) - 1 for g in (pp.gaussian_weights(h, Hd), pp.gaussian_weights(w, Wd))],
+        "antialias": entry(lambda: pp.antialias(m, (Hd, Wd)), B * h * w * 8),
+        "resize_order1": entry(lambda: pp.resize(m, (Hd, Wd), order=1, anti_aliasing=True), once),
+        "resize_order3": entry(lambda: pp.resize(m, (Hd, Wd), order=3, anti_aliasing=True), once),
+    }
 print(json.dumps(res))
