@@ -1316,7 +1316,8 @@ extern "C" int diffsal_conv_in(const float* x, const float* w, const float* bias
 extern "C" int diffsal_pack_frames(const float* vis, const void* noise, void* out, int B, int C, int Tv, int Tout,
                                    int hw, int dtype, diffsal_stream_t stream) {
   DS_REQUIRE(vis && out, DIFFSAL_E_ARG, "pack_frames: null argument");
-  DS_REQUIRE(B > 0 && C > 0 && C % 4 == 0 && Tv > 0 && hw > 0 && Tout >= Tv + (noise ? 1 : 0), DIFFSAL_E_SHAPE,
+  // the transpose is scalar and guarded at both edges: any C; the noise frame is copied 16 bytes at a time
+  DS_REQUIRE(B > 0 && C > 0 && (C % 4 == 0 || !noise) && Tv > 0 && hw > 0 && Tout >= Tv + (noise ? 1 : 0), DIFFSAL_E_SHAPE,
              "pack_frames: bad shape C=%d Tv=%d Tout=%d hw=%d", C, Tv, Tout, hw);
   DS_REQUIRE(aligned16(out) && (!noise || aligned16(noise)), DIFFSAL_E_ALIGN, "pack_frames: misaligned pointer");
   const int Q = Tv * hw;

@@ -72,11 +72,15 @@ __global__ __launch_bounds__(kRedBlock) void reduce_final_kernel(const double* _
 
 // out = x * s[0]  (chain-rule factor arriving as a device scalar)
 __global__ __launch_bounds__(256) void scale_by_kernel(const float* __restrict__ x, const float* __restrict__ s,
-                                                       float* __restrict__ out, long n4) {
+                                                       float* __restrict__ out, long n4, long n) {
   const float k = s[0];
   for (long i = static_cast<long>(blockIdx.x) * 256 + threadIdx.x; i < n4; i += static_cast<long>(gridDim.x) * 256) {
     const float4 v = ld4(x + i * 4);
     st4(out + i * 4, make_float4(v.x * k, v.y * k, v.z * k, v.w * k));
+  }
+  if (blockIdx.x == 0 && threadIdx.x < static_cast<int>(n - n4 * 4)) {   // tail of 1 to 3 elements
+    const long i = n4 * 4 + threadIdx.x;
+    out[i] = x[i] * k;
   }
 }
 
@@ -168,11 +172,11 @@ extern "C" int diffsal_mse_loss(const float* pred, const float* target, float* d
 
 extern "C" int diffsal_scale_by(const float* x, const float* s, float* out, long n, diffsal_stream_t stream) {
   DS_REQUIRE(x && s && out, DIFFSAL_E_ARG, "scale_by: null argument");
-  DS_REQUIRE(n > 0 && n % 4 == 0 && aligned16(x) && aligned16(out), DIFFSAL_E_SHAPE,
-             "scale_by: need n %% 4 == 0 and 16-byte aligned buffers");
+  DS_REQUIRE(n > 0 && aligned16(x) && aligned16(out), DIFFSAL_E_SHAPE, "scale_by: need n > 0 and 16-byte aligned buffers");
   long need = (n / 4 + 255) / 256;
+  if (need < 1) need = 1;
   hipLaunchKernelGGL(scale_by_kernel, dim3(static_cast<int>(need < 4096 ? need : 4096)), dim3(256), 0,
-                     static_cast<hipStream_t>(stream), x, s, out, n / 4);
+                     static_cast<hipStream_t>(stream), x, s, out, n / 4, n);
   return check_launch("scale_by");
 }
 

@@ -133,12 +133,12 @@ class RelTablesFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rel_t, rel_h, rel_w, plans):
-        ctx.plans = plans
+        ctx.plans, ctx.D = plans, rel_t.shape[1]
         return tuple(ops.rel_tables((rel_t, rel_h, rel_w), plans))
 
     @staticmethod
     def backward(ctx, dt, dh, dw):
-        zeros = [None if g is not None else torch.zeros((pl["q"], pl["k"], 96), device=pl["idx2"].device)
+        zeros = [None if g is not None else torch.zeros((pl["q"], pl["k"], ctx.D), device=pl["idx2"].device)
                  for g, pl in zip((dt, dh, dw), ctx.plans)]
         gs = [g if g is not None else z for g, z in zip((dt, dh, dw), zeros)]
         d = ops.rel_tables_bwd(gs, ctx.plans)

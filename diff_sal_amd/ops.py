@@ -1585,12 +1585,13 @@ def scale_by(x: Tensor, s: Tensor) -> Tensor:
 def multi_copy(srcs: Sequence[Tensor], dst_offsets: Sequence[int], dst: Tensor) -> None:
     """dst[off_i : off_i + srcs[i].numel()] = srcs[i] for all i, in a handful of launches (csrc/optim.hip)."""
     lib = _lib.load()
-    n = len(srcs)
+    live = [(t, o) for t, o in zip(srcs, dst_offsets) if t.numel() > 0]      # an empty tensor has no storage: nothing to copy
+    n = len(live)
     if n == 0:
         return
-    keep = [t if t.is_contiguous() else t.contiguous() for t in srcs]
+    keep = [t if t.is_contiguous() else t.contiguous() for t, _ in live]
     ptrs = (C.c_void_p * n)(*[_p(t) for t in keep])
-    offs = (C.c_long * n)(*[int(o) for o in dst_offsets])
+    offs = (C.c_long * n)(*[int(o) for _, o in live])
     sizes = (C.c_long * n)(*[t.numel() for t in keep])
     _lib.check(lib.diffsal_multi_copy(ptrs, offs, sizes, n, _p(dst), _stream()), "multi_copy")
 

@@ -455,7 +455,8 @@ int diffsal_audio_fuse_bwd(const float* a_small, const float* x, const float* do
 /* ---- K6: frame packing: visual features NCTHW[B,C,Tv,h,w] + noise NHWC[B,h,w,C] ->
  * NHWC frames [B,Tv+1,h,w,C] with the noise map as the LAST frame (quirk Q2).
  * Replaces torch.cat(dim=2) + rearrange().contiguous(), R/.../sal_unet.py:311-317,
- * transformer.py:273-279. noise may be NULL (then only Tv frames of a [B,Tout,...] buffer are written). */
+ * transformer.py:273-279. noise may be NULL (then only Tv frames of a [B,Tout,...] buffer are written, and C may be any
+ * positive count: the transpose is scalar; with a noise map C % 4 == 0, since that frame is copied 16 bytes at a time). */
 int diffsal_pack_frames(const float* vis /*fp32: the module's input contract*/, const void* noise, void* out, int B,
                         int C, int Tv, int Tout, int hw, int dtype, diffsal_stream_t stream);
 /* The same for up to four (vis, noise, out) triples of one batch size and storage type in ONE launch: the frame tensors of all
@@ -1280,7 +1281,7 @@ int diffsal_train_key_advance(unsigned long long* key, diffsal_stream_t stream);
  *   p, m (exp_avg), v (exp_avg_sq), with the gradient first multiplied by
  *   gscale * min(1, max_norm / (norm[0] + 1e-6)) (norm may be NULL or max_norm <= 0: no clipping).  `step` counts
  *   from 1.  store_clipped_grad != 0 writes the scaled gradient back into g as clip_grad_norm_ does.
- * scale_by: out = x * s[0] with s a device scalar (the incoming d(loss) of the MSE backward).  n % 4 == 0.
+ * scale_by: out = x * s[0] with s a device scalar (the incoming d(loss) of the MSE backward); any n > 0.
  * multi_copy: dst[dst_offsets[i] .. +sizes[i]) = srcs[i][0 .. sizes[i]) for i < count, a few launches for any count
  *   (gathers the per-parameter gradients autograd produced into the flat gradient buffer; the three tables are HOST
  *   arrays, the pointers in them device pointers; dst_offsets multiples of 4 elements).

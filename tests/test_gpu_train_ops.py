@@ -489,3 +489,50 @@ def test_wgrad_dma_kernel_equals_the_register_staged_kernel(M, K, N, tuning):
     ref = dy.reshape(M, N).double().t() @ x.reshape(M, K).double()
     assert (dw1.double() - ref).abs().max().item() < 2e-5 * ref.abs().max().item()
     assert (db1.double() - dy.reshape(M, N).double().sum(0)).abs().max().item() < 1e-4 * (dy.abs().sum(dim=(0, 1, 2)).max().item())
+
+
+# ---- the gradient gather and the chain-rule factor (csrc/optim.hip) ----
+@pytest.mark.parametrize("count", [1, 48, 49, 100])
+def test_multi_copy_fills_its_slots_and_nothing_else(ag, count):
+    """Sources of 1 .. 70001 elements, each once 16-byte aligned (vector body + a tail of 1 to 3) and once as t[1:] (4 bytes off: the
+    scalar path); 48 sources per launch, so 49 and 100 take two and three.  Every slot equals its source, every gap keeps the sentinel."""
+    from tests import _train_nodes_ref as R
+
+    _, ops = ag
+    plan, offs, total = R.copy_plan(count)
+    g = torch.Generator().manual_seed(count)
+    srcs = []
+    for n, misaligned in plan:
+        t = torch.randn(n + 1, generator=g).to(DEV)
+        srcs.append(t[1:] if misaligned else t[:n])
+        assert srcs[-1].is_contiguous() and (srcs[-1].data_ptr() % 16 == 4) == misaligned
+    dst = torch.full((total,), R.SENTINEL, device=DEV)
+    ops.multi_copy(srcs, offs, dst)
+    expect = torch.full((total,), R.SENTINEL)
+    for t, o in zip(srcs, offs):
+        expect[o:o + t.numel()] = t.cpu()
+    assert torch.equal(dst.cpu(), expect)
+
+
+def test_multi_copy_skips_sources_without_elements(ag):
+    _, ops = ag
+    a, b = torch.randn(5, device=DEV), torch.randn(70001, device=DEV)
+    empty = torch.empty(0, device=DEV)
+    dst = torch.full((70400,), -12345.0, device=DEV)
+    ops.multi_copy([empty, a, empty, b, empty], [0, 64, 64, 128, 70399], dst)
+    expect = torch.full((70400,), -12345.0)
+    expect[64:69], expect[128:128 + 70001] = a.cpu(), b.cpu()
+    assert torch.equal(dst.cpu(), expect)
+    ops.multi_copy([empty, empty], [0, 64], dst)                # nothing but empty sources: no launch, nothing written
+    ops.multi_copy([], [], dst)
+    assert torch.equal(dst.cpu(), expect)
+
+
+@pytest.mark.parametrize("n", [1, 5, 1 << 20])
+def test_scale_by_is_the_fp32_product(ag, n):
+    """x * s[0] with a device scalar: the vector body and the tail of 1 to 3 elements; bit-equal to the fp32 product."""
+    _, ops = ag
+    g = torch.Generator().manual_seed(n)
+    x, s = torch.randn(n, generator=g), torch.tensor([-0.37])
+    got = ops.scale_by(x.to(DEV), s.to(DEV))
+    assert got.shape == x.shape and torch.equal(got.cpu(), x * s)

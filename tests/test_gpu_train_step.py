@@ -425,9 +425,11 @@ def test_train_step_odd_batches_and_dropout_determinism(B, av):
 
 
 def test_fused_tape_nodes_leave_every_gradient_where_the_separate_nodes_put_it(monkeypatch):
-    """LayerNorm + residual accumulation, GELU + fc2 and (in the encoder) rel-pos projection + attention are single tape nodes
-    (autograd_ops.layernorm_fork / linear(in_gelu) / encoder_autograd.relpos_attention); with the switches off the same step
-    runs on the separate nodes.  Same forward bit for bit, gradients equal up to the order of one addition per element."""
+    """LayerNorm + residual accumulation and GELU + fc2 are single tape nodes (autograd_ops.layernorm_fork / linear(in_gelu)); with
+    the switches off the same step runs on the separate nodes.  Same forward bit for bit, gradients equal up to the order of one
+    addition per element.  FUSE_RELPOS is toggled along with them, but the denoiser built here has no rel-pos attention: the encoder's
+    fused node (encoder_autograd.relpos_attention) is compared with its two-node form in
+    tests/test_gpu_encoder_nodes.py::test_relpos_attention_node_against_the_two_nodes_and_fp64."""
     from diff_sal_amd import autograd_ops as ag
 
     cfg = CASES["tiny_av"][0]
