@@ -56,14 +56,31 @@ def decode(files: Sequence, mode: str, device, strict: bool, *, codec: str, pack
     return frames
 
 
+MAX_READ_THREADS = 16
+
+
+def _read(path) -> bytes:
+    with open(path, "rb") as f:
+        return f.read()
+
+
+def read_files(paths: Sequence, threads: int = 1) -> list:
+    """the bytes of the files at ``paths``, in their order; ``threads`` above 1 reads them from that many host threads (at most
+    ``MAX_READ_THREADS``, and no more than there are files): a read releases the interpreter lock, so a video's files arrive together"""
+    paths = list(paths)
+    n = min(int(threads), MAX_READ_THREADS, len(paths))
+    if n <= 1:
+        return [_read(p) for p in paths]
+    from concurrent.futures import ThreadPoolExecutor
+
+    with ThreadPoolExecutor(max_workers=n) as pool:
+        return list(pool.map(_read, paths))
+
+
 def file_decoder(decode: Callable) -> Callable:
     def decode_files(paths: Sequence, mode: str = "RGB", device=None, strict: bool = True):
         """``decode`` of the files at ``paths``."""
-        data = []
-        for p in paths:
-            with open(p, "rb") as f:
-                data.append(f.read())
-        return decode(data, mode=mode, device=device, strict=strict)
+        return decode(read_files(paths), mode=mode, device=device, strict=strict)
     return decode_files
 
 

@@ -85,7 +85,8 @@ class DiffusionSampler:
         #    (SalUNet.max_clips_per_pass = 1 for the trajectory).  Its kernels choose tiles by the batch size, so a clip's output moves
         #    by ~1e-6 with the batch it is evaluated in; one clip per pass makes the whole prediction, not only the noise, bit-equal
         #    on any layout, at the price of the batched launches (B = 1 is unaffected).  False keeps the batched passes: the noise
-        #    is still layout-independent, the prediction then agrees across layouts to ~1e-6.
+        #    is still layout-independent, the prediction then agrees across layouts to ~1e-6.  sample_image applies the same rule
+        #    to the encoders it runs in front of the trajectory.
         self.noise_source, self.seed = noise_source, int(seed)
         self.clip_passes = (noise_source == "device") if clip_passes is None else bool(clip_passes)
         if self.step_invariant_shortcut:
@@ -509,13 +510,22 @@ class DiffusionSampler:
     @torch.no_grad()
     def sample_image(self, x: Optional[Tensor], img: Optional[Tensor] = None, audio: Optional[Tensor] = None, clip_ids=None) -> Tensor:
         """Encoders once per clip, then the per-step loop (R/diffusion_trainer.py:546-640).  noise_source="device":
-        ``clip_ids`` name the clips and ``x=None`` starts from their x_T."""
+        ``clip_ids`` name the clips and ``x=None`` starts from their x_T.  With ``clip_passes`` on, the encoders too evaluate a
+        batch one clip per pass: their kernels choose tiles by the batch size like the denoiser's, and a feature that moves by
+        ~1e-6 with the batch moves a pixel of the 8-bit export now and then."""
         m = self.model
         audio_embed = None
         if getattr(m, "audio_net", None):
-            _, audio_embed = m.forward_vggish(audio)
+            if self.clip_passes and audio is not None and audio.shape[0] > 1:
+                audio_embed = torch.cat([m.forward_vggish(audio[i:i + 1])[1] for i in range(audio.shape[0])])
+            else:
+                _, audio_embed = m.forward_vggish(audio)
         if getattr(m, "visual_net", None):
-            vis_list = m.visual_net(img)
+            if self.clip_passes and img.shape[0] > 1:
+                per_clip = [m.visual_net(img[i:i + 1]) for i in range(img.shape[0])]
+                vis_list = [torch.cat(scale) for scale in zip(*per_clip)]
+            else:
+                vis_list = m.visual_net(img)
         else:  # same synthetic fall-back shapes as the reference (:564-569)
             if x is None:
                 x = self.initial_noise(clip_ids)
