@@ -29,7 +29,7 @@ __device__ __forceinline__ double block_sum_f64(double v, double* sh) {
 // dpred = 2 scale (pred - target); part[block] = sum (pred - target)^2
 __global__ __launch_bounds__(kRedBlock) void mse_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                         float* __restrict__ dpred, double* __restrict__ part, long n4,
-                                                        float gscale) {
+                                                        long n, float gscale) {
   __shared__ double sh[kRedBlock / kWave];
   double acc = 0.0;
   for (long i = static_cast<long>(blockIdx.x) * kRedBlock + threadIdx.x; i < n4; i += static_cast<long>(gridDim.x) * kRedBlock) {
@@ -37,6 +37,12 @@ __global__ __launch_bounds__(kRedBlock) void mse_kernel(const float* __restrict_
     const float4 d = make_float4(p.x - t.x, p.y - t.y, p.z - t.z, p.w - t.w);
     if (dpred) st4(dpred + i * 4, make_float4(gscale * d.x, gscale * d.y, gscale * d.z, gscale * d.w));
     acc += static_cast<double>(fmaf(d.x, d.x, fmaf(d.y, d.y, fmaf(d.z, d.z, d.w * d.w))));
+  }
+  if (blockIdx.x == 0 && threadIdx.x < static_cast<int>(n - n4 * 4)) {   // tail of 1 to 3 elements
+    const long i = n4 * 4 + threadIdx.x;
+    const float d = pred[i] - target[i];
+    if (dpred) dpred[i] = gscale * d;
+    acc += static_cast<double>(d * d);
   }
   const double s = block_sum_f64(acc, sh);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
@@ -159,12 +165,12 @@ extern "C" int diffsal_reduce_blocks(void) { return 1024; }
 extern "C" int diffsal_mse_loss(const float* pred, const float* target, float* dpred, float* loss, double* part, long n,
                                 float loss_scale, diffsal_stream_t stream) {
   DS_REQUIRE(pred && target && loss && part, DIFFSAL_E_ARG, "mse_loss: null argument");
-  DS_REQUIRE(n > 0 && n % 4 == 0, DIFFSAL_E_SHAPE, "mse_loss: element count %ld must be a positive multiple of 4", n);
+  DS_REQUIRE(n > 0, DIFFSAL_E_SHAPE, "mse_loss: element count %ld must be positive", n);
   DS_REQUIRE(aligned16(pred) && aligned16(target) && (!dpred || aligned16(dpred)), DIFFSAL_E_ARG,
              "mse_loss: pointers must be 16-byte aligned");
   const int blocks = red_grid(n / 4, diffsal_reduce_blocks());
   hipLaunchKernelGGL(mse_kernel, dim3(blocks), dim3(kRedBlock), 0, static_cast<hipStream_t>(stream), pred, target, dpred,
-                     part, n / 4, 2.f * loss_scale);
+                     part, n / 4, n, 2.f * loss_scale);
   hipLaunchKernelGGL(reduce_final_kernel, dim3(1), dim3(kRedBlock), 0, static_cast<hipStream_t>(stream), part, blocks, loss,
                      static_cast<double>(loss_scale), 0);
   return check_launch("mse_loss");

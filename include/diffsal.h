@@ -1274,7 +1274,8 @@ int diffsal_train_key_advance(unsigned long long* key, diffsal_stream_t stream);
  *
  * mse_loss: loss[0] = loss_scale * sum (pred - target)^2 and, if dpred != NULL, dpred = 2 loss_scale (pred - target).
  *   With loss_scale = mse_weight / batch this is `mse_weight * (pred-gt).square().sum(dim=(1,2,3)).mean(dim=0)`
- *   (R/models/sal_losses.py:189-192) and its gradient.  n % 4 == 0.
+ *   (R/models/sal_losses.py:189-192) and its gradient.  Any n > 0 (a tail of 1 to 3 elements is read and written one by one);
+ *   pred, target and dpred 16-byte aligned.
  * grad_norm: norm[0] = gscale * ||g||_2 over the flat gradient buffer -- total_norm of
  *   torch.nn.utils.clip_grad_norm_ (R/diffusion_trainer.py:228-233); gscale = 1/world_size folds in the DDP mean.
  * adam_step: torch.optim.Adam.step (R/util/utils.py:116-123, R/diffusion_trainer.py:235; amsgrad=false) on
