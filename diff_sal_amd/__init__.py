@@ -10,7 +10,7 @@ from .dpm_solver import DPM_Solver, NoiseScheduleVP, model_wrapper  # noqa: F401
 from .sampling import DiffusionSampler, ddpm_steps, generalized_steps  # noqa: F401
 from .diffusion_utils import get_beta_schedule, to_torch  # noqa: F401
 from .train_step import DiffusionTrainStep, FlatParams, GradReducer  # noqa: F401
-from . import audio_input, eval_metrics, evaluate, jpeg, postprocess, predict, video_input  # noqa: F401
+from . import audio_input, eval_metrics, evaluate, jpeg, postprocess, predict, train, video_input  # noqa: F401
 
 __all__ = ["SalUNet", "VideoSaliencyModel", "MViT", "VGGish", "AudioAttnNet", "DiffusionModel", "DiffusionModel_w_MultiScale", "EMAHelper", "DPM_Solver", "NoiseScheduleVP", "model_wrapper", "DiffusionSampler",
-           "generalized_steps", "ddpm_steps", "get_beta_schedule", "to_torch", "DiffusionTrainStep", "FlatParams", "GradReducer", "eval_metrics", "evaluate", "postprocess", "jpeg", "audio_input", "video_input", "predict"]
+           "generalized_steps", "ddpm_steps", "get_beta_schedule", "to_torch", "DiffusionTrainStep", "FlatParams", "GradReducer", "eval_metrics", "evaluate", "postprocess", "jpeg", "audio_input", "video_input", "predict", "train"]

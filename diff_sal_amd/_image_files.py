@@ -103,6 +103,41 @@ def parse_files(files: Sequence, codec: str, parse: Callable, refused: type, key
     return files, parsed
 
 
+def decode_groups(files: Sequence, mode: str, device, *, codec: str, geometry: Callable, refused: type, decode: Callable,
+                  status_bits: dict, noun: str):
+    """``jpeg.decode_groups`` / ``png.decode_groups``: files of several geometries through the codec's ``decode``, which takes one
+    geometry per call.  ``geometry(f, i)`` reads file ``i``'s header and gives what the files of a call must share; the files are
+    grouped by it (groups in order of first appearance, a group's files in list order) and every group is one ``decode`` call, so
+    the calls number the distinct geometries, not the files.  Returns ``(groups, where)``: the decoded tensor of every group and,
+    per file, ``(group, position in it)``.  The per-file status of all calls is read back once; damage raises as ``decode`` does,
+    naming the files by their positions in ``files``."""
+    files = list(files)
+    if not files:
+        raise ValueError(f"{codec}.decode_groups: an empty list of files")
+    index, members, where = {}, [], []
+    for i, f in enumerate(files):
+        try:
+            key = geometry(f, i)
+        except refused as e:
+            raise ValueError(f"{codec}.decode_groups: file {i}: {e}") from None
+        g = index.setdefault(key, len(index))
+        if g == len(members):
+            members.append([])
+        where.append((g, len(members[g])))
+        members[g].append(f)
+    groups, status = [], []
+    for m in members:
+        frames, st = decode(m, mode, device, False)
+        groups.append(frames)
+        status.append(st)
+    per_group = [s.cpu().numpy() for s in ([torch.cat(status)] if len(status) > 1 else status)][0]
+    if per_group.any():
+        first = np.concatenate([[0], np.cumsum([len(m) for m in members])])
+        in_order = np.array([per_group[first[g] + k] for g, k in where])
+        raise ValueError(damage_message(in_order, status_bits, codec, noun))
+    return groups, where
+
+
 def checked_ids(n: int, video_ids: Sequence, frame_ids, module: str):
     """``save_predictions``' ids for ``n`` predictions -> (video ids as a list, frame ids as Python ints; a tensor is flattened)"""
     frame_ids = [int(f) for f in (frame_ids.reshape(-1).tolist() if isinstance(frame_ids, Tensor) else frame_ids)]

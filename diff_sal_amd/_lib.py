@@ -26,12 +26,15 @@ def constants(prefix, names):
     return [K["DIFFSAL_" + prefix + n] for n in names.split()]
 
 
-# the two structs the host fills and passes by reference, and the element of diffsal_pack_weight_many's device job table
+# the two structs the host fills and passes by reference, the element of diffsal_pack_weight_many's device job table and the
+# element of diffsal_resample_u8_groups' host array
 _STRUCTS = dict.fromkeys(_H.structs)
 ConvDesc = _cdecl.structure("ConvDesc", _H.structs["diffsal_conv_desc"], _STRUCTS, "struct diffsal_conv_desc (include/diffsal.h).")
 Wino4Ext = _cdecl.structure("Wino4Ext", _H.structs["diffsal_wino4_ext"], _STRUCTS,
                             "struct diffsal_wino4_ext (include/diffsal.h): optional extras of diffsal_conv_wino4.")
 PackJob = _cdecl.structure("PackJob", _H.structs["diffsal_pack_job"], _STRUCTS, "struct diffsal_pack_job (include/diffsal.h).")
+ResampleGroup = _cdecl.structure("ResampleGroup", _H.structs["diffsal_resample_group"], _STRUCTS,
+                                 "struct diffsal_resample_group (include/diffsal.h): a host array of them is passed as c_void_p.")
 _STRUCTS.update(diffsal_conv_desc=ConvDesc, diffsal_wino4_ext=Wino4Ext)
 
 # the header's value; diffsal_version() is the one the loaded binary was compiled with.  load() refuses a binary whose value

@@ -12,6 +12,10 @@
 //                     support and redo that much horizontal work; rs_plan picks the band height from the LDS budget.
 //   rs_h_kernel, rs_v_kernel   the two passes through an HBM workspace [N][H0][W1][C]: the form for sizes where not even a band
 //                     of one output row fits in LDS; an axis whose size does not change runs no pass in either form.
+//   rs_*_groups_kernel   the same three bodies (rs_fused_body, rs_h_body, rs_v_body) over frames of several source sizes: a
+//                     workgroup finds its (group, frame, band or tile) through a prefix table of the groups' workgroup counts, and
+//                     a dst table names the output frame of every input frame (diffsal_resample_u8_groups: at most one launch per
+//                     form however many sizes a shuffled training batch holds).  The kernels above are the one-group callers.
 //   vg_gather_kernel  uint8 [N][h][w][C] + index table [B][T] + look-up table [C][256] -> fp32 [B][C][T][h][w], 16-byte stores.
 // The tables live in device memory and cannot be checked by the host: every bound read from them is clamped to the source, the
 // tap count to the table's width and the band's row span to the LDS image, so a wrong table gives wrong pixels and no access
@@ -42,14 +46,31 @@ __device__ __forceinline__ void rs_bounds(const int* __restrict__ b, int o, int 
   cnt = rs_clampi(b[2 * o + 1], 0, room);
 }
 
+// Output frame of a group's frame n: the group's slice of the dst table (in device memory, so the host could not check it: clamped
+// to the output's slots), or n itself where the group's frames are consecutive in the output.
+__device__ __forceinline__ long rs_slot(const int* __restrict__ dst, int nslots, long n) {
+  return dst ? static_cast<long>(rs_clampi(dst[n], 0, nslots - 1)) : n;
+}
+
+// Horizontal pass of output pixel idx of in [rows][W0][C] -> out [..][W1][C].  The frames have Hf rows each and frame n goes to
+// frame rs_slot(n) of out; xb = NULL: the width does not change and the pixel is copied.
 template <int C>
-__global__ __launch_bounds__(256) void rs_h_kernel(const unsigned char* __restrict__ in, long rows, int W0, int W1,
-                                                   const int* __restrict__ xb, const int* __restrict__ xk, int xks,
-                                                   unsigned char* __restrict__ out) {
-  const long idx = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
+__device__ __forceinline__ void rs_h_body(const unsigned char* __restrict__ in, long rows, int W0, int W1, const int* __restrict__ xb,
+                                          const int* __restrict__ xk, int xks, unsigned char* __restrict__ out, long idx, int Hf,
+                                          const int* __restrict__ dst, int nslots) {
   if (idx >= rows * W1) return;
   const long y = idx / W1;
   const int xo = static_cast<int>(idx - y * W1);
+  long oidx = idx;
+  if (dst) {
+    const long n = y / Hf;
+    oidx = (rs_slot(dst, nslots, n) * Hf + (y - n * Hf)) * W1 + xo;
+  }
+  if (!xb) {
+#pragma unroll
+    for (int c = 0; c < C; ++c) out[oidx * C + c] = in[idx * C + c];
+    return;
+  }
   int lo, cnt;
   rs_bounds(xb, xo, W0, xks, lo, cnt);
   const unsigned char* src = in + (y * W0 + lo) * C;
@@ -63,7 +84,14 @@ __global__ __launch_bounds__(256) void rs_h_kernel(const unsigned char* __restri
     for (int c = 0; c < C; ++c) acc[c] = rs_mad(src[t * C + c], kv, acc[c]);
   }
 #pragma unroll
-  for (int c = 0; c < C; ++c) out[idx * C + c] = static_cast<unsigned char>(rs_clip8(acc[c]));
+  for (int c = 0; c < C; ++c) out[oidx * C + c] = static_cast<unsigned char>(rs_clip8(acc[c]));
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void rs_h_kernel(const unsigned char* __restrict__ in, long rows, int W0, int W1,
+                                                   const int* __restrict__ xb, const int* __restrict__ xk, int xks,
+                                                   unsigned char* __restrict__ out) {
+  rs_h_body<C>(in, rows, W0, W1, xb, xk, xks, out, static_cast<long>(blockIdx.x) * 256 + threadIdx.x, 1, nullptr, 0);
 }
 
 // four accumulators from one packed word of four bytes
@@ -76,7 +104,13 @@ __device__ __forceinline__ void rs_mad4(unsigned w, int k, int (&acc)[4]) {
 // bytes x .. x + 3 of a row of WB bytes (those past the row's end: not written), as one word when the row allows it
 __device__ __forceinline__ void rs_store4(unsigned char* row, int x, int WB, const int (&acc)[4], bool vec) {
   if (vec && x + 4 <= WB) {
-    *reinterpret_cast<unsigned*>(row + x) = rs_clip8(acc[0]) | (rs_clip8(acc[1]) << 8) | (rs_clip8(acc[2]) << 16) | (rs_clip8(acc[3]) << 24);
+    // The first byte is kept opaque until the word is put together.  Left to itself the compiler folds clip8(a) | clip8(b) << 8 into
+    // one v_ashr_pk_u8_i32 and then ORs its whole destination register into the word, but the instruction writes 16 bits and leaves
+    // the upper half as it was: the word was right only where the register allocator had left zeros there (seen on an MI355X:
+    // bits 16 .. 31 of acc[0] in bytes 2 and 3 of every word, once the kernel's body moved into a function).
+    unsigned b0 = rs_clip8(acc[0]);
+    asm volatile("" : "+v"(b0));
+    *reinterpret_cast<unsigned*>(row + x) = b0 | (rs_clip8(acc[1]) << 8) | (rs_clip8(acc[2]) << 16) | (rs_clip8(acc[3]) << 24);
   } else {
 #pragma unroll
     for (int e = 0; e < 4; ++e)
@@ -84,12 +118,11 @@ __device__ __forceinline__ void rs_store4(unsigned char* row, int x, int WB, con
   }
 }
 
-// in [N][H0][WB] bytes -> out [N][H1][WB]; a thread owns four consecutive bytes of an output row.  vec: WB % 4 == 0 and both
-// pointers 4-byte aligned, so every row starts on a word.
-__global__ __launch_bounds__(256) void rs_v_kernel(const unsigned char* __restrict__ in, int H0, int H1, int WB, int G, long total,
-                                                   const int* __restrict__ yb, const int* __restrict__ yk, int yks,
-                                                   unsigned char* __restrict__ out, int vec) {
-  const long idx = static_cast<long>(blockIdx.x) * 256 + threadIdx.x;
+// in [N][H0][WB] bytes -> out [..][H1][WB]; a thread owns four consecutive bytes of an output row (item idx), frame n goes to
+// frame rs_slot(n) of out.  vec: WB % 4 == 0 and both pointers 4-byte aligned, so every row starts on a word.
+__device__ __forceinline__ void rs_v_body(const unsigned char* __restrict__ in, int H0, int H1, int WB, int G, long total,
+                                          const int* __restrict__ yb, const int* __restrict__ yk, int yks, unsigned char* __restrict__ out,
+                                          int vec, long idx, const int* __restrict__ dst, int nslots) {
   if (idx >= total) return;
   const int g = static_cast<int>(idx % G);
   const long r = idx / G;
@@ -113,7 +146,13 @@ __global__ __launch_bounds__(256) void rs_v_kernel(const unsigned char* __restri
       rs_mad4(w, k[t], acc);
     }
   }
-  rs_store4(out + (n * H1 + yo) * WB, 4 * g, WB, acc, vec != 0);
+  rs_store4(out + (rs_slot(dst, nslots, n) * H1 + yo) * WB, 4 * g, WB, acc, vec != 0);
+}
+
+__global__ __launch_bounds__(256) void rs_v_kernel(const unsigned char* __restrict__ in, int H0, int H1, int WB, int G, long total,
+                                                   const int* __restrict__ yb, const int* __restrict__ yk, int yks,
+                                                   unsigned char* __restrict__ out, int vec) {
+  rs_v_body(in, H0, H1, WB, G, total, yb, yk, yks, out, vec, static_cast<long>(blockIdx.x) * 256 + threadIdx.x, nullptr, 0);
 }
 
 // What the host fixes per launch of the fused form (rs_plan): band rows, the LDS image's rows and pitch, source rows per round,
@@ -124,19 +163,20 @@ struct RsPlan {
   long lds;
 };
 
+// One band of the fused form: output rows y0 .. y0 + pl.band - 1 of frame n of `in`, written to frame `on` of `out`; rs_smem is
+// the workgroup's pl.lds bytes of LDS, 16-byte aligned.
 template <int C>
-__global__ __launch_bounds__(RS_THREADS) void rs_fused_kernel(const unsigned char* __restrict__ in, int H0, int W0, int H1, int W1,
-                                                              const int* __restrict__ xb, const int* __restrict__ xk, int xks,
-                                                              const int* __restrict__ yb, const int* __restrict__ yk, int yks,
-                                                              RsPlan pl, unsigned char* __restrict__ out, int vec) {
-  extern __shared__ __align__(16) unsigned char rs_smem[];
+__device__ __forceinline__ void rs_fused_body(unsigned char* rs_smem, const unsigned char* __restrict__ in, int H0, int W0, int H1, int W1,
+                                              const int* __restrict__ xb, const int* __restrict__ xk, int xks,
+                                              const int* __restrict__ yb, const int* __restrict__ yk, int yks, const RsPlan& pl,
+                                              unsigned char* __restrict__ out, int vec, int n, int y0, long on) {
   int* sxb = reinterpret_cast<int*>(rs_smem);                  // [W1][2]   clamped (xmin, count)
   int* sxk = sxb + 2 * W1;                                     // [W1][xks]
   int* syb = reinterpret_cast<int*>(rs_smem + pl.off_yb);      // [band][2]
   int* syk = reinterpret_cast<int*>(rs_smem + pl.off_yk);      // [band][yks]
   unsigned char* tmp = rs_smem + pl.off_tmp;                   // [R][pitch]  the horizontally resampled rows of this band
   unsigned char* stage = rs_smem + pl.off_stage;               // S source rows, at the global address's offset within 16 bytes
-  const int t = threadIdx.x, n = blockIdx.y, y0 = blockIdx.x * pl.band;
+  const int t = threadIdx.x;
   const int nb = H1 - y0 < pl.band ? H1 - y0 : pl.band;
   const int WB = W1 * C;
   const long row_bytes = static_cast<long>(W0) * C;
@@ -206,8 +246,70 @@ __global__ __launch_bounds__(RS_THREADS) void rs_fused_kernel(const unsigned cha
       const int row = rs_clampi(lo + q, 0, nrows - 1);
       rs_mad4(*reinterpret_cast<const unsigned*>(tmp + row * pl.pitch + 4 * g4), k[q], acc);      // the pitch is a multiple of 16
     }
-    rs_store4(out + (static_cast<long>(n) * H1 + y0 + j) * WB, 4 * g4, WB, acc, vec != 0);
+    rs_store4(out + (on * H1 + y0 + j) * WB, 4 * g4, WB, acc, vec != 0);
   }
+}
+
+template <int C>
+__global__ __launch_bounds__(RS_THREADS) void rs_fused_kernel(const unsigned char* __restrict__ in, int H0, int W0, int H1, int W1,
+                                                              const int* __restrict__ xb, const int* __restrict__ xk, int xks,
+                                                              const int* __restrict__ yb, const int* __restrict__ yk, int yks,
+                                                              RsPlan pl, unsigned char* __restrict__ out, int vec) {
+  extern __shared__ __align__(16) unsigned char rs_smem[];
+  rs_fused_body<C>(rs_smem, in, H0, W0, H1, W1, xb, xk, xks, yb, yk, yks, pl, out, vec, blockIdx.y, blockIdx.x * pl.band, blockIdx.y);
+}
+
+// ---- the grouped forms: frames of several source sizes in one launch per form ------------------------------------------
+// The parameter block of one group in one launch, and the launch's argument: the blocks travel by value, so a launch takes at most
+// DIFFSAL_RESAMPLE_MAX_GROUPS of them.  first[g] is the first workgroup of group g (first[G]: the grid); a workgroup finds its
+// group by walking that table, which is uniform over the workgroup.
+struct RsGroup {
+  const unsigned char* in;
+  unsigned char* out;
+  const int *xb, *xk, *yb, *yk;
+  const int* dst;      // the group's slice of the dst table; NULL: `out` is already the group's first frame
+  int N, H0, W0, xks, yks, vec;
+  int per;             // fused: bands per frame
+  RsPlan pl;           // fused only
+};
+struct RsGroups {
+  int G, nslots, H1, W1;
+  unsigned first[DIFFSAL_RESAMPLE_MAX_GROUPS + 1];
+  RsGroup g[DIFFSAL_RESAMPLE_MAX_GROUPS];
+};
+
+__device__ __forceinline__ int rs_find_group(const RsGroups& a, unsigned wg) {
+  int g = 0;
+  while (g + 1 < a.G && wg >= a.first[g + 1]) ++g;
+  return g;
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void rs_h_groups_kernel(const RsGroups a) {
+  const int g = rs_find_group(a, blockIdx.x);
+  const RsGroup& p = a.g[g];
+  const long idx = static_cast<long>(blockIdx.x - a.first[g]) * 256 + threadIdx.x;
+  rs_h_body<C>(p.in, static_cast<long>(p.N) * p.H0, p.W0, a.W1, p.xb, p.xk, p.xks, p.out, idx, p.H0, p.dst, a.nslots);
+}
+
+template <int C>
+__global__ __launch_bounds__(256) void rs_v_groups_kernel(const RsGroups a) {
+  const int g = rs_find_group(a, blockIdx.x);
+  const RsGroup& p = a.g[g];
+  const long idx = static_cast<long>(blockIdx.x - a.first[g]) * 256 + threadIdx.x;
+  const int WB = a.W1 * C, G4 = (WB + 3) >> 2;
+  rs_v_body(p.in, p.H0, a.H1, WB, G4, static_cast<long>(p.N) * a.H1 * G4, p.yb, p.yk, p.yks, p.out, p.vec, idx, p.dst, a.nslots);
+}
+
+template <int C>
+__global__ __launch_bounds__(RS_THREADS) void rs_fused_groups_kernel(const RsGroups a) {
+  extern __shared__ __align__(16) unsigned char rs_smem[];
+  const int g = rs_find_group(a, blockIdx.x);
+  const RsGroup& p = a.g[g];
+  const unsigned local = blockIdx.x - a.first[g];
+  const int n = static_cast<int>(local / p.per), band = static_cast<int>(local - static_cast<unsigned>(n) * p.per);
+  rs_fused_body<C>(rs_smem, p.in, p.H0, p.W0, a.H1, a.W1, p.xb, p.xk, p.xks, p.yb, p.yk, p.yks, p.pl, p.out, p.vec, n, band * p.pl.band,
+                   rs_slot(p.dst, a.nslots, n));
 }
 
 template <int C>
@@ -433,6 +535,210 @@ extern "C" int diffsal_resample_u8(const unsigned char* in, int N, int H0, int W
     else rs_launch_fused<1>(s, in, N, H0, W0, H1, W1, xbounds, xkk, xks, ybounds, ykk, yks, pl, out);
   }
   return check_launch("resample_u8");
+}
+
+// ---- grouped call ---------------------------------------------------------------------------------------------------------
+
+namespace diffsal {
+
+enum RsKind { RS_COPY, RS_H, RS_V, RS_TWO, RS_FUSED };
+
+// What one group of the grouped call runs and its checks, which are those of diffsal_resample_u8 with band_rows = 0.
+static int rs_group_kind(const char* what, int g, const diffsal_resample_group& gr, int C, int H1, int W1, int filter, int form, RsKind& kind,
+                         RsPlan& pl) {
+  const int rc = rs_check_shape(what, gr.N, gr.H0, gr.W0, C, H1, W1, filter);
+  if (rc != DIFFSAL_OK) return rc;
+  const int H0 = gr.H0, W0 = gr.W0;
+  const bool do_x = W0 != W1, do_y = H0 != H1;
+  DS_REQUIRE(static_cast<long>(gr.N) * H0 * (W0 > W1 ? W0 : W1) < (1L << 38) && static_cast<long>(gr.N) * H1 * W1 < (1L << 38), DIFFSAL_E_SHAPE,
+             "%s: group %d: %d frames of %dx%d -> %dx%d are more pixels than one launch takes (2^38)", what, g, gr.N, H0, W0, H1, W1);
+  DS_REQUIRE(!do_x || gr.xks == rs_ksize(W0, W1, filter), DIFFSAL_E_SHAPE, "%s: group %d: %d coefficients per output column, %d -> %d takes %d",
+             what, g, gr.xks, W0, W1, rs_ksize(W0, W1, filter));
+  DS_REQUIRE(!do_y || gr.yks == rs_ksize(H0, H1, filter), DIFFSAL_E_SHAPE, "%s: group %d: %d coefficients per output row, %d -> %d takes %d",
+             what, g, gr.yks, H0, H1, rs_ksize(H0, H1, filter));
+  pl.band = 0;
+  if (do_x && do_y && form != DIFFSAL_RESAMPLE_TWO_PASS) {
+    pl = rs_plan(H0, W0, C, H1, W1, filter);
+    if (pl.lds > RS_LDS_MAX) pl.band = 0;
+    if (form == DIFFSAL_RESAMPLE_AUTO && !rs_auto_fused(H0, W0, H1, W1, pl)) pl.band = 0;
+    DS_REQUIRE(pl.band > 0 || form == DIFFSAL_RESAMPLE_AUTO, DIFFSAL_E_SHAPE,
+               "%s: group %d: a band of one output row of %dx%d -> %dx%d does not fit in %ld bytes of LDS: use the two-pass form", what, g, H0,
+               W0, H1, W1, RS_LDS_MAX);
+  }
+  kind = !do_x && !do_y ? RS_COPY : !do_y ? RS_H : !do_x ? RS_V : pl.band == 0 ? RS_TWO : RS_FUSED;
+  return DIFFSAL_OK;
+}
+
+static int rs_groups_check(const char* what, const diffsal_resample_group* groups, int G, int form) {
+  DS_REQUIRE(groups && G > 0, DIFFSAL_E_ARG, "%s: %d groups (at least one)", what, G);
+  DS_REQUIRE(form == DIFFSAL_RESAMPLE_AUTO || form == DIFFSAL_RESAMPLE_FUSED || form == DIFFSAL_RESAMPLE_TWO_PASS, DIFFSAL_E_ARG,
+             "%s: form %d (DIFFSAL_RESAMPLE_AUTO, _FUSED or _TWO_PASS)", what, form);
+  return DIFFSAL_OK;
+}
+
+// one launch of a grouped form; `blocks` counts the workgroups that a.first has been given so far
+struct RsBatch {
+  RsGroups a;
+  long blocks;
+  long lds;
+  void reset(int nslots, int H1, int W1) {
+    a.G = 0;
+    a.nslots = nslots;
+    a.H1 = H1;
+    a.W1 = W1;
+    a.first[0] = 0;
+    blocks = 0;
+    lds = 0;
+  }
+  void add(const RsGroup& p, long nblocks) {
+    a.g[a.G] = p;
+    blocks += nblocks;
+    a.first[++a.G] = static_cast<unsigned>(blocks);
+  }
+};
+
+}  // namespace diffsal
+
+extern "C" size_t diffsal_resample_u8_groups_ws_bytes(const diffsal_resample_group* groups, int G, int C, int H1, int W1, int filter,
+                                                      int form) {
+  if (rs_groups_check("resample_u8_groups_ws_bytes", groups, G, form) != DIFFSAL_OK) return 0;
+  size_t total = 0;
+  for (int g = 0; g < G; ++g) {
+    RsKind kind;
+    RsPlan pl;
+    if (rs_group_kind("resample_u8_groups_ws_bytes", g, groups[g], C, H1, W1, filter, form, kind, pl) != DIFFSAL_OK) return 0;
+    if (kind == RS_TWO) total += static_cast<size_t>(rs_up16(static_cast<long>(groups[g].N) * groups[g].H0 * W1 * C));
+  }
+  return total;
+}
+
+extern "C" int diffsal_resample_u8_groups_launches(const diffsal_resample_group* groups, int G, int C, int H1, int W1, int filter, int form) {
+  if (rs_groups_check("resample_u8_groups_launches", groups, G, form) != DIFFSAL_OK) return -1;
+  int launches = 0;
+  for (int g0 = 0; g0 < G; g0 += DIFFSAL_RESAMPLE_MAX_GROUPS) {
+    bool fused = false, hpass = false, vpass = false;
+    for (int g = g0; g < G && g < g0 + DIFFSAL_RESAMPLE_MAX_GROUPS; ++g) {
+      RsKind kind;
+      RsPlan pl;
+      if (rs_group_kind("resample_u8_groups_launches", g, groups[g], C, H1, W1, filter, form, kind, pl) != DIFFSAL_OK) return -1;
+      fused |= kind == RS_FUSED;
+      hpass |= kind == RS_COPY || kind == RS_H || kind == RS_TWO;
+      vpass |= kind == RS_V || kind == RS_TWO;
+    }
+    launches += fused + hpass + vpass;
+  }
+  return launches;
+}
+
+extern "C" int diffsal_resample_u8_groups(const diffsal_resample_group* groups, int G, int C, int H1, int W1, int filter, int form,
+                                          const int* dst, int n_total, unsigned char* out, void* ws, size_t ws_bytes,
+                                          diffsal_stream_t stream) {
+  const char* what = "resample_u8_groups";
+  int rc = rs_groups_check(what, groups, G, form);
+  if (rc != DIFFSAL_OK) return rc;
+  // every check of every group precedes the first launch
+  long frames = 0, pixels = 0;
+  size_t need = 0;
+  for (int g = 0; g < G; ++g) {
+    RsKind kind;
+    RsPlan pl;
+    rc = rs_group_kind(what, g, groups[g], C, H1, W1, filter, form, kind, pl);
+    if (rc != DIFFSAL_OK) return rc;
+    const diffsal_resample_group& gr = groups[g];
+    DS_REQUIRE(gr.in && (gr.W0 == W1 || (gr.xbounds && gr.xkk)) && (gr.H0 == H1 || (gr.ybounds && gr.ykk)), DIFFSAL_E_ARG,
+               "%s: group %d: null argument", what, g);
+    if (kind == RS_TWO) need += static_cast<size_t>(rs_up16(static_cast<long>(gr.N) * gr.H0 * W1 * C));
+    frames += gr.N;
+    pixels += static_cast<long>(gr.N) * gr.H0 * (gr.W0 > W1 ? gr.W0 : W1);
+  }
+  DS_REQUIRE(frames == n_total, DIFFSAL_E_SHAPE, "%s: the groups hold %ld frames, the output has n_total = %d", what, frames, n_total);
+  // so that no launch has 2^31 workgroups: a workgroup of the passes owns 256 pixels or more
+  DS_REQUIRE(pixels < (1L << 38) && static_cast<long>(n_total) * H1 * W1 < (1L << 38), DIFFSAL_E_SHAPE,
+             "%s: %d frames -> %dx%d are more pixels than one call takes (2^38)", what, n_total, H1, W1);
+  DS_REQUIRE(need == 0 || (ws_bytes >= need && ws), DIFFSAL_E_ARG, "%s: workspace too small: %zu bytes, the two-pass groups need %zu", what,
+             ws_bytes, need);
+  DS_REQUIRE(out, DIFFSAL_E_ARG, "%s: null argument", what);
+  const long frame_bytes = static_cast<long>(H1) * W1 * C;
+  for (int g = 0; g < G; ++g) {
+    const unsigned char* in = groups[g].in;
+    const long in_bytes = static_cast<long>(groups[g].N) * groups[g].H0 * groups[g].W0 * C;
+    DS_REQUIRE(in + in_bytes <= out || out + n_total * frame_bytes <= in, DIFFSAL_E_ARG, "%s: group %d overlaps the output", what, g);
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int WB = W1 * C, G4 = (WB + 3) / 4;
+  const bool out_vec = WB % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 3u) == 0;
+  RsBatch bf, bh, bv;      // ~2 KB each
+  long base = 0;
+  size_t ws_off = 0;
+  for (int g0 = 0; g0 < G; g0 += DIFFSAL_RESAMPLE_MAX_GROUPS) {
+    bf.reset(n_total, H1, W1);
+    bh.reset(n_total, H1, W1);
+    bv.reset(n_total, H1, W1);
+    for (int g = g0; g < G && g < g0 + DIFFSAL_RESAMPLE_MAX_GROUPS; ++g) {
+      const diffsal_resample_group& gr = groups[g];
+      RsKind kind;
+      RsPlan pl;
+      (void)rs_group_kind(what, g, gr, C, H1, W1, filter, form, kind, pl);
+      RsGroup p;
+      p.in = gr.in;
+      p.out = dst ? out : out + base * frame_bytes;
+      p.xb = gr.W0 == W1 ? nullptr : gr.xbounds;
+      p.xk = gr.W0 == W1 ? nullptr : gr.xkk;
+      p.yb = gr.H0 == H1 ? nullptr : gr.ybounds;
+      p.yk = gr.H0 == H1 ? nullptr : gr.ykk;
+      p.dst = dst ? dst + base : nullptr;
+      p.N = gr.N;
+      p.H0 = gr.H0;
+      p.W0 = gr.W0;
+      p.xks = gr.xks;
+      p.yks = gr.yks;
+      p.vec = out_vec;
+      p.per = 1;
+      p.pl = pl;
+      const long h_blocks = (static_cast<long>(gr.N) * gr.H0 * W1 + 255) / 256;
+      const long v_blocks = (static_cast<long>(gr.N) * H1 * G4 + 255) / 256;
+      if (kind == RS_FUSED) {
+        p.per = (H1 + pl.band - 1) / pl.band;
+        bf.add(p, static_cast<long>(gr.N) * p.per);
+        if (pl.lds > bf.lds) bf.lds = pl.lds;
+      } else if (kind == RS_COPY || kind == RS_H) {
+        bh.add(p, h_blocks);
+      } else if (kind == RS_V) {
+        p.vec = out_vec && (reinterpret_cast<uintptr_t>(gr.in) & 3u) == 0;
+        bv.add(p, v_blocks);
+      } else {      // two passes through the group's slice of the workspace, whose offset is a multiple of 16
+        unsigned char* mid = static_cast<unsigned char*>(ws) + ws_off;
+        ws_off += static_cast<size_t>(rs_up16(static_cast<long>(gr.N) * gr.H0 * W1 * C));
+        RsGroup ph = p;
+        ph.out = mid;
+        ph.dst = nullptr;
+        bh.add(ph, h_blocks);
+        p.in = mid;
+        bv.add(p, v_blocks);
+      }
+      base += gr.N;
+    }
+    if (bf.a.G) {
+      if (C == 3) {
+        DS_RAISE_DYNAMIC_LDS(rs_fused_groups_kernel<3>, static_cast<int>(RS_LDS_MAX));
+        hipLaunchKernelGGL((rs_fused_groups_kernel<3>), dim3(static_cast<unsigned>(bf.blocks)), dim3(RS_THREADS), static_cast<size_t>(bf.lds), s,
+                           bf.a);
+      } else {
+        DS_RAISE_DYNAMIC_LDS(rs_fused_groups_kernel<1>, static_cast<int>(RS_LDS_MAX));
+        hipLaunchKernelGGL((rs_fused_groups_kernel<1>), dim3(static_cast<unsigned>(bf.blocks)), dim3(RS_THREADS), static_cast<size_t>(bf.lds), s,
+                           bf.a);
+      }
+    }
+    if (bh.a.G) {
+      if (C == 3) hipLaunchKernelGGL((rs_h_groups_kernel<3>), dim3(static_cast<unsigned>(bh.blocks)), dim3(256), 0, s, bh.a);
+      else hipLaunchKernelGGL((rs_h_groups_kernel<1>), dim3(static_cast<unsigned>(bh.blocks)), dim3(256), 0, s, bh.a);
+    }
+    if (bv.a.G) {
+      if (C == 3) hipLaunchKernelGGL((rs_v_groups_kernel<3>), dim3(static_cast<unsigned>(bv.blocks)), dim3(256), 0, s, bv.a);
+      else hipLaunchKernelGGL((rs_v_groups_kernel<1>), dim3(static_cast<unsigned>(bv.blocks)), dim3(256), 0, s, bv.a);
+    }
+  }
+  return check_launch(what);
 }
 
 extern "C" int diffsal_clip_gather_u8(const unsigned char* frames, int N, int h, int w, int C, const int* indices, int B, int T,

@@ -362,6 +362,20 @@ def pack(files: Sequence) -> dict:
 decode_files = _image_files.file_decoder(decode)
 
 
+def decode_groups(files: Sequence, mode: str = "RGB", device=None):
+    """``decode`` for files that do not share one geometry (a shuffled training batch holds frames of several videos): the headers
+    are parsed, the files grouped by (height, width, components, luma sampling) and every group decoded in one ``decode`` call.
+    Returns ``(groups, where)``: the uint8 tensor of every group, in order of first appearance, and per file its
+    ``(group, position)``.  One read-back of all the files' status, as ``decode(strict=True)``."""
+    def geometry(f, i):
+        if not isinstance(f, (bytes, bytearray, memoryview)):
+            raise _Refused(f"expected bytes, bytearray or memoryview, got {type(f).__name__}")
+        return _parse_header(np.frombuffer(f, dtype=np.uint8))[1][:5]
+
+    return _image_files.decode_groups(files, mode, device, codec="jpeg", geometry=geometry, refused=_Refused, decode=decode,
+                                      status_bits=STATUS_BITS, noun="scan")
+
+
 def save_predictions(pred: Tensor, video_ids: Sequence, frame_ids: Sequence, root: str, quality: int = 95):
     """The reference's ``save_img`` for the audio-visual sets: ``<root>/<video id>/pred_sal_{frame id:06d}.jpg`` holding
     ``encode(postprocess.to_uint8(pred))``'s bytes.  One host copy of ``lengths``, then one of the used part of ``data``: nothing else leaves the device.  The

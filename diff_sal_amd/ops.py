@@ -2246,6 +2246,71 @@ def resample_u8(frames: Tensor, H1: int, W1: int, filter_id: int, xtab, ytab, *,
     return out
 
 
+RESAMPLE_MAX_GROUPS = _lib.K["DIFFSAL_RESAMPLE_MAX_GROUPS"]
+
+
+def _resample_tab(tab, n_out: int, what: str):
+    if tab is None:
+        return None, None, 0
+    b, k = tab
+    for t in (b, k):
+        if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 2 or t.shape[0] != n_out:
+            raise ValueError(f"{what}: a table must be contiguous int32 GPU tensors with {n_out} rows, got {t.dtype} {t.device} "
+                             f"{tuple(t.shape)}")
+    if b.shape[1] != 2:
+        raise ValueError(f"{what}: bounds must be [n_out, 2], got {tuple(b.shape)}")
+    return b.data_ptr(), k.data_ptr(), k.shape[1]
+
+
+def _resample_group_array(groups, xtabs, ytabs, H1: int, W1: int):
+    groups = [_u8_frames(g, f"groups[{i}]") for i, g in enumerate(groups)]
+    if not groups:
+        raise ValueError("resample_u8_groups: at least one group")
+    dev, Cc = groups[0].device, groups[0].shape[3]
+    arr = (_lib.ResampleGroup * len(groups))()
+    for i, (g, xt, yt) in enumerate(zip(groups, xtabs, ytabs)):
+        if g.device != dev or g.shape[3] != Cc:
+            raise ValueError(f"resample_u8_groups: the groups share one device and one channel count; groups[{i}] is {g.device} "
+                             f"{tuple(g.shape)}, groups[0] {dev} {tuple(groups[0].shape)}")
+        a = arr[i]
+        a.N, a.H0, a.W0 = g.shape[0], g.shape[1], g.shape[2]
+        setattr(a, "in", g.data_ptr())
+        a.xbounds, a.xkk, a.xks = _resample_tab(xt, W1, "resample_u8_groups")
+        a.ybounds, a.ykk, a.yks = _resample_tab(yt, H1, "resample_u8_groups")
+    return groups, arr, dev, Cc
+
+
+def resample_u8_groups_launches(groups, H1: int, W1: int, filter_id: int, xtabs, ytabs, *, form: int = RESAMPLE_AUTO) -> int:
+    """``diffsal_resample_u8_groups_launches``: the kernel launches ``resample_u8_groups`` makes for these groups."""
+    groups, arr, _, Cc = _resample_group_array(groups, xtabs, ytabs, int(H1), int(W1))
+    n = _lib.load().diffsal_resample_u8_groups_launches(arr, len(groups), Cc, int(H1), int(W1), int(filter_id), int(form))
+    if n < 0:
+        _lib.check(n, "resample_u8_groups_launches")
+    return n
+
+
+def resample_u8_groups(groups, H1: int, W1: int, filter_id: int, xtabs, ytabs, *, form: int = RESAMPLE_AUTO,
+                       dst: Optional[Tensor] = None) -> Tensor:
+    """``diffsal_resample_u8_groups`` (include/diffsal.h, "video front end"): ``groups`` a sequence of uint8 ``[N_g, H_g, W_g, C]``,
+    xtabs / ytabs one table pair (or None) per group as for ``resample_u8`` -> uint8 ``[sum N_g, H1, W1, C]``.  ``dst``: int32
+    GPU tensor ``[sum N_g]``, the output frame of every input frame in group order (None: that order)."""
+    lib = _lib.load()
+    H1, W1 = int(H1), int(W1)
+    groups, arr, dev, Cc = _resample_group_array(groups, xtabs, ytabs, H1, W1)
+    G, total = len(groups), sum(g.shape[0] for g in groups)
+    if dst is not None and (not dst.is_cuda or dst.dtype != torch.int32 or not dst.is_contiguous() or dst.numel() != total):
+        raise ValueError(f"resample_u8_groups: dst must be a contiguous int32 GPU tensor of {total} entries, got {dst.dtype} {dst.device} "
+                         f"{tuple(dst.shape)}")
+    out = torch.empty((total, H1, W1, Cc) if H1 > 0 and W1 > 0 else (0,), device=dev, dtype=torch.uint8)
+    nws = lib.diffsal_resample_u8_groups_ws_bytes(arr, G, Cc, H1, W1, int(filter_id), int(form))
+    ws = torch.empty((nws,), device=dev, dtype=torch.uint8) if nws else None
+    with _prof("video_input", 0.0, _nb(out, *groups) + 2 * nws):
+        _lib.check(lib.diffsal_resample_u8_groups(arr, G, Cc, H1, W1, int(filter_id), int(form), None if dst is None else dst.data_ptr(),
+                                                  total, out.data_ptr(), None if ws is None else ws.data_ptr(), nws, _stream()),
+                   "resample_u8_groups")
+    return out
+
+
 def clip_gather_u8(frames: Tensor, indices: Optional[Tensor], B: int, T: int, table: Tensor) -> Tensor:
     """``diffsal_clip_gather_u8`` on frames [N, h, w, C] uint8, indices int32 [B, T] (None: frame b * T + t), table fp32 [C, 256]
     -> fp32 [B, C, T, h, w] = table[c, frames[indices[b, t], y, x, c]]."""

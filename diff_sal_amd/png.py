@@ -188,6 +188,19 @@ def decode(files: Sequence, mode: str = "RGB", device=None, strict: bool = True)
 decode_files = _image_files.file_decoder(decode)
 
 
+def decode_groups(files: Sequence, mode: str = "RGB", device=None):
+    """``decode`` for files that do not share one geometry (a shuffled training batch holds frames of several videos): the chunk
+    headers are parsed, the files grouped by (height, width, colour type, bit depth) and every group decoded in one ``decode``
+    call.  Returns ``(groups, where)``: the uint8 tensor of every group, in order of first appearance, and per file its
+    ``(group, position)``.  One read-back of all the files' status, as ``decode(strict=True)``."""
+    def geometry(f, i):
+        p = _parse(_bytes_of(f, i))
+        return p["H"], p["W"], p["color_type"], p["bit_depth"]
+
+    return _image_files.decode_groups(files, mode, device, codec="png", geometry=geometry, refused=_Refused, decode=decode,
+                                      status_bits=STATUS_BITS, noun="stream")
+
+
 # ---- export: 8-bit maps -> complete .png files (csrc/png_encode.hip, include/diffsal.h "PNG export") ----
 def _limit(shape):
     if shape[0] > 65535 or shape[1] > 65535 or shape[2] > MAX_WIDTH:

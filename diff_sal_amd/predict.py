@@ -349,7 +349,7 @@ class _eval_mode:
 def predict_directory(model, sampler, data_type: str, root: str, out_root: str, *, batch: int = 4, size=video_input.SAMPLE_SIZE,
                       fmt: str = "png", videos: Optional[Sequence] = None, losses: bool = False, loss_config=None, group=None,
                       norm_value=255, mean=video_input.IMAGENET_MEAN, std=video_input.IMAGENET_STD, threads: int = 16,
-                      **list_kwargs) -> Report:
+                      write: bool = True, **list_kwargs) -> Report:
     """The reference's ``test()`` (R/diffusion_trainer.py:714-765) for ``list_clips(data_type, root, videos=videos,
     **list_kwargs)``: writes ``<out_root>/<video>/<gt_index>.png`` for every clip, the layout ``evaluate.pair_files`` expects under
     a task folder, and returns a ``Report``.
@@ -370,7 +370,10 @@ def predict_directory(model, sampler, data_type: str, root: str, out_root: str, 
     ``test()`` returns and a training loop picks ``best.pth`` by.  ``loss_config=None`` leaves ``main`` (the KL term) at zero.
 
     ``group`` (a ``torch.distributed`` process group): the videos are divided over its ranks with ``dist.shard_range``, every rank
-    writes its own files and reports its own clips, and the loss sums are all-reduced, so ``losses`` is the same on every rank."""
+    writes its own files and reports its own clips, and the loss sums are all-reduced, so ``losses`` is the same on every rank.
+
+    ``write=False`` writes nothing (``out_root`` is not used, ``Report.files`` stays empty): the validation pass of a training loop,
+    ``save_img=False`` of the reference's ``test()``."""
     from . import png, postprocess, sal_losses
 
     device, batch, size = _checked(model, sampler, batch, size)
@@ -394,7 +397,8 @@ def predict_directory(model, sampler, data_type: str, root: str, out_root: str, 
                 pred = _sample(sampler, img, None, [clip_id(video, c.gt_index) for c in chunk], device)
                 if losses:
                     meter.update(sal_losses.get_kl_cc_sim_loss_wo_weight(loss_config, pred, targets[lo:lo + batch]))
-                report.files += save(pred, [video] * len(chunk), [c.gt_index for c in chunk], out_root)
+                if write:
+                    report.files += save(pred, [video] * len(chunk), [c.gt_index for c in chunk], out_root)
                 report.clips += len(chunk)
     if losses:
         report.losses, report.chunks = meter.means(device, group)
@@ -404,7 +408,7 @@ def predict_directory(model, sampler, data_type: str, root: str, out_root: str, 
 @torch.no_grad()
 def predict_av(model, sampler, clips_or_args, out_root: str, *, batch: int = 4, size=video_input.SAMPLE_SIZE, quality: int = 95,
                losses: bool = False, loss_config=None, group=None, window: Optional[int] = None, resample="kaiser_best",
-               threads: int = 16) -> Report:
+               threads: int = 16, write: bool = True) -> Report:
     """The reference's ``test_av_data()`` loop for one set and one fold (R/diffusion_trainer.py:823-896): ``clips_or_args`` is a
     list of ``AVClip`` or the ``(video_root, fold_list, salmap_root, audio_root)`` ``list_av_clips`` takes.  Writes
     ``<out_root>/<set's folder>/<video>/pred_sal_%06d.jpg`` of the clip's median frame number through ``jpeg.save_predictions`` at
@@ -422,8 +426,8 @@ def predict_av(model, sampler, clips_or_args, out_root: str, *, batch: int = 4, 
 
     The clips' ``eyeMap`` files are decoded (``"L"``) and made targets with ``video_input.target_maps`` whether or not losses are
     asked for: a clip whose target is all zero is skipped -- no sample, no file, no loss -- and listed in ``Report.skipped`` (one
-    read-back of a flag per clip and video).  Chunks, ``clip_id("<set>/<video>", gt_index)``, ``losses``, ``loss_config`` and
-    ``group`` are as in ``predict_directory``."""
+    read-back of a flag per clip and video).  Chunks, ``clip_id("<set>/<video>", gt_index)``, ``losses``, ``loss_config``,
+    ``group`` and ``write`` are as in ``predict_directory``."""
     from . import audio_input, jpeg, sal_losses
 
     device, batch, size = _checked(model, sampler, batch, size)
@@ -473,7 +477,9 @@ def predict_av(model, sampler, clips_or_args, out_root: str, *, batch: int = 4, 
                 pred = _sample(sampler, img, audio, [clip_id(c.video_id, c.gt_index) for c in chunk], device)
                 if losses:
                     meter.update(sal_losses.get_kl_cc_sim_loss_wo_weight(loss_config, pred, targets[at]))
-                report.files += jpeg.save_predictions(pred, [folders[c.video_id]] * len(chunk), [c.gt_index for c in chunk], out_root, quality)
+                if write:
+                    report.files += jpeg.save_predictions(pred, [folders[c.video_id]] * len(chunk), [c.gt_index for c in chunk], out_root,
+                                                          quality)
                 report.clips += len(chunk)
     if losses:
         report.losses, report.chunks = meter.means(device, group)

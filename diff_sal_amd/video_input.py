@@ -22,7 +22,8 @@ horizontal and the vertical pass), and ``ToTensor`` / ``Normalize`` see only 256
 
 JPEG decoding with ``convert('RGB' | 'L')`` is ``jpeg.decode`` / ``jpeg.decode_files``, whose output is the ``frames`` taken here; the
 visual sets' PNG frames and maps are decoded the same way by ``png.decode`` / ``png.decode_files``.  Only the bilinear and bicubic filters are built; all
-frames of a call share one source size.  Indices given on the host (a sequence, a numpy array, a CPU tensor) are range-checked
+frames of a call share one source size, except in ``resize_groups`` / ``transform_groups`` / ``target_maps_groups``, which take one
+tensor per source size (a shuffled training batch holds clips of several videos) and still make a fixed number of launches.  Indices given on the host (a sequence, a numpy array, a CPU tensor) are range-checked
 here and uploaded; a GPU tensor is used as it is, with no host copy and no synchronisation (the kernel clamps what could not be
 checked), so the call can be captured in a graph.  The first call for a size, filter or normalisation uploads its tables from
 host memory, which a capture does not allow: call once, or ``warm(device, ...)``, before capturing.  GPU only: a CPU ``frames``
@@ -275,6 +276,74 @@ def transform_frames(frames: Tensor, size, pre_size=None, pre_filter: str = "bic
     if pre_size is not None:
         x = resize_u8(x, pre_size, pre_filter, fused)
     return resize_u8(x, size, filter, fused)
+
+
+def _dst(dst, total: int, device) -> Optional[Tensor]:
+    """The ``dst`` table of the grouped calls: a host sequence is range-checked and uploaded, a GPU tensor is used as it is."""
+    if dst is None:
+        return None
+    if isinstance(dst, Tensor) and dst.is_cuda:
+        if dst.dim() != 1 or dst.numel() != total or dst.is_floating_point() or dst.dtype == torch.bool:
+            raise ValueError(f"video_input: dst must be {total} integers, got {dst.dtype} {tuple(dst.shape)}")
+        return dst.to(torch.int32).contiguous()
+    a = np.asarray(dst.numpy() if isinstance(dst, Tensor) else dst)
+    if a.ndim != 1 or a.size != total or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError(f"video_input: dst must be {total} integers, one per frame of the groups, got {a.dtype} {a.shape}")
+    if (a < 0).any() or (a >= total).any():
+        raise ValueError(f"video_input: dst entry outside 0 .. {total - 1}")
+    return torch.from_numpy(a.astype(np.int32)).to(device)
+
+
+def _group_list(groups, what: str = "groups"):
+    if isinstance(groups, Tensor) or len(groups) == 0:
+        raise ValueError(f"video_input: {what} must be a non-empty sequence of uint8 tensors [N, H, W, C]")
+    return [ops._u8_frames(g, f"{what}[{i}]") for i, g in enumerate(groups)]
+
+
+def resize_groups(groups, size, filter: str = "bilinear", fused: Optional[bool] = None, dst=None) -> Tensor:
+    """``resize_u8`` of frames of several source sizes in one call: ``groups`` is a sequence of uint8 ``[N_g, H_g, W_g, C]`` (one C),
+    the result uint8 ``[sum N_g, h, w, C]``.  Frame ``i`` of the concatenated groups lands at ``dst[i]`` (a permutation of
+    ``range(sum N_g)``; None: at ``i``).  Group ``g``'s frames are bit-equal to ``resize_u8(groups[g], size, filter, fused)``, and
+    each group takes the form that call would take.  The launches do not grow with the number of groups: at most three (fused
+    bands, horizontal pass, vertical pass) per ``ops.RESAMPLE_MAX_GROUPS`` groups.  ``dst`` given on the host is range-checked here,
+    before any launch; a GPU tensor is used as it is (the kernels clamp it)."""
+    fid = _filter_id(filter)
+    if fused not in _FORMS:
+        raise ValueError(f"video_input: fused must be None, True or False, got {fused!r}")
+    h, w = _hw(size)
+    xs = _group_list(groups)
+    dev = xs[0].device
+    d = _dst(dst, sum(x.shape[0] for x in xs), dev)
+    xt = [device_table(dev, x.shape[2], w, filter) for x in xs]
+    yt = [device_table(dev, x.shape[1], h, filter) for x in xs]
+    return ops.resample_u8_groups(xs, h, w, fid, xt, yt, form=_FORMS[fused], dst=d)
+
+
+def transform_groups(groups, size, pre_size=None, pre_filter: str = "bicubic", filter: str = "bilinear", fused: Optional[bool] = None,
+                     dst=None) -> Tensor:
+    """``transform_frames`` of frames of several source sizes: the first resize of the chain is the grouped call; with ``pre_size``
+    the second one has a single source size and is the existing call.  A single group in its own order goes through
+    ``transform_frames``, the one-size route, which gives the same bytes."""
+    xs = _group_list(groups)
+    if len(xs) == 1 and dst is None:
+        return transform_frames(xs[0], size, pre_size, pre_filter, filter, fused)
+    if pre_size is not None:
+        return resize_u8(resize_groups(xs, pre_size, pre_filter, fused, dst), size, filter, fused)
+    return resize_groups(xs, size, filter, fused, dst)
+
+
+def target_maps_groups(groups, size=SAMPLE_SIZE, filter: str = "bilinear", fused: Optional[bool] = None, dst=None) -> Tensor:
+    """``target_maps`` of annotation maps of several sizes: ``groups`` a sequence of uint8 ``[N_g, H_g, W_g]`` (or ``[..., 1]``) ->
+    float32 ``[sum N_g, 1, h, w]``, map ``i`` of the concatenated groups at ``dst[i]``."""
+    if isinstance(groups, Tensor) or len(groups) == 0:
+        raise ValueError("video_input: groups must be a non-empty sequence of uint8 maps [N, H, W]")
+    xs = [g[..., None] if isinstance(g, Tensor) and g.dim() == 3 else g for g in groups]
+    xs = _group_list(xs)
+    if any(x.shape[3] != 1 for x in xs):
+        raise ValueError(f"video_input: target_maps_groups takes single-channel maps, got {[tuple(x.shape) for x in xs]}")
+    r = resize_u8(xs[0], size, filter, fused) if len(xs) == 1 and dst is None else resize_groups(xs, size, filter, fused, dst)
+    N, h, w, _ = r.shape
+    return ops.clip_gather_u8(r, None, N, 1, _lut(r.device, None, None, None, None)).view(N, 1, h, w)
 
 
 def _indices(indices, n_frames: int, device) -> Tuple[Tensor, int, int]:

@@ -1155,7 +1155,7 @@ int diffsal_resample_excerpts(const void* wav, int wav_dtype, int V, long Lmax, 
  * The kernels do integer work only.  Horizontal pass first, every channel alike:
  *   mid[y][o] = clip8((2^21 + sum_{t < count} in[y][xmin + t] * kk[o][t]) >> 22)      int32 sum, arithmetic shift, clip to 0..255
  * then the vertical pass the same way on the uint8 image `mid`.  An axis whose size does not change runs no pass (its tables may
- * be NULL); equal sizes make the call a copy.  All N frames share the source size.
+ * be NULL); equal sizes make the call a copy.  All N frames share the source size (diffsal_resample_u8_groups: several sizes).
  * form: DIFFSAL_RESAMPLE_FUSED is one launch: a workgroup owns band_rows output rows over the full width, resamples the source
  * rows they need horizontally into LDS and runs the vertical pass out of LDS (band_rows = 0: the library picks it from the LDS
  * budget, diffsal_resample_u8_band_rows; at most 32; DIFFSAL_E_SHAPE if the band does not fit in 160 KB).
@@ -1170,6 +1170,25 @@ int diffsal_resample_excerpts(const void* wav, int wav_dtype, int V, long Lmax, 
  * ToTensor and Normalize are matched bit for bit: the caller evaluates the reference's own float32 operations on the 256 byte
  * values per channel (x / norm_value, then - mean, then / std) and the kernel only indexes.  C = 1, T = 1, indices NULL and
  * table[v] = v / 255 is the target path.  An index outside [0, N) is clamped (check it on the host where it is known there).
+ *
+ * diffsal_resample_u8_groups: frames of G source sizes to one output size in one call.  `groups` is a HOST array of G blocks;
+ * group g holds N frames [N][H0][W0][C] at its own device pointer `in` with its own tables (as for diffsal_resample_u8; NULL for
+ * an axis that does not change).  C, (H1, W1) and the filter are shared.  out is [n_total][H1][W1][C] with n_total the sum of the
+ * groups' N.  dst (device memory, int32 [n_total], or NULL) names the output frame of every input frame, the groups' frames
+ * counted in group order; NULL: that order itself.  Group g's frames are, byte for byte, what diffsal_resample_u8 gives for that
+ * group alone with band_rows = 0 and the same `form`; each group takes the form that call would take, so DIFFSAL_RESAMPLE_AUTO
+ * may run some groups fused and others in two passes.
+ * Launches: the group blocks travel by value in the launch arguments, DIFFSAL_RESAMPLE_MAX_GROUPS of them at most.  Every run of
+ * that many groups takes at most one launch of each of three kernels, however many groups it holds: the fused bands of its fused
+ * groups; the horizontal pass (two-pass groups into the workspace, groups whose height does not change into `out`, and groups
+ * whose size does not change at all, which are copied there); the vertical pass (two-pass groups out of the workspace, groups
+ * whose width does not change).  A workgroup finds its (group, frame, band or tile) through a prefix table of the groups'
+ * workgroup counts; the fused launch holds the largest LDS of its groups' plans.  diffsal_resample_u8_groups_launches is that
+ * count (-1: bad argument).  ws holds the two-pass groups' intermediate images, each rounded up to 16 bytes
+ * (diffsal_resample_u8_groups_ws_bytes).
+ * The clamping contract holds: dst cannot be checked by the host, so an entry is clamped to [0, n_total); an entry named twice
+ * leaves one of the two frames there.  A wrong table or dst gives wrong pixels, never an access outside the buffers.
+ *
  * All calls: no atomics, no allocation, no synchronisation, bit-reproducible, graph-safe; all argument checks precede the
  * launch. */
 #define DIFFSAL_FILTER_BILINEAR 0
@@ -1185,6 +1204,21 @@ int diffsal_resample_u8(const unsigned char* in, int N, int H0, int W0, int C, i
                         unsigned char* out, void* ws, size_t ws_bytes, diffsal_stream_t stream);
 int diffsal_clip_gather_u8(const unsigned char* frames, int N, int h, int w, int C, const int* indices, int B, int T,
                            const float* table, float* out, diffsal_stream_t stream);
+#define DIFFSAL_RESAMPLE_MAX_GROUPS 16      /* groups per launch; a call with more is split into runs of this many */
+typedef struct diffsal_resample_group {
+  const unsigned char* in;      /* [N][H0][W0][C], device memory */
+  int N, H0, W0;
+  const int* xbounds;           /* [W1][2], [W1][xks]; NULL where W0 == W1 */
+  const int* xkk;
+  int xks;
+  const int* ybounds;           /* [H1][2], [H1][yks]; NULL where H0 == H1 */
+  const int* ykk;
+  int yks;
+} diffsal_resample_group;
+size_t diffsal_resample_u8_groups_ws_bytes(const diffsal_resample_group* groups, int G, int C, int H1, int W1, int filter, int form);
+int diffsal_resample_u8_groups_launches(const diffsal_resample_group* groups, int G, int C, int H1, int W1, int filter, int form);
+int diffsal_resample_u8_groups(const diffsal_resample_group* groups, int G, int C, int H1, int W1, int filter, int form,
+                               const int* dst, int n_total, unsigned char* out, void* ws, size_t ws_bytes, diffsal_stream_t stream);
 
 /* ---- K15: sampler elementwise update out = a*x + b*y + c*z  (y, z may be NULL) -----------
  * scalar-coefficient axpys of R/diffusion_trainer.py:459-478 and R/models/dpm_solver/sampler.py:548-593,816-853. */
