@@ -7,6 +7,8 @@
 // The clip coefficient never visits the host: adam reads the norm the previous kernel left in device memory.
 #include "common.h"
 
+#include <cstring>
+
 namespace diffsal {
 namespace {
 
@@ -123,9 +125,10 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
   p = fmaf(-a.step_size, m / denom, p);              // param.addcdiv_(exp_avg, denom, value=-step_size)
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                                   float* __restrict__ v, const float* __restrict__ norm, long n4,
-                                                   long n, AdamArgs a, int store_grad) {
+// The update loop of both kernels below: the grid-stride float4 walk, then the tail of 1 to 3 elements in block 0.
+__device__ __forceinline__ void adam_walk(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                          float* __restrict__ v, const float* __restrict__ norm, long n4, long n,
+                                          const AdamArgs& a, int store_grad) {
   // clip_grad_norm_: coef = min(1, max_norm / (total_norm + 1e-6)); the DDP average is folded in as gscale
   float coef = a.gscale;
   if (norm != nullptr && a.max_norm > 0.f) coef *= fminf(1.f, a.max_norm / (norm[0] + 1e-6f));
@@ -147,6 +150,29 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float*
     p[i] = pv; m[i] = mv; v[i] = vv;
     if (store_grad) g[i] = gv * coef;
   }
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                   float* __restrict__ v, const float* __restrict__ norm, long n4,
+                                                   long n, AdamArgs a, int store_grad) {
+  adam_walk(p, g, m, v, norm, n4, n, a, store_grad);
+}
+
+// Same update with the nine numbers read from device memory: one load of the block per wave, from an address every lane
+// shares (a kernel argument), into registers before the walk.  A captured graph replays this launch with whatever the
+// host wrote into `args` before the replay.
+__global__ __launch_bounds__(256) void adam_args_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                        float* __restrict__ v, const float* __restrict__ norm, long n4,
+                                                        long n, const AdamArgs* __restrict__ args, int store_grad) {
+  const AdamArgs a = *args;
+  adam_walk(p, g, m, v, norm, n4, n, a, store_grad);
+}
+
+int adam_grid(long n) {
+  long need = (n / 4 + 255) / 256;
+  if (need < 1) need = 1;
+  const int grid = static_cast<int>(need < 256L * 16 ? need : 256L * 16);
+  return grid;
 }
 
 int red_grid(long n4, int blocks) {
@@ -196,13 +222,12 @@ extern "C" int diffsal_grad_norm(const float* g, long n, float gscale, float* no
   return check_launch("grad_norm");
 }
 
-extern "C" int diffsal_adam_step(float* p, float* g, float* m, float* v, long n, double lr, double beta1, double beta2,
-                                 double eps, double weight_decay, int step, float gscale, const float* norm, float max_norm,
-                                 int store_clipped_grad, diffsal_stream_t stream) {
-  DS_REQUIRE(p && g && m && v, DIFFSAL_E_ARG, "adam_step: null argument");
-  DS_REQUIRE(n > 0 && step >= 1, DIFFSAL_E_SHAPE, "adam_step: need n > 0 and step >= 1");
-  DS_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), DIFFSAL_E_ARG,
-             "adam_step: buffers must be 16-byte aligned");
+extern "C" size_t diffsal_adam_args_size(void) { return sizeof(AdamArgs); }
+
+extern "C" int diffsal_adam_args(double lr, double beta1, double beta2, double eps, double weight_decay, int step, float gscale,
+                                 float max_norm, void* out /*host*/) {
+  DS_REQUIRE(out, DIFFSAL_E_ARG, "adam_args: null argument");
+  DS_REQUIRE(step >= 1, DIFFSAL_E_SHAPE, "adam_args: need step >= 1");
   // bias corrections in double on the host, as torch.optim.Adam does for a python-scalar step
   const double bc1 = 1.0 - pow(beta1, step);
   const double bc2 = 1.0 - pow(beta2, step);
@@ -212,12 +237,34 @@ extern "C" int diffsal_adam_step(float* p, float* g, float* m, float* v, long n,
   a.step_size = static_cast<float>(lr / bc1);
   a.bc2_sqrt = static_cast<float>(sqrt(bc2));
   a.max_norm = max_norm;
-  long need = (n / 4 + 255) / 256;
-  if (need < 1) need = 1;
-  const int grid = static_cast<int>(need < 256L * 16 ? need : 256L * 16);
-  hipLaunchKernelGGL(adam_kernel, dim3(grid), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, norm, n / 4, n, a,
-                     store_clipped_grad);
+  memcpy(out, &a, sizeof(a));
+  return DIFFSAL_OK;
+}
+
+extern "C" int diffsal_adam_step(float* p, float* g, float* m, float* v, long n, double lr, double beta1, double beta2,
+                                 double eps, double weight_decay, int step, float gscale, const float* norm, float max_norm,
+                                 int store_clipped_grad, diffsal_stream_t stream) {
+  DS_REQUIRE(p && g && m && v, DIFFSAL_E_ARG, "adam_step: null argument");
+  DS_REQUIRE(n > 0 && step >= 1, DIFFSAL_E_SHAPE, "adam_step: need n > 0 and step >= 1");
+  DS_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v), DIFFSAL_E_ARG,
+             "adam_step: buffers must be 16-byte aligned");
+  AdamArgs a;
+  const int rc = diffsal_adam_args(lr, beta1, beta2, eps, weight_decay, step, gscale, max_norm, &a);
+  if (rc != DIFFSAL_OK) return rc;
+  hipLaunchKernelGGL(adam_kernel, dim3(adam_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, norm, n / 4,
+                     n, a, store_clipped_grad);
   return check_launch("adam_step");
+}
+
+extern "C" int diffsal_adam_step_args(float* p, float* g, float* m, float* v, long n, const void* args_dev, const float* norm,
+                                      int store_clipped_grad, diffsal_stream_t stream) {
+  DS_REQUIRE(p && g && m && v && args_dev, DIFFSAL_E_ARG, "adam_step_args: null argument");
+  DS_REQUIRE(n > 0, DIFFSAL_E_SHAPE, "adam_step_args: need n > 0");
+  DS_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(args_dev), DIFFSAL_E_ARG,
+             "adam_step_args: buffers and the argument block must be 16-byte aligned");
+  hipLaunchKernelGGL(adam_args_kernel, dim3(adam_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, norm,
+                     n / 4, n, static_cast<const AdamArgs*>(args_dev), store_clipped_grad);
+  return check_launch("adam_step_args");
 }
 
 extern "C" int diffsal_multi_copy_max(void) { return kMultiCopyMax; }

@@ -526,12 +526,17 @@ _PACKS = _PackBatch()
 
 
 @contextlib.contextmanager
-def batched_packs():
-    """One launch for the weight repacks of the parameters seen in earlier uses of this context (see ``_PackBatch``)."""
-    pb = _PACKS
-    if pb.active:
+def batched_packs(batch: Optional[_PackBatch] = None):
+    """One launch for the weight repacks of the parameters seen in earlier uses of this context (see ``_PackBatch``).
+    ``batch``: a table of the caller's own in place of the process-wide one, for the duration of the context.  A captured
+    training step replays the table's launch with the table's device address, so its table must not be rebuilt -- and its old
+    storage released -- because some other model's step registered parameters (``DiffusionTrainStep(hip_graph=True)``)."""
+    global _PACKS
+    if _PACKS.active:
         yield
         return
+    prev = _PACKS
+    pb = _PACKS = prev if batch is None else batch
     pb.active = True
     try:
         pb.refresh()
@@ -539,6 +544,7 @@ def batched_packs():
     finally:
         pb.active = False
         pb.fresh = set()
+        _PACKS = prev
 
 
 def pack_conv_weight(w: Tensor) -> Tensor:
@@ -1572,6 +1578,44 @@ def adam_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, *, step: int, lr: floa
                                      float(max_norm), int(store_clipped_grad), _stream()), "adam_step")
 
 
+def adam_args_size() -> int:
+    """Bytes of the block ``adam_args`` fills and ``adam_step_args`` reads."""
+    return int(_lib.load().diffsal_adam_args_size())
+
+
+def adam_args(*, step: int, lr: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, gscale: float = 1.0,
+              max_norm: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
+    """The numbers ``adam_step`` hands its kernel for these hyper-parameters and this step, formed by the library's one routine,
+    as a pinned uint8 host tensor of ``adam_args_size()`` bytes (``out``: such a tensor to fill again).  A non-blocking copy of
+    it to the device is what ``adam_step_args`` reads."""
+    lib = _lib.load()
+    size = adam_args_size()
+    if out is None:
+        out = torch.empty((size,), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    elif out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != size:
+        raise ValueError(f"adam_args: out must be a contiguous uint8 host tensor of {size} bytes")
+    _lib.check(lib.diffsal_adam_args(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
+                                     float(gscale), float(max_norm), out.data_ptr()), "adam_args")
+    return out
+
+
+@_classed("optim")
+def adam_step_args(p: Tensor, g: Tensor, m: Tensor, v: Tensor, args_dev: Tensor, norm: Optional[Tensor] = None,
+                   store_clipped_grad: bool = False) -> None:
+    """``adam_step`` with its numbers read from ``args_dev``, a uint8 GPU tensor holding a copy of an ``adam_args`` block made
+    in stream order before this call: no hyper-parameter and no step number is a launch argument, so the launch can be
+    replayed from a captured graph for any step.  Bit-identical to ``adam_step`` for the same numbers."""
+    lib = _lib.load()
+    n = p.numel()
+    if not (g.numel() == n and m.numel() == n and v.numel() == n):
+        raise RuntimeError("adam_step_args: p, g, m, v must have the same number of elements")
+    if not (isinstance(args_dev, Tensor) and args_dev.is_cuda and args_dev.dtype == torch.uint8 and args_dev.is_contiguous()
+            and args_dev.numel() >= adam_args_size()):
+        raise ValueError(f"adam_step_args: args_dev must be a contiguous uint8 GPU tensor of at least {adam_args_size()} bytes")
+    _lib.check(lib.diffsal_adam_step_args(_p(p), _p(g), _p(m), _p(v), n, args_dev.data_ptr(), _p(norm) if norm is not None else None,
+                                          int(store_clipped_grad), _stream()), "adam_step_args")
+
+
 @_classed("optim")
 def scale_by(x: Tensor, s: Tensor) -> Tensor:
     """x * s[0] with s a one-element device tensor."""
@@ -2493,9 +2537,10 @@ def train_key(seed: int, step: int, device) -> Tensor:
     return torch.tensor([_u64_pattern(seed), int(step)], dtype=torch.int64).to(device)
 
 
-def sample_ids(ids, device, count: Optional[int] = None) -> Tensor:
+def sample_ids(ids, device, count: Optional[int] = None, pinned: bool = False) -> Tensor:
     """Sample ids as the int64 device tensor the training kernels read: a host sequence is checked to be non-negative and
-    uploaded, an int64 GPU tensor is taken as it is."""
+    uploaded, an int64 GPU tensor is taken as it is.  ``pinned``: the upload goes through page-locked memory and does not wait
+    for the stream's earlier work (a copy from pageable memory does), so a host that only replays a graph keeps running ahead."""
     host = _host_ids(ids, "sample")
     n = ids.numel() if host is None else len(host)
     if count is not None and n != count:
@@ -2503,7 +2548,10 @@ def sample_ids(ids, device, count: Optional[int] = None) -> Tensor:
     device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("diff_sal_amd device noise runs on the GPU only (no CPU fallback); got device " + str(device))
-    return ids.contiguous() if host is None else torch.tensor(host, dtype=torch.int64).to(device)
+    if host is None:
+        return ids.contiguous()
+    t = torch.tensor(host, dtype=torch.int64)
+    return t.pin_memory().to(device, non_blocking=True) if pinned else t.to(device)
 
 
 def _check_key(what: str, ids: Tensor, key: Tensor, B: int) -> None:

@@ -671,7 +671,12 @@ def fit_directory(model, trainer, data_type: str, root: str, out_root: str, epoc
     ``stop_epoch`` ends the run after that many epochs of the ``epochs`` the schedule is laid out for; ``resume`` names a
     ``ckpt_<k>.pth`` and restores both dictionaries, the epoch and the step, so that stopping and resuming gives the uninterrupted
     run's parameters and moments.  ``group``: ``epoch_order`` shards the listing over its ranks and rank 0 writes; the
-    validation shards its videos as ``predict_directory`` does.  Returns a ``FitReport``."""
+    validation shards its videos as ``predict_directory`` does.  Returns a ``FitReport``.
+
+    A trainer built with ``hip_graph=True`` works as it is: the loop calls ``trainer.step`` and reads ``trainer.last_losses`` and
+    nothing else.  Its loss tensors are static, overwritten by the next step in stream order; the meters add them to their device
+    sums right after each step, on the same stream, so they read every step's own values.  The front end's uploads run on the
+    loop's thread between steps, never during a capture, and the prefetch thread only reads and decodes files on the host."""
     clips = list_train_clips(data_type, root, len_snippet=len_snippet, alternate=alternate, videos=videos)
     validate = None
     if sampler is not None:
@@ -701,7 +706,9 @@ def fit_av(model, trainer, sets: Sequence, out_root: str, epochs: int, batch: in
       drawn; this is the deliberate difference named in the module's docstring;
     * the condition holds ``audio`` when the model has an ``audio_net`` (``load_batches``);
     * with a ``sampler``, every set of ``val_sets`` (same four paths; default: none) is validated with ``predict.predict_av(...,
-      losses=True)`` without files, and the ``val.log`` row holds the means over all their chunks."""
+      losses=True)`` without files, and the ``val.log`` row holds the means over all their chunks.
+
+    A trainer built with ``hip_graph=True`` works as it is (see ``fit_directory``)."""
     clips: list = []
     for s in sets:
         clips += list_av_train_clips(*s, sample_duration=sample_duration, step_duration=step_duration)

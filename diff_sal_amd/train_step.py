@@ -179,6 +179,7 @@ class GradReducer:
         self.relearned: List[int] = []         # parameters that left the predicted set in the last step
         self.launch_order: List[int] = []
         self.collectives: List[str] = []       # what was issued per bucket in the last step ("allreduce" / "reduce_scatter+all_gather")
+        self.deferred = False                  # hooks and finish() only gather; finish_deferred() exchanges (captured steps)
         for i, p in enumerate(flat.params):
             p.register_post_accumulate_grad_hook(self._make_hook(i))
 
@@ -211,8 +212,11 @@ class GradReducer:
         if self._unused:       # a surprise gradient stays out of the bucket on every rank (finish() exchanges it on its own)
             members = [i for i in members if i not in self._unused]
         self.flat.gather(members)
-        if not self.exchange:
-            return
+        if self.exchange and not self.deferred:
+            self._exchange(b)
+
+    def _exchange(self, b: int) -> None:
+        r = self.flat.buckets[b]
         buf = self.flat.flat_g[r.start:r.stop]
         n = buf.numel()
         if self.mode == "reduce_scatter" and n % self.world == 0:
@@ -289,6 +293,16 @@ class GradReducer:
         for b in range(len(self.flat.buckets)):     # the rest, in bucket order
             self._ready[b] = True
         self._drain()
+        if self.deferred:
+            # nothing has been exchanged yet, so a gradient that arrived for a parameter predicted to stay without one simply
+            # joins its bucket now; the prediction itself stays as it is (a replay is this very graph: nothing to verify)
+            for i in sorted(self._unused or ()):
+                p, slot = self.flat.params[i], self.flat.grad_view(i)
+                if self._fired[i] and p.grad is not None and p.grad.data_ptr() != slot.data_ptr():
+                    slot.copy_(p.grad)
+                    p.grad = slot
+            self._armed = False
+            return
         for w in self._work:
             w.wait()
         self._work, self._armed = [], False
@@ -296,6 +310,27 @@ class GradReducer:
             self._verify_unused()
         if self.static_unused and self._unused is None:
             self._learn_unused()
+
+
+    def finish_deferred(self) -> None:
+        """The exchange of a step whose gathers ran with ``deferred`` set (a replayed graph): every bucket's collective, in
+        bucket order 0, 1, 2, ... as always, same form and same buffers as ``_launch`` issues them, then the wait."""
+        self._work, self.launch_order, self.collectives = [], [], []
+        if self.exchange:
+            for b in range(len(self.flat.buckets)):
+                self.launch_order.append(b)
+                self._exchange(b)
+        for w in self._work:
+            w.wait()
+        self._work = []
+
+
+class _StepGraph:
+    """One captured training step: the graph, its static inputs and outputs, and what its launches read besides them."""
+    __slots__ = ("warm", "graph", "sal", "cond", "ids", "loss", "losses", "norm", "keep")
+
+    def __init__(self):
+        self.warm, self.graph = 0, None
 
 
 class FlatAdam(torch.optim.Optimizer):
@@ -358,7 +393,38 @@ class DiffusionTrainStep:
     rewritten by ``load_state_dict``; no value travels from the host inside a step.
     ``t_mode``: "batch" (default) keeps the reference's ONE timestep per rank batch (R/diffusion_trainer.py:111); with device
     noise it is the draw of the FIRST sample id of the call, so it depends on the batch layout by nature.  "per_sample" -- the
-    ordinary DDPM recipe, device noise only -- gives every sample the timestep of its own id."""
+    ordinary DDPM recipe, device noise only -- gives every sample the timestep of its own id.
+
+    ``hip_graph`` (default False: nothing below applies): replay the step from a captured HIP graph.  Needs
+    ``noise_source="device"`` (torch's generator and numpy's ``t0`` are host state, a ``ValueError`` otherwise).  The first
+    ``graph_warmup`` calls of ``step()`` (default 2: library load, discovery of the weight packs, workspace caches, the reducer's
+    unused set) run eagerly; the next one captures fused prepare, forward, loss, backward with the bucket gathers, the step word's
+    advance, the gradient norm and clip + Adam on ONE stream (``torch.cuda.graph``, no side stream inside) and from then on a
+    ``step()`` is: copy ``sal_maps``, every tensor of ``cond`` and the sample ids into static buffers, form the optimizer's
+    numbers for ``step_count + 1`` from the parameter group's CURRENT ``lr`` / ``betas`` / ``eps`` / ``weight_decay``
+    (``ops.adam_args``) and enqueue their copy to the device block the captured Adam reads (``ops.adam_step_args``) -- a
+    learning-rate scheduler acts on the next step without a new capture --, replay, then the host's bookkeeping (``step_count``,
+    the step word's range, ``parameters_updated()`` so that a later ``eval()`` forward repacks, the optimizer face's step hooks
+    and scheduler counters).  Results are bit-identical to the eager step's.
+    * One capture per signature: shapes and dtypes of the inputs, the keys of ``cond``, which parameters require a gradient,
+      ``grad_clip``, ``store_clipped_grad``, ``t_mode``, ``training_target``, ``gaussian_dequantization``, ``mse_weight``, the
+      identity of ``loss_fn`` and the world size.  A new signature runs one eager step of its own, then captures; a signature
+      that returns replays its old capture.  ``graph_captures`` / ``graph_replays`` count.  Every capture keeps its own
+      activations: memory grows by about one step's peak per signature.
+    * ``step(..., t0=)`` / ``noise=`` / ``dequant_noise=``, a call while ``ops.PROFILE`` is set, a call inside somebody else's
+      capture and a call after ``reducer.reset_unused()`` (until the set is learnt again) run eagerly, for that call.
+    * ``step()`` returns the STATIC loss tensor, and ``last_losses`` / ``last_norm`` are static too: the next step of the same
+      signature overwrites them in stream order.  Work enqueued on the stream before that step reads this step's values
+      (``train``'s meters add them to their device sums right after each step, so they do); ``clone()`` what must outlive it.
+    * ``load_state_dict`` (and ``model.load_state_dict``) write ``train_key``, the flat buffers and the model's buffers in place,
+      so a live capture goes on from the loaded state.  A failed capture raises with its cause chained: no fallback.
+    * With an exchange (more than one rank, or ``exchange_single_rank``) the reducer runs deferred: the captured hooks only
+      gather; after each replay ``reducer.finish_deferred()`` issues the bucket collectives in bucket order and waits, and the
+      step word's advance, norm and Adam run eagerly after it.  The buffer broadcast runs eagerly before the replay.  This gives
+      up the overlap of the exchange with backward.  Every rank must pass the same ``hip_graph`` (checked at construction).
+    Measured on the full audio-visual step (224 x 384, batch 4, one MI355X): the replay is NOT faster, 66.0 ms
+    against 65.9 ms eager on the same box -- the step is bound by the device, whose eager host issue takes 56.5 ms.  It cuts the
+    host's time in a step to 2.2 ms, costs 0.7 s for the capturing call and 64 MB of peak memory (14 544 against 14 480 MB)."""
 
     def __init__(self, model: nn.Module, *, lr: float = 1e-4, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
                  weight_decay: float = 0.0, grad_clip: float = 1.0, mse_weight: float = 1.0,
@@ -367,7 +433,11 @@ class DiffusionTrainStep:
                  bucket_mb: float = 32.0, process_group=None, broadcast_buffers: bool = True,
                  store_clipped_grad: bool = False, exchange_single_rank: bool = False,
                  loss_fn: Optional[Callable] = None, loss_config=None, exchange: str = "allreduce",
-                 noise_source: str = "torch", seed: int = 0, t_mode: str = "batch", training_target: str = "x0"):
+                 noise_source: str = "torch", seed: int = 0, t_mode: str = "batch", training_target: str = "x0",
+                 hip_graph: bool = False, graph_warmup: int = 2):
+        if hip_graph and noise_source != "device":
+            raise ValueError("DiffusionTrainStep: hip_graph=True needs noise_source='device': torch's generator and numpy's t0 "
+                             "are host state, which a replayed graph would not advance")
         if noise_source not in ("torch", "device"):
             raise ValueError(f"DiffusionTrainStep: noise_source={noise_source!r} (torch or device)")
         if t_mode not in ("batch", "per_sample"):
@@ -419,6 +489,23 @@ class DiffusionTrainStep:
             self.train_key = ops.train_key(seed, 0, dev)
             self._tab_a = self.sqrt_alphas_hat.to(torch.float32).contiguous().to(dev)
             self._tab_b = self.sqrt_one_minus_alphas_hat.to(torch.float32).contiguous().to(dev)
+        self.hip_graph, self.graph_warmup = bool(hip_graph), max(1, int(graph_warmup))
+        self.graph_captures = self.graph_replays = 0
+        self._graphs: Dict[tuple, _StepGraph] = {}
+        self._packs = None               # this trainer's own weight-pack table: a capture replays its launch
+        self._adam_dev: Optional[Tensor] = None
+        self._in_graph = False           # the device half of optimizer_step already ran inside the replayed graph
+        if self.hip_graph:
+            from . import ops
+
+            self._packs = ops._PackBatch()
+        if self.world > 1:               # every rank replays or none does: a mixed group would pair different collectives
+            mine = 1.0 if self.hip_graph else 0.0
+            seen = torch.tensor([mine, -mine], dtype=torch.float32, device=dev)
+            dist.all_reduce(seen, op=dist.ReduceOp.MAX, group=process_group)
+            hi, lo = seen.tolist()
+            if hi != -lo:
+                raise ValueError("DiffusionTrainStep: hip_graph differs between the ranks of the group; pass the same value on all")
 
     # hyper-parameters live in the optimizer face's single parameter group (what a scheduler rewrites)
     def _hp(self, key):
@@ -436,13 +523,13 @@ class DiffusionTrainStep:
         return self.optimizer.param_groups
 
     # ---- R/diffusion_trainer.py:78-120 (training branch) ----
-    def _sample_ids(self, sample_ids, sal_maps: Tensor) -> Tensor:
+    def _sample_ids(self, sample_ids, sal_maps: Tensor, pinned: bool = False) -> Tensor:
         """Argument rules of the device-noise path, then the ids as an int64 tensor next to ``sal_maps``."""
         from . import ops
 
         if sample_ids is None:
             raise ValueError("DiffusionTrainStep: noise_source='device' needs sample_ids (one non-negative id per sample)")
-        ids = ops.sample_ids(sample_ids, sal_maps.device, sal_maps.shape[0])       # raises for a CPU tensor, after the id checks
+        ids = ops.sample_ids(sample_ids, sal_maps.device, sal_maps.shape[0], pinned)       # raises for a CPU tensor, after the id checks
         if self.train_key is None:
             raise RuntimeError("diff_sal_amd device noise runs on the GPU only (no CPU fallback); the model is on the CPU")
         return ids
@@ -525,7 +612,7 @@ class DiffusionTrainStep:
         for b in others:           # none in the reference's model; kept exact for foreign modules
             dist.broadcast(b, src=src, group=self.group)
 
-    def loss_and_backward(self, x0: Tensor, x_t: Tensor, t: Tensor, cond: Dict, sample_ids=None) -> Tensor:
+    def loss_and_backward(self, x0: Tensor, x_t: Tensor, t: Tensor, cond: Dict, sample_ids=None, _captured: bool = False) -> Tensor:
         """Forward + loss + backward + gradient exchange; leaves the rank-SUMMED gradient in ``flat.flat_g``.  ``x0`` is the
         regression target (the forward-process noise when ``training_target="noise"``).  With device noise ``sample_ids`` key
         the dropout masks (required then); the masks of forward and backward both read the device step word, which
@@ -539,13 +626,13 @@ class DiffusionTrainStep:
             raise ValueError("DiffusionTrainStep: sample_ids mean nothing to torch's generator; use noise_source='device'")
 
         self.model.train()
-        if self.broadcast_buffers:
+        if self.broadcast_buffers and not _captured:       # a captured step broadcasts eagerly, before its replay
             self._sync_buffers()
         self.flat.zero_grad()
         self.reducer.arm()
         from . import ops
 
-        with ops.batched_packs():        # every parameter's kernel layouts (forward, data-gradient) rebuilt by one launch
+        with ops.batched_packs(self._packs):        # every parameter's kernel layouts (forward, data-gradient) rebuilt by one launch
             pred = self._forward(x_t, t, cond, dropout_key)
             if self.loss_fn is None:
                 loss = ag.mse_loss(pred, x0, self.mse_weight / x0.shape[0])
@@ -564,19 +651,7 @@ class DiffusionTrainStep:
         self.reducer.finish()
         return loss.detach()
 
-    def optimizer_step(self) -> None:
-        from . import ops
-
-        if self.train_key is not None:
-            ops.train_draw(self.step_count + 1, 0)     # the host mirror of the draw word's 27-bit step field
-            ops.train_key_advance(self.train_key)      # same stream as backward, so after the last reader of the old step
-        self.step_count += 1
-        gscale = 1.0 / self.world
-        norm = ops.grad_norm(self.flat.flat_g, gscale) if self.grad_clip > 0 else None
-        self.last_norm = norm
-        ops.adam_step(self.flat.flat_p, self.flat.flat_g, self.flat.exp_avg, self.flat.exp_avg_sq, step=self.step_count,
-                      lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, gscale=gscale, norm=norm,
-                      max_norm=self.grad_clip, store_clipped_grad=self.store_clipped_grad)
+    def _parameters_updated(self) -> None:
         bump = getattr(self.model, "parameters_updated", None)
         if bump is not None:
             bump()
@@ -584,16 +659,172 @@ class DiffusionTrainStep:
             if m is not self.model and hasattr(m, "parameters_updated"):
                 m.parameters_updated()
 
+    def _device_tail(self, args_dev: Optional[Tensor] = None) -> None:
+        """Step word, gradient norm, clip + Adam: the launches after the exchange.  ``args_dev``: Adam's numbers come from that
+        device block (a captured step) instead of the launch arguments."""
+        from . import ops
+
+        if self.train_key is not None:
+            ops.train_key_advance(self.train_key)      # same stream as backward, so after the last reader of the old step
+        gscale = 1.0 / self.world
+        norm = ops.grad_norm(self.flat.flat_g, gscale) if self.grad_clip > 0 else None
+        self.last_norm = norm
+        f = self.flat
+        if args_dev is not None:
+            ops.adam_step_args(f.flat_p, f.flat_g, f.exp_avg, f.exp_avg_sq, args_dev, norm, self.store_clipped_grad)
+        else:
+            ops.adam_step(f.flat_p, f.flat_g, f.exp_avg, f.exp_avg_sq, step=self.step_count + 1,
+                          lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, gscale=gscale, norm=norm,
+                          max_norm=self.grad_clip, store_clipped_grad=self.store_clipped_grad)
+
+    def optimizer_step(self) -> None:
+        from . import ops
+
+        if self.train_key is not None:
+            ops.train_draw(self.step_count + 1, 0)     # the host mirror of the draw word's 27-bit step field
+        if not self._in_graph:
+            self._device_tail()
+        self.step_count += 1
+        self._parameters_updated()
+
     def step(self, sal_maps: Tensor, cond: Dict, *, t0: Optional[int] = None, noise: Optional[Tensor] = None,
              dequant_noise: Optional[Tensor] = None, sample_ids=None) -> Tensor:
         """One training step on this rank's clips; returns the (detached, device-resident) loss.  ``sample_ids``: one id per
-        sample, required with (and only with) ``noise_source="device"``."""
+        sample, required with (and only with) ``noise_source="device"``.  With ``hip_graph=True`` the returned tensor is static:
+        the next step overwrites it in stream order (see the class)."""
+        if self.hip_graph and t0 is None and noise is None and dequant_noise is None and self._graphable(sal_maps):
+            return self._graph_step(sal_maps, cond, sample_ids)
+        return self._eager_step(sal_maps, cond, t0=t0, noise=noise, dequant_noise=dequant_noise, sample_ids=sample_ids)
+
+    def _eager_step(self, sal_maps: Tensor, cond: Dict, *, t0=None, noise=None, dequant_noise=None, sample_ids=None) -> Tensor:
         if self.noise_source == "device" and noise is None and dequant_noise is None:
             sample_ids = self._sample_ids(sample_ids, sal_maps)        # checked and uploaded once for prepare and dropout
         x0, x_t, t, nz = self.prepare_data(sal_maps, t0=t0, noise=noise, dequant_noise=dequant_noise, sample_ids=sample_ids)
         loss = self.loss_and_backward(nz if self.training_target == "noise" else x0, x_t, t, cond, sample_ids=sample_ids)
         self.optimizer.step()          # the torch.optim.Optimizer face: step hooks and lr_scheduler bookkeeping see the step
         return loss
+
+    # ---- hip_graph=True: one captured step per signature ----
+    def _graphable(self, sal_maps: Tensor) -> bool:
+        from . import ops
+
+        if not torch.is_tensor(sal_maps) or not sal_maps.is_cuda or self.train_key is None:
+            return False                    # the eager path raises what it always raised
+        if ops.PROFILE is not None or torch.cuda.is_current_stream_capturing():
+            return False                    # per-launch events cannot be recorded inside a capture; no capture inside a capture
+        # the unused set is learnt by a host read at the end of a step: not inside a capture
+        return not (self.reducer.static_unused and self.reducer._unused is None and self.step_count > 0 and self._graphs)
+
+    @staticmethod
+    def _cond_tensors(cond: Dict):
+        """(structure for the signature, the tensors in a fixed order)"""
+        desc, flat = [], []
+        for k in sorted(cond):
+            v = cond[k]
+            if torch.is_tensor(v):
+                desc.append((k, "t", tuple(v.shape), v.dtype))
+                flat.append(v)
+            elif isinstance(v, (list, tuple)) and all(torch.is_tensor(x) for x in v):
+                desc.append((k, "l", tuple((tuple(x.shape), x.dtype) for x in v)))
+                flat += list(v)
+            elif v is None:
+                desc.append((k, "n"))
+            else:
+                raise ValueError(f"DiffusionTrainStep(hip_graph=True): cond[{k!r}] must be a tensor, a list of tensors or None")
+        return tuple(desc), flat
+
+    @staticmethod
+    def _cond_like(cond: Dict, flat: List[Tensor]) -> Dict:
+        out, it = {}, iter(flat)
+        for k in sorted(cond):
+            v = cond[k]
+            out[k] = next(it) if torch.is_tensor(v) else (None if v is None else [next(it) for _ in v])
+        return out
+
+    def _signature(self, sal_maps: Tensor, desc) -> tuple:
+        return (tuple(sal_maps.shape), sal_maps.dtype, desc, tuple(p.requires_grad for p in self.model.parameters()),
+                self.grad_clip, self.store_clipped_grad, self.t_mode, self.training_target, self.gaussian_dequantization,
+                self.mse_weight, id(self.loss_fn), self.world)
+
+    def _captured_step(self, ent: _StepGraph):
+        x0, x_t, t, nz = self.prepare_data(ent.sal, sample_ids=ent.ids)
+        loss = self.loss_and_backward(nz if self.training_target == "noise" else x0, x_t, t, ent.cond, sample_ids=ent.ids,
+                                      _captured=True)
+        if not self.reducer.exchange:
+            self._device_tail(self._adam_dev)
+        return loss
+
+    def _capture(self, ent: _StepGraph, sal_maps: Tensor, cond: Dict, flat: List[Tensor], ids: Tensor) -> None:
+        from . import ops
+
+        dev = sal_maps.device
+        ent.sal, ent.ids = torch.empty_like(sal_maps).copy_(sal_maps), ids.clone()
+        ent.cond = self._cond_like(cond, [torch.empty_like(v).copy_(v) for v in flat])
+        if self._adam_dev is None:
+            self._adam_dev = torch.zeros((_aligned(ops.adam_args_size()),), dtype=torch.uint8, device=dev)
+        self._parameters_updated()          # whatever an eval() forward cached since the last step is packed again inside
+        with ops.batched_packs(self._packs):
+            pass                            # the pack table is built (a host upload) and the dead entries leave it now
+        torch.cuda.synchronize(dev)
+        graph = torch.cuda.CUDAGraph()
+        self.reducer.deferred = self.reducer.exchange
+        try:
+            with torch.cuda.graph(graph):
+                ent.loss = self._captured_step(ent)
+        except Exception as e:              # the user asked for a graph: no silent eager step
+            raise RuntimeError(f"DiffusionTrainStep(hip_graph=True): capturing the training step failed "
+                               f"({type(e).__name__}: {e})") from e
+        finally:
+            self.reducer.deferred = False
+        ent.losses, ent.norm = self.last_losses, self.last_norm
+        # the table and the packed weights the captured launches address stay alive with the capture
+        ent.keep = (self._packs.table, [e[1] for e in self._packs.entries.values()])
+        ent.graph = graph
+        self.graph_captures += 1
+
+    def _graph_step(self, sal_maps: Tensor, cond: Dict, sample_ids) -> Tensor:
+        from . import ops
+
+        ids = self._sample_ids(sample_ids, sal_maps, pinned=True)      # a pageable upload would stall the host behind the replay
+        desc, flat = self._cond_tensors(cond)
+        sig = self._signature(sal_maps, desc)
+        ent = self._graphs.get(sig)
+        if ent is None:
+            ent = self._graphs[sig] = _StepGraph()
+        need = self.graph_warmup if len(self._graphs) == 1 else 1
+        if ent.graph is None and ent.warm < need:
+            ent.warm += 1
+            return self._eager_step(sal_maps, cond, sample_ids=ids)
+        ops.train_draw(self.step_count + 1, 0)             # the step word's range, before anything is enqueued
+        if ent.graph is None:
+            self._capture(ent, sal_maps, cond, flat, ids)
+        else:
+            ent.sal.copy_(sal_maps)
+            ent.ids.copy_(ids)
+            for d, s in zip(self._cond_tensors(ent.cond)[1], flat):
+                d.copy_(s)
+        self.model.train()
+        if self.reducer.exchange:
+            if self.broadcast_buffers:
+                self._sync_buffers()
+        else:
+            # a fresh pinned block every step: the host allocator hands it out again only after this copy has run
+            block = ops.adam_args(step=self.step_count + 1, lr=self.lr, betas=self.betas, eps=self.eps,
+                                  weight_decay=self.weight_decay, gscale=1.0 / self.world, max_norm=self.grad_clip)
+            self._adam_dev[:block.numel()].copy_(block, non_blocking=True)
+        ent.graph.replay()
+        self.graph_replays += 1
+        self.last_losses, self.last_norm = ent.losses, ent.norm
+        if self.reducer.exchange:
+            self.reducer.finish_deferred()
+            self.optimizer.step()           # step word, norm and Adam eagerly, after the exchange
+        else:
+            self._in_graph = True
+            try:
+                self.optimizer.step()       # hooks, scheduler counters and this object's bookkeeping; Adam ran in the graph
+            finally:
+                self._in_graph = False
+        return ent.loss
 
     # ---- checkpoint surface of torch.optim.Adam (R/diffusion_trainer.py:187-193, 263-268: "optim_dict") ----
     def _indexed_params(self):

@@ -1316,6 +1316,14 @@ int diffsal_train_key_advance(unsigned long long* key, diffsal_stream_t stream);
  *   p, m (exp_avg), v (exp_avg_sq), with the gradient first multiplied by
  *   gscale * min(1, max_norm / (norm[0] + 1e-6)) (norm may be NULL or max_norm <= 0: no clipping).  `step` counts
  *   from 1.  store_clipped_grad != 0 writes the scaled gradient back into g as clip_grad_norm_ does.
+ * adam_args (host code, no launch): fills the block of adam_args_size() bytes at `out` (HOST memory) with the numbers
+ *   adam_step hands its kernel -- 1 - beta in fp32 rounded from double, the bias corrections 1 - pow(beta, step) formed
+ *   in double as torch.optim.Adam forms them for a python-scalar step (R/util/utils.py:116-123), lr / bc1 and sqrt(bc2)
+ *   rounded to fp32, gscale and max_norm.  adam_step itself calls it: one place forms these numbers.
+ * adam_step_args: the update of adam_step with that block read from DEVICE memory (`args_dev`, 16-byte aligned; a copy
+ *   of an adam_args block made in stream order before the launch) -- nothing of the step number, the learning rate or
+ *   the clip bound is a launch argument, so a captured graph replays it for any step (R/diffusion_trainer.py:228-235
+ *   once per replay).  Same grid, vector width, tail and arithmetic as adam_step: bit-identical results.
  * scale_by: out = x * s[0] with s a device scalar (the incoming d(loss) of the MSE backward); any n > 0.
  * multi_copy: dst[dst_offsets[i] .. +sizes[i]) = srcs[i][0 .. sizes[i]) for i < count, a few launches for any count
  *   (gathers the per-parameter gradients autograd produced into the flat gradient buffer; the three tables are HOST
@@ -1331,6 +1339,11 @@ int diffsal_grad_norm(const float* g, long n, float gscale, float* norm, double*
 int diffsal_adam_step(float* p, float* g, float* m, float* v, long n, double lr, double beta1, double beta2,
                       double eps, double weight_decay, int step, float gscale, const float* norm, float max_norm,
                       int store_clipped_grad, diffsal_stream_t stream);
+size_t diffsal_adam_args_size(void);
+int diffsal_adam_args(double lr, double beta1, double beta2, double eps, double weight_decay, int step, float gscale,
+                      float max_norm, void* out /*host*/);
+int diffsal_adam_step_args(float* p, float* g, float* m, float* v, long n, const void* args_dev, const float* norm,
+                           int store_clipped_grad, diffsal_stream_t stream);
 
 #ifdef __cplusplus
 }
