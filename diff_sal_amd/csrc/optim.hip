@@ -125,21 +125,40 @@ __device__ __forceinline__ void adam_one(float& p, float g, float& m, float& v, 
   p = fmaf(-a.step_size, m / denom, p);              // param.addcdiv_(exp_avg, denom, value=-step_size)
 }
 
-// The update loop of both kernels below: the grid-stride float4 walk, then the tail of 1 to 3 elements in block 0.
+// The shadow's numbers: s = mu s + (1 - mu) p, with 1 - mu formed in double and both rounded to fp32 on the host.
+struct EmaArgs {
+  float omm, mu;
+};
+struct AdamEmaArgs {     // the device block of the EMA form: Adam's nine numbers, then the shadow's two
+  AdamArgs adam;
+  EmaArgs ema;
+};
+
+// lincomb3's rounding sequence (misc.hip) for axpbypcz(p, 1 - mu, s, mu): the product is rounded, then one fma.
+__device__ __forceinline__ float ema_one(float s, float p, const EmaArgs& e) { return fmaf(e.mu, s, e.omm * p); }
+
+// The update loop of the kernels below: the grid-stride float4 walk, then the tail of 1 to 3 elements in block 0.
+// kEma: the walk also carries the shadow buffer `s`, updated from the new p in the same pass; without it `s` and `e` are
+// not touched and the code is the plain Adam walk.
+template <bool kEma>
 __device__ __forceinline__ void adam_walk(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
-                                          float* __restrict__ v, const float* __restrict__ norm, long n4, long n,
-                                          const AdamArgs& a, int store_grad) {
+                                          float* __restrict__ v, float* __restrict__ s, const float* __restrict__ norm, long n4,
+                                          long n, const AdamArgs& a, const EmaArgs& e, int store_grad) {
   // clip_grad_norm_: coef = min(1, max_norm / (total_norm + 1e-6)); the DDP average is folded in as gscale
   float coef = a.gscale;
   if (norm != nullptr && a.max_norm > 0.f) coef *= fminf(1.f, a.max_norm / (norm[0] + 1e-6f));
   for (long i = static_cast<long>(blockIdx.x) * 256 + threadIdx.x; i < n4; i += static_cast<long>(gridDim.x) * 256) {
     float4 pv = ld4(p + i * 4), mv = ld4(m + i * 4), vv = ld4(v + i * 4);
     const float4 gv = ld4(g + i * 4);
+    float4 sv;
+    if constexpr (kEma) sv = ld4(s + i * 4);
     adam_one(pv.x, gv.x, mv.x, vv.x, a, coef);
     adam_one(pv.y, gv.y, mv.y, vv.y, a, coef);
     adam_one(pv.z, gv.z, mv.z, vv.z, a, coef);
     adam_one(pv.w, gv.w, mv.w, vv.w, a, coef);
     st4(p + i * 4, pv); st4(m + i * 4, mv); st4(v + i * 4, vv);
+    if constexpr (kEma)
+      st4(s + i * 4, make_float4(ema_one(sv.x, pv.x, e), ema_one(sv.y, pv.y, e), ema_one(sv.z, pv.z, e), ema_one(sv.w, pv.w, e)));
     if (store_grad) st4(g + i * 4, make_float4(gv.x * coef, gv.y * coef, gv.z * coef, gv.w * coef));
   }
   if (blockIdx.x == 0 && threadIdx.x < static_cast<int>(n - n4 * 4)) {
@@ -148,6 +167,7 @@ __device__ __forceinline__ void adam_walk(float* __restrict__ p, float* __restri
     const float gv = g[i];
     adam_one(pv, gv, mv, vv, a, coef);
     p[i] = pv; m[i] = mv; v[i] = vv;
+    if constexpr (kEma) s[i] = ema_one(s[i], pv, e);
     if (store_grad) g[i] = gv * coef;
   }
 }
@@ -155,7 +175,7 @@ __device__ __forceinline__ void adam_walk(float* __restrict__ p, float* __restri
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, const float* __restrict__ norm, long n4,
                                                    long n, AdamArgs a, int store_grad) {
-  adam_walk(p, g, m, v, norm, n4, n, a, store_grad);
+  adam_walk<false>(p, g, m, v, nullptr, norm, n4, n, a, EmaArgs{}, store_grad);
 }
 
 // Same update with the nine numbers read from device memory: one load of the block per wave, from an address every lane
@@ -165,7 +185,39 @@ __global__ __launch_bounds__(256) void adam_args_kernel(float* __restrict__ p, f
                                                         float* __restrict__ v, const float* __restrict__ norm, long n4,
                                                         long n, const AdamArgs* __restrict__ args, int store_grad) {
   const AdamArgs a = *args;
-  adam_walk(p, g, m, v, norm, n4, n, a, store_grad);
+  adam_walk<false>(p, g, m, v, nullptr, norm, n4, n, a, EmaArgs{}, store_grad);
+}
+
+// The EMA forms of the two kernels above: one more read and write of 4 bytes per element in the same pass.
+__global__ __launch_bounds__(256) void adam_ema_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                       float* __restrict__ v, float* __restrict__ s,
+                                                       const float* __restrict__ norm, long n4, long n, AdamEmaArgs a,
+                                                       int store_grad) {
+  adam_walk<true>(p, g, m, v, s, norm, n4, n, a.adam, a.ema, store_grad);
+}
+
+__global__ __launch_bounds__(256) void adam_ema_args_kernel(float* __restrict__ p, float* __restrict__ g, float* __restrict__ m,
+                                                            float* __restrict__ v, float* __restrict__ s,
+                                                            const float* __restrict__ norm, long n4, long n,
+                                                            const AdamEmaArgs* __restrict__ args, int store_grad) {
+  const AdamEmaArgs a = *args;
+  adam_walk<true>(p, g, m, v, s, norm, n4, n, a.adam, a.ema, store_grad);
+}
+
+// p <-> s in place, as bits (a NaN's payload and the sign of zero survive): same walk and tail, every element is read and
+// written by one thread only, so no third buffer.  Its own inverse.
+__global__ __launch_bounds__(256) void ema_swap_kernel(uint32_t* __restrict__ p, uint32_t* __restrict__ s, long n4, long n) {
+  for (long i = static_cast<long>(blockIdx.x) * 256 + threadIdx.x; i < n4; i += static_cast<long>(gridDim.x) * 256) {
+    uint4* pp = reinterpret_cast<uint4*>(p + i * 4);
+    uint4* sp = reinterpret_cast<uint4*>(s + i * 4);
+    const uint4 a = *pp, b = *sp;
+    *pp = b; *sp = a;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < static_cast<int>(n - n4 * 4)) {
+    const long i = n4 * 4 + threadIdx.x;
+    const uint32_t a = p[i], b = s[i];
+    p[i] = b; s[i] = a;
+  }
 }
 
 int adam_grid(long n) {
@@ -265,6 +317,57 @@ extern "C" int diffsal_adam_step_args(float* p, float* g, float* m, float* v, lo
   hipLaunchKernelGGL(adam_args_kernel, dim3(adam_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, norm,
                      n / 4, n, static_cast<const AdamArgs*>(args_dev), store_clipped_grad);
   return check_launch("adam_step_args");
+}
+
+extern "C" size_t diffsal_adam_ema_args_size(void) { return sizeof(AdamEmaArgs); }
+
+extern "C" int diffsal_adam_ema_args(double lr, double beta1, double beta2, double eps, double weight_decay, int step,
+                                     float gscale, float max_norm, double ema_mu, void* out /*host*/) {
+  DS_REQUIRE(out, DIFFSAL_E_ARG, "adam_ema_args: null argument");
+  DS_REQUIRE(ema_mu >= 0.0 && ema_mu <= 1.0, DIFFSAL_E_ARG, "adam_ema_args: ema_mu %g must be in [0, 1]", ema_mu);
+  AdamEmaArgs a;
+  const int rc = diffsal_adam_args(lr, beta1, beta2, eps, weight_decay, step, gscale, max_norm, &a.adam);
+  if (rc != DIFFSAL_OK) return rc;
+  a.ema.omm = static_cast<float>(1.0 - ema_mu);
+  a.ema.mu = static_cast<float>(ema_mu);
+  memcpy(out, &a, sizeof(a));
+  return DIFFSAL_OK;
+}
+
+extern "C" int diffsal_adam_ema_step(float* p, float* g, float* m, float* v, float* s, long n, double lr, double beta1,
+                                     double beta2, double eps, double weight_decay, int step, float gscale, const float* norm,
+                                     float max_norm, int store_clipped_grad, double ema_mu, diffsal_stream_t stream) {
+  DS_REQUIRE(p && g && m && v && s, DIFFSAL_E_ARG, "adam_ema_step: null argument");
+  DS_REQUIRE(n > 0 && step >= 1, DIFFSAL_E_SHAPE, "adam_ema_step: need n > 0 and step >= 1");
+  DS_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(s), DIFFSAL_E_ARG,
+             "adam_ema_step: buffers must be 16-byte aligned");
+  AdamEmaArgs a;
+  const int rc = diffsal_adam_ema_args(lr, beta1, beta2, eps, weight_decay, step, gscale, max_norm, ema_mu, &a);
+  if (rc != DIFFSAL_OK) return rc;
+  hipLaunchKernelGGL(adam_ema_kernel, dim3(adam_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, s, norm,
+                     n / 4, n, a, store_clipped_grad);
+  return check_launch("adam_ema_step");
+}
+
+extern "C" int diffsal_adam_ema_step_args(float* p, float* g, float* m, float* v, float* s, long n, const void* args_dev,
+                                          const float* norm, int store_clipped_grad, diffsal_stream_t stream) {
+  DS_REQUIRE(p && g && m && v && s && args_dev, DIFFSAL_E_ARG, "adam_ema_step_args: null argument");
+  DS_REQUIRE(n > 0, DIFFSAL_E_SHAPE, "adam_ema_step_args: need n > 0");
+  DS_REQUIRE(aligned16(p) && aligned16(g) && aligned16(m) && aligned16(v) && aligned16(s) && aligned16(args_dev), DIFFSAL_E_ARG,
+             "adam_ema_step_args: buffers and the argument block must be 16-byte aligned");
+  hipLaunchKernelGGL(adam_ema_args_kernel, dim3(adam_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream), p, g, m, v, s,
+                     norm, n / 4, n, static_cast<const AdamEmaArgs*>(args_dev), store_clipped_grad);
+  return check_launch("adam_ema_step_args");
+}
+
+extern "C" int diffsal_ema_swap(float* p, float* s, long n, diffsal_stream_t stream) {
+  DS_REQUIRE(p && s, DIFFSAL_E_ARG, "ema_swap: null argument");
+  DS_REQUIRE(n > 0, DIFFSAL_E_SHAPE, "ema_swap: need n > 0");
+  DS_REQUIRE(aligned16(p) && aligned16(s), DIFFSAL_E_ARG, "ema_swap: buffers must be 16-byte aligned");
+  DS_REQUIRE(p + n <= s || s + n <= p, DIFFSAL_E_ARG, "ema_swap: the two buffers overlap");
+  hipLaunchKernelGGL(ema_swap_kernel, dim3(adam_grid(n)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<uint32_t*>(p), reinterpret_cast<uint32_t*>(s), n / 4, n);
+  return check_launch("ema_swap");
 }
 
 extern "C" int diffsal_multi_copy_max(void) { return kMultiCopyMax; }

@@ -1617,6 +1617,67 @@ def adam_step_args(p: Tensor, g: Tensor, m: Tensor, v: Tensor, args_dev: Tensor,
 
 
 @_classed("optim")
+def adam_ema_step(p: Tensor, g: Tensor, m: Tensor, v: Tensor, s: Tensor, *, step: int, lr: float, ema_mu: float, betas=(0.9, 0.999),
+                  eps: float = 1e-8, weight_decay: float = 0.0, gscale: float = 1.0, norm: Optional[Tensor] = None,
+                  max_norm: float = 0.0, store_clipped_grad: bool = False) -> None:
+    """``adam_step`` that also updates the shadow ``s`` from the new ``p`` in the same pass: bit-equal to ``adam_step`` followed by
+    ``axpbypcz(p, 1 - ema_mu, s, ema_mu, out=s)``."""
+    lib = _lib.load()
+    n = p.numel()
+    if not (g.numel() == n and m.numel() == n and v.numel() == n and s.numel() == n):
+        raise RuntimeError("adam_ema_step: p, g, m, v, s must have the same number of elements")
+    _lib.check(lib.diffsal_adam_ema_step(_p(p), _p(g), _p(m), _p(v), _p(s), n, float(lr), float(betas[0]), float(betas[1]),
+                                         float(eps), float(weight_decay), int(step), float(gscale),
+                                         _p(norm) if norm is not None else None, float(max_norm), int(store_clipped_grad),
+                                         float(ema_mu), _stream()), "adam_ema_step")
+
+
+def adam_ema_args_size() -> int:
+    """Bytes of the block ``adam_ema_args`` fills and ``adam_ema_step_args`` reads: ``adam_args``' block, then 1 - mu and mu."""
+    return int(_lib.load().diffsal_adam_ema_args_size())
+
+
+def adam_ema_args(*, step: int, lr: float, ema_mu: float, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                  gscale: float = 1.0, max_norm: float = 0.0, out: Optional[Tensor] = None) -> Tensor:
+    """``adam_args`` for the EMA form: a pinned uint8 host tensor of ``adam_ema_args_size()`` bytes."""
+    lib = _lib.load()
+    size = adam_ema_args_size()
+    if out is None:
+        out = torch.empty((size,), dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    elif out.is_cuda or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != size:
+        raise ValueError(f"adam_ema_args: out must be a contiguous uint8 host tensor of {size} bytes")
+    _lib.check(lib.diffsal_adam_ema_args(float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
+                                         float(gscale), float(max_norm), float(ema_mu), out.data_ptr()), "adam_ema_args")
+    return out
+
+
+@_classed("optim")
+def adam_ema_step_args(p: Tensor, g: Tensor, m: Tensor, v: Tensor, s: Tensor, args_dev: Tensor, norm: Optional[Tensor] = None,
+                       store_clipped_grad: bool = False) -> None:
+    """``adam_ema_step`` with its numbers, the shadow's rate included, read from ``args_dev``, a uint8 GPU tensor holding a copy of
+    an ``adam_ema_args`` block made in stream order before this call.  Bit-identical to ``adam_ema_step`` for the same numbers."""
+    lib = _lib.load()
+    n = p.numel()
+    if not (g.numel() == n and m.numel() == n and v.numel() == n and s.numel() == n):
+        raise RuntimeError("adam_ema_step_args: p, g, m, v, s must have the same number of elements")
+    if not (isinstance(args_dev, Tensor) and args_dev.is_cuda and args_dev.dtype == torch.uint8 and args_dev.is_contiguous()
+            and args_dev.numel() >= adam_ema_args_size()):
+        raise ValueError(f"adam_ema_step_args: args_dev must be a contiguous uint8 GPU tensor of at least {adam_ema_args_size()} bytes")
+    _lib.check(lib.diffsal_adam_ema_step_args(_p(p), _p(g), _p(m), _p(v), _p(s), n, args_dev.data_ptr(),
+                                              _p(norm) if norm is not None else None, int(store_clipped_grad), _stream()),
+               "adam_ema_step_args")
+
+
+@_classed("optim")
+def ema_swap(p: Tensor, s: Tensor) -> None:
+    """Exchange ``p`` and ``s`` in place, bit for bit, with one launch."""
+    lib = _lib.load()
+    if s.numel() != p.numel():
+        raise RuntimeError("ema_swap: p and s must have the same number of elements")
+    _lib.check(lib.diffsal_ema_swap(_p(p), _p(s), p.numel(), _stream()), "ema_swap")
+
+
+@_classed("optim")
 def scale_by(x: Tensor, s: Tensor) -> Tensor:
     """x * s[0] with s a one-element device tensor."""
     lib = _lib.load()

@@ -38,6 +38,7 @@ GPU only: a CPU model raises.
 """
 from __future__ import annotations
 
+import contextlib
 import csv
 import math
 import os
@@ -527,20 +528,57 @@ def milestones(epochs: int) -> List[int]:
 
 def checkpoint(model, trainer, epoch: int, step: int) -> dict:
     """The reference's checkpoint dictionary (R/diffusion_trainer.py:263-268, 408-413): ``state_dict`` is the model's,
-    ``optim_dict`` is ``torch.optim.Adam``'s format (``trainer.state_dict()``), ``epoch`` the number of finished epochs."""
-    return {"state_dict": model.state_dict(), "optim_dict": trainer.state_dict(), "epoch": int(epoch), "step": int(step)}
+    ``optim_dict`` is ``torch.optim.Adam``'s format (``trainer.state_dict()``), ``epoch`` the number of finished epochs.  A trainer
+    built with ``ema=`` adds ``ema_dict``, its ``ema_state_dict()``; the four reference keys are what they are without it."""
+    states = {"state_dict": model.state_dict(), "optim_dict": trainer.state_dict(), "epoch": int(epoch), "step": int(step)}
+    if getattr(trainer, "ema", None) is not None:
+        states["ema_dict"] = trainer.ema_state_dict()
+    return states
 
 
 def resume_from(path: str, model, trainer) -> Tuple[int, int]:
     """Loads ``state_dict`` and ``optim_dict`` of a checkpoint file (R/diffusion_trainer.py:183-190, 328-333) and returns its
-    ``(epoch, step)``.  The model is loaded with ``strict=False``, as the reference does."""
+    ``(epoch, step)``.  The model is loaded with ``strict=False``, as the reference does.  A trainer built with ``ema=`` also takes
+    the checkpoint's ``ema_dict``; from a checkpoint without one its shadow restarts as a copy of the loaded weights with no update
+    done, which is ``EMAHelper.register`` after a load."""
     states = torch.load(os.fspath(path), map_location="cpu")
     for key in ("state_dict", "optim_dict", "epoch", "step"):
         if key not in states:
             raise ValueError(f"train: {path}: a checkpoint holds state_dict, optim_dict, epoch and step; {key!r} is missing")
     model.load_state_dict(states["state_dict"], strict=False)
     trainer.load_state_dict(states["optim_dict"])
+    if getattr(trainer, "ema", None) is not None:
+        if "ema_dict" in states:
+            trainer.load_ema_state_dict(states["ema_dict"])
+        else:
+            trainer.reset_ema()
     return int(states["epoch"]), int(states["step"])
+
+
+def load_ema_weights(path: str, model) -> dict:
+    """A checkpoint's averaged weights into ``model``, for ``predict_directory`` / ``predict_av``: loads ``state_dict`` (``strict=False``,
+    as ``resume_from`` does), then overwrites every parameter named in ``ema_dict["shadow"]`` with its average and tells the
+    weight-pack caches of every module.  Buffers (BatchNorm running statistics) are the checkpoint's: they are not averaged.
+    Returns the ``ema_dict``.  A checkpoint without one, a name the model does not have or a shape that differs raises."""
+    states = torch.load(os.fspath(path), map_location="cpu")
+    for key in ("state_dict", "ema_dict"):
+        if key not in states:
+            raise ValueError(f"train: {path}: {key!r} is missing; load_ema_weights takes a checkpoint of a trainer built with ema=")
+    shadow = states["ema_dict"]["shadow"]
+    params = dict(model.named_parameters())
+    for name, value in shadow.items():
+        if name not in params:
+            raise ValueError(f"train: {path}: ema_dict names the parameter {name!r}, which the model does not have")
+        if tuple(value.shape) != tuple(params[name].shape):
+            raise ValueError(f"train: {path}: shadow of {name!r} has shape {tuple(value.shape)}, the parameter {tuple(params[name].shape)}")
+    model.load_state_dict(states["state_dict"], strict=False)
+    with torch.no_grad():
+        for name, value in shadow.items():
+            params[name].copy_(value)
+    for m in model.modules():
+        if hasattr(m, "parameters_updated"):
+            m.parameters_updated()
+    return states["ema_dict"]
 
 
 def _ranks(group) -> Tuple[int, int]:
@@ -553,13 +591,14 @@ def _ranks(group) -> Tuple[int, int]:
 
 def _fit(model, trainer, clips: list, out_root: str, epochs: int, batch: int, size, validate, *, seed: int, decode: str,
          steps_per_load: int, threads: int, log_freq: int, resume, stop_epoch, group, prefetch: bool, load_kw: dict,
-         report: FitReport) -> FitReport:
+         report: FitReport, ema_validation: bool = True) -> FitReport:
     p = next(iter(model.parameters()), None)
     if p is None or not p.is_cuda:
         raise RuntimeError("diff_sal_amd train runs on the GPU only (no CPU fallback); the model is on "
                            f"{'no device (it has no parameter)' if p is None else p.device}")
     if getattr(trainer, "model", model) is not model:
         raise ValueError("train: trainer was not built around this model")
+    use_ema = bool(ema_validation) and getattr(trainer, "ema", None) is not None
     _check_decode(decode, steps_per_load)
     epochs, batch, steps_per_load = int(epochs), int(batch), int(steps_per_load)
     if epochs < 1 or batch < 1 or not clips:
@@ -624,7 +663,9 @@ def _fit(model, trainer, clips: list, out_root: str, epochs: int, batch: int, si
                 torch.save(states, path)
                 report.checkpoints.append(path)
             if validate is not None:
-                val = validate()
+                # the checkpoint above holds the raw weights; val.log and the choice of best.pth refer to the average
+                with trainer.ema_weights() if use_ema else contextlib.nullcontext():
+                    val = validate()
                 vrow = val_row(epoch + 1, step, val.losses)
                 report.val_rows.append(vrow)
                 if writes:
@@ -650,7 +691,7 @@ def fit_directory(model, trainer, data_type: str, root: str, out_root: str, epoc
                   decode: str = DEFAULT_DECODE, steps_per_load: int = DEFAULT_STEPS_PER_LOAD, threads: int = 16, log_freq: int = 0,
                   resume: Optional[str] = None, stop_epoch: Optional[int] = None, group=None, prefetch: bool = True,
                   videos: Optional[Sequence] = None, val_videos: Optional[Sequence] = None, len_snippet: int = 32, alternate: int = 1,
-                  norm_value=None, mean=None, std=None) -> FitReport:
+                  norm_value=None, mean=None, std=None, ema_validation: bool = True) -> FitReport:
     """The reference's ``train()`` (R/diffusion_trainer.py:300-432) for ``list_train_clips(data_type, root, len_snippet=...,
     alternate=..., videos=videos)``.  ``trainer`` is the caller's ``DiffusionTrainStep`` around ``model``: ``loss_config``,
     ``noise_source``, ``t_mode`` and ``training_target`` are theirs.  Per epoch, from ``resume``'s epoch on:
@@ -673,6 +714,11 @@ def fit_directory(model, trainer, data_type: str, root: str, out_root: str, epoc
     run's parameters and moments.  ``group``: ``epoch_order`` shards the listing over its ranks and rank 0 writes; the
     validation shards its videos as ``predict_directory`` does.  Returns a ``FitReport``.
 
+    A trainer built with ``ema=`` has its average saved and restored (``ema_dict`` of the checkpoint) and, unless
+    ``ema_validation=False``, validated: ``validate`` runs inside ``trainer.ema_weights()``, so ``val.log`` and the choice of
+    ``best.pth`` refer to the averaged weights (the file itself holds the raw weights and the shadow; ``load_ema_weights`` is the
+    route from it to a prediction with the average).
+
     A trainer built with ``hip_graph=True`` works as it is: the loop calls ``trainer.step`` and reads ``trainer.last_losses`` and
     nothing else.  Its loss tensors are static, overwritten by the next step in stream order; the meters add them to their device
     sums right after each step, on the same stream, so they read every step's own values.  The front end's uploads run on the
@@ -687,7 +733,7 @@ def fit_directory(model, trainer, data_type: str, root: str, out_root: str, epoc
                                              alternate=alternate)
     return _fit(model, trainer, clips, out_root, epochs, batch, size, validate, seed=seed, decode=decode, steps_per_load=steps_per_load,
                 threads=threads, log_freq=log_freq, resume=resume, stop_epoch=stop_epoch, group=group, prefetch=prefetch,
-                load_kw=dict(norm_value=norm_value, mean=mean, std=std), report=FitReport())
+                load_kw=dict(norm_value=norm_value, mean=mean, std=std), report=FitReport(), ema_validation=ema_validation)
 
 
 def fit_av(model, trainer, sets: Sequence, out_root: str, epochs: int, batch: int, *, size=video_input.SAMPLE_SIZE, sampler=None,
@@ -695,7 +741,7 @@ def fit_av(model, trainer, sets: Sequence, out_root: str, epochs: int, batch: in
            decode: str = DEFAULT_DECODE, steps_per_load: int = DEFAULT_STEPS_PER_LOAD, threads: int = 16, log_freq: int = 0,
            resume: Optional[str] = None, stop_epoch: Optional[int] = None, group=None, prefetch: bool = True, drop_empty: bool = True,
            sample_duration: int = predict.CLIP_FRAMES, step_duration: int = 90, window: Optional[int] = None,
-           resample="kaiser_best") -> FitReport:
+           resample="kaiser_best", ema_validation: bool = True) -> FitReport:
     """The loop of the reference's ``train_av_data()`` (R/diffusion_trainer.py:139-298) for one split.  ``sets`` is a list of
     ``(video_root, fold_list, salmap_root, audio_root)``; their ``list_av_train_clips`` listings are concatenated in that order, as
     ``get_training_av_loader`` concatenates its six datasets (R/datasets/prepare_data.py:131-139).  Everything else is as in
@@ -730,4 +776,4 @@ def fit_av(model, trainer, sets: Sequence, out_root: str, epochs: int, batch: in
             return predict.Report(losses={k: (total[k] / chunks if chunks else float("nan")) for k in LOSS_NAMES}, chunks=chunks)
     return _fit(model, trainer, clips, out_root, epochs, batch, size, validate, seed=seed, decode=decode, steps_per_load=steps_per_load,
                 threads=threads, log_freq=log_freq, resume=resume, stop_epoch=stop_epoch, group=group, prefetch=prefetch,
-                load_kw=dict(window=window, resample=resample), report=report)
+                load_kw=dict(window=window, resample=resample), report=report, ema_validation=ema_validation)

@@ -30,6 +30,7 @@ message) at the start of each step.
 from __future__ import annotations
 
 import contextlib
+import gc
 from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
@@ -44,13 +45,25 @@ def _aligned(n: int, a: int = 64) -> int:
     return (n + a - 1) // a * a
 
 
+def ema_rate_at(mu: float, updates: int, warmup: bool) -> float:
+    """The rate of the EMA update that follows ``updates`` earlier ones: ``mu``, or with ``warmup`` the usual ramp
+    ``min(mu, (1 + updates) / (10 + updates))`` -- 0.1 for the first update, ``mu`` from the first count at which the ramp
+    reaches it.  A fixed 0.9999 would leave 86 % of the initial weights in the average after 1 500 steps, the length of a
+    reference run (3 epochs at batch 48); the ramp forgets them within a few dozen updates.  Python floats, no device value."""
+    mu, updates = float(mu), int(updates)
+    if not warmup:
+        return mu
+    return min(mu, (1.0 + updates) / (10.0 + updates))
+
+
 class FlatParams:
     """Flat fp32 storage for the trainable parameters of ``module`` (+ grads and optimizer moments).
 
     Layout: reverse registration order, each tensor padded to 64 elements (256 B) so every view is 16-byte aligned
-    for the vectorised kernels.  Padding stays zero in all four buffers (Adam maps 0 -> 0)."""
+    for the vectorised kernels.  Padding stays zero in all four buffers (Adam maps 0 -> 0).  ``shadow=True`` adds a fifth,
+    ``shadow``: a copy of ``flat_p`` (what ``EMAHelper.register`` makes per tensor), padding zero as well (the EMA of 0 and 0)."""
 
-    def __init__(self, module: nn.Module, bucket_bytes: int = 32 << 20):
+    def __init__(self, module: nn.Module, bucket_bytes: int = 32 << 20, shadow: bool = False):
         params = [p for p in module.parameters() if p.requires_grad]
         if not params:
             raise ValueError("FlatParams: module has no trainable parameters")
@@ -74,6 +87,7 @@ class FlatParams:
             view.copy_(p.data)
             p.data = view
             p.grad = None
+        self.shadow: Optional[Tensor] = self.flat_p.clone() if shadow else None
         # buckets: contiguous ranges of whole tensors, closed once they reach bucket_bytes
         self.buckets: List[range] = []       # element ranges of the flat buffer
         self.bucket_of: List[int] = []       # parameter index -> bucket
@@ -424,7 +438,22 @@ class DiffusionTrainStep:
       up the overlap of the exchange with backward.  Every rank must pass the same ``hip_graph`` (checked at construction).
     Measured on the full audio-visual step (224 x 384, batch 4, one MI355X): the replay is NOT faster, 66.0 ms
     against 65.9 ms eager on the same box -- the step is bound by the device, whose eager host issue takes 56.5 ms.  It cuts the
-    host's time in a step to 2.2 ms, costs 0.7 s for the capturing call and 64 MB of peak memory (14 544 against 14 480 MB)."""
+    host's time in a step to 2.2 ms, costs 0.7 s for the capturing call and 64 MB of peak memory (14 544 against 14 480 MB).
+
+    ``ema`` (default None: nothing below applies): keep an exponential moving average of the trained parameters at rate
+    ``ema`` in [0, 1] -- the reference's ``model.ema`` / ``model.ema_rate`` (R/cfgs/diffusion.yml) and its ``EMAHelper`` --
+    in a fifth flat buffer, ``flat.shadow``, that starts as a copy of the parameters (``EMAHelper.register``).  The update
+    ``shadow = (1 - mu) p + mu shadow`` runs inside the clip + Adam kernel on the new parameters (``ops.adam_ema_step``): no launch
+    of its own, and bit-equal to ``EMAHelper.update`` after the step.  ``ema_warmup=True`` ramps the rate (``ema_rate_at``); the
+    rate of a step is formed on the host from ``ema_updates``, the count of updates done, and reaches a captured step through the
+    device block its Adam reads, so a replay needs no new capture for it.  Every rank computes the same shadow; none is exchanged.
+    BatchNorm running statistics are buffers and are not averaged, as in ``EMAHelper``.
+    * ``ema_weights()``: a context manager inside which the model HOLDS the average -- weights and shadow are exchanged in place
+      by one launch on entry and again on exit (``ops.ema_swap``: bits move, nothing is rounded, so the exit restores the weights
+      exactly), with ``parameters_updated()`` after each.  No address changes, so a live capture stays valid.  ``step()``,
+      ``optimizer_step()``, ``load_ema_state_dict()`` and a nested entry raise ``RuntimeError`` inside it.
+    * ``ema_state_dict()`` / ``load_ema_state_dict()`` carry the shadow by parameter name (``EMAHelper.state_dict()``'s layout), the
+      update count, the rate and the warm-up switch; ``state_dict()`` stays ``torch.optim.Adam``'s format."""
 
     def __init__(self, model: nn.Module, *, lr: float = 1e-4, beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8,
                  weight_decay: float = 0.0, grad_clip: float = 1.0, mse_weight: float = 1.0,
@@ -434,7 +463,11 @@ class DiffusionTrainStep:
                  store_clipped_grad: bool = False, exchange_single_rank: bool = False,
                  loss_fn: Optional[Callable] = None, loss_config=None, exchange: str = "allreduce",
                  noise_source: str = "torch", seed: int = 0, t_mode: str = "batch", training_target: str = "x0",
-                 hip_graph: bool = False, graph_warmup: int = 2):
+                 hip_graph: bool = False, graph_warmup: int = 2, ema: Optional[float] = None, ema_warmup: bool = False):
+        if ema is not None and not 0.0 <= float(ema) <= 1.0:
+            raise ValueError(f"DiffusionTrainStep: ema={ema!r} must be a rate in [0, 1] (or None)")
+        if ema_warmup and ema is None:
+            raise ValueError("DiffusionTrainStep: ema_warmup=True needs ema=<rate>")
         if hip_graph and noise_source != "device":
             raise ValueError("DiffusionTrainStep: hip_graph=True needs noise_source='device': torch's generator and numpy's t0 "
                              "are host state, which a replayed graph would not advance")
@@ -470,7 +503,11 @@ class DiffusionTrainStep:
         self.sqrt_alphas_hat = torch.sqrt(alphas_hat)
         self.sqrt_one_minus_alphas_hat = torch.sqrt(1.0 - alphas_hat)
         self.num_timesteps = int(betas.shape[0])
-        self.flat = FlatParams(model, int(bucket_mb * (1 << 20)))
+        self.ema: Optional[float] = None if ema is None else float(ema)
+        self.ema_warmup = bool(ema_warmup)
+        self.ema_updates = 0                 # EMA updates done: what ema_rate_at counts from
+        self._ema_swapped = False            # inside ema_weights(): flat_p holds the average, shadow the weights
+        self.flat = FlatParams(model, int(bucket_mb * (1 << 20)), shadow=self.ema is not None)
         self.optimizer = FlatAdam(self, self.flat.params, float(lr), (float(beta1), float(beta2)), float(eps), float(weight_decay))
         self.group = process_group
         self.reducer = GradReducer(self.flat, process_group, exchange_single_rank, exchange)
@@ -670,7 +707,15 @@ class DiffusionTrainStep:
         norm = ops.grad_norm(self.flat.flat_g, gscale) if self.grad_clip > 0 else None
         self.last_norm = norm
         f = self.flat
-        if args_dev is not None:
+        if self.ema is not None:
+            if args_dev is not None:
+                ops.adam_ema_step_args(f.flat_p, f.flat_g, f.exp_avg, f.exp_avg_sq, f.shadow, args_dev, norm, self.store_clipped_grad)
+            else:
+                ops.adam_ema_step(f.flat_p, f.flat_g, f.exp_avg, f.exp_avg_sq, f.shadow, step=self.step_count + 1,
+                                  lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, gscale=gscale,
+                                  norm=norm, max_norm=self.grad_clip, store_clipped_grad=self.store_clipped_grad,
+                                  ema_mu=ema_rate_at(self.ema, self.ema_updates, self.ema_warmup))
+        elif args_dev is not None:
             ops.adam_step_args(f.flat_p, f.flat_g, f.exp_avg, f.exp_avg_sq, args_dev, norm, self.store_clipped_grad)
         else:
             ops.adam_step(f.flat_p, f.flat_g, f.exp_avg, f.exp_avg_sq, step=self.step_count + 1,
@@ -680,11 +725,14 @@ class DiffusionTrainStep:
     def optimizer_step(self) -> None:
         from . import ops
 
+        self._not_in_ema_weights("optimizer_step()")
         if self.train_key is not None:
             ops.train_draw(self.step_count + 1, 0)     # the host mirror of the draw word's 27-bit step field
         if not self._in_graph:
             self._device_tail()
         self.step_count += 1
+        if self.ema is not None:
+            self.ema_updates += 1
         self._parameters_updated()
 
     def step(self, sal_maps: Tensor, cond: Dict, *, t0: Optional[int] = None, noise: Optional[Tensor] = None,
@@ -692,6 +740,7 @@ class DiffusionTrainStep:
         """One training step on this rank's clips; returns the (detached, device-resident) loss.  ``sample_ids``: one id per
         sample, required with (and only with) ``noise_source="device"``.  With ``hip_graph=True`` the returned tensor is static:
         the next step overwrites it in stream order (see the class)."""
+        self._not_in_ema_weights("step()")
         if self.hip_graph and t0 is None and noise is None and dequant_noise is None and self._graphable(sal_maps):
             return self._graph_step(sal_maps, cond, sample_ids)
         return self._eager_step(sal_maps, cond, t0=t0, noise=noise, dequant_noise=dequant_noise, sample_ids=sample_ids)
@@ -761,11 +810,20 @@ class DiffusionTrainStep:
         ent.sal, ent.ids = torch.empty_like(sal_maps).copy_(sal_maps), ids.clone()
         ent.cond = self._cond_like(cond, [torch.empty_like(v).copy_(v) for v in flat])
         if self._adam_dev is None:
-            self._adam_dev = torch.zeros((_aligned(ops.adam_args_size()),), dtype=torch.uint8, device=dev)
+            size = ops.adam_args_size() if self.ema is None else ops.adam_ema_args_size()
+            self._adam_dev = torch.zeros((_aligned(size),), dtype=torch.uint8, device=dev)
         self._parameters_updated()          # whatever an eval() forward cached since the last step is packed again inside
         with ops.batched_packs(self._packs):
             pass                            # the pack table is built (a host upload) and the dead entries leave it now
         torch.cuda.synchronize(dev)
+        # Dead reference cycles that own device state (an earlier trainer with its captures and pools) are destroyed by whichever
+        # thread the collector next runs on; inside a global-mode capture their frees and graph destructions are illegal calls and
+        # abort the process.  torch.cuda.graph collected before a capture up to torch 2.9 and no longer does by default: collect
+        # here, and keep the collector off until the capture has ended (backward runs on autograd's threads: the switch is
+        # process-wide).
+        gc.collect()
+        gc_was_on = gc.isenabled()
+        gc.disable()
         graph = torch.cuda.CUDAGraph()
         self.reducer.deferred = self.reducer.exchange
         try:
@@ -776,6 +834,8 @@ class DiffusionTrainStep:
                                f"({type(e).__name__}: {e})") from e
         finally:
             self.reducer.deferred = False
+            if gc_was_on:
+                gc.enable()
         ent.losses, ent.norm = self.last_losses, self.last_norm
         # the table and the packed weights the captured launches address stay alive with the capture
         ent.keep = (self._packs.table, [e[1] for e in self._packs.entries.values()])
@@ -809,8 +869,12 @@ class DiffusionTrainStep:
                 self._sync_buffers()
         else:
             # a fresh pinned block every step: the host allocator hands it out again only after this copy has run
-            block = ops.adam_args(step=self.step_count + 1, lr=self.lr, betas=self.betas, eps=self.eps,
-                                  weight_decay=self.weight_decay, gscale=1.0 / self.world, max_norm=self.grad_clip)
+            hp = dict(step=self.step_count + 1, lr=self.lr, betas=self.betas, eps=self.eps, weight_decay=self.weight_decay,
+                      gscale=1.0 / self.world, max_norm=self.grad_clip)
+            if self.ema is None:
+                block = ops.adam_args(**hp)
+            else:       # this step's rate travels with Adam's numbers: a warm-up that moves every step needs no new capture
+                block = ops.adam_ema_args(ema_mu=ema_rate_at(self.ema, self.ema_updates, self.ema_warmup), **hp)
             self._adam_dev[:block.numel()].copy_(block, non_blocking=True)
         ent.graph.replay()
         self.graph_replays += 1
@@ -825,6 +889,78 @@ class DiffusionTrainStep:
             finally:
                 self._in_graph = False
         return ent.loss
+
+    # ---- the averaged weights ----
+    def _not_in_ema_weights(self, what: str) -> None:
+        if self._ema_swapped:
+            raise RuntimeError(f"DiffusionTrainStep: {what} inside ema_weights(): the model holds the averaged weights; leave the "
+                               "context first")
+
+    def _need_ema(self, what: str) -> None:
+        if self.ema is None:
+            raise RuntimeError(f"DiffusionTrainStep: {what} needs a trainer built with ema=<rate>")
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """Inside the context the model's trained parameters are the average (see the class)."""
+        from . import ops
+
+        self._need_ema("ema_weights()")
+        self._not_in_ema_weights("ema_weights()")
+        ops.ema_swap(self.flat.flat_p, self.flat.shadow)
+        self._ema_swapped = True
+        self._parameters_updated()
+        try:
+            yield self
+        finally:
+            ops.ema_swap(self.flat.flat_p, self.flat.shadow)
+            self._ema_swapped = False
+            self._parameters_updated()
+
+    def _named_slots(self):
+        """(name, parameter, offset in the flat buffers) of every trained parameter, in ``named_parameters()`` order"""
+        slot = {id(p): k for k, p in enumerate(self.flat.params)}
+        return [(name, p, self.flat.offsets[slot[id(p)]]) for name, p in self.model.named_parameters() if id(p) in slot]
+
+    def ema_state_dict(self) -> Dict:
+        """``{"shadow": {parameter name: tensor}, "updates", "mu", "warmup"}``; ``shadow`` is ``EMAHelper.state_dict()``'s layout
+        (the trained parameters by name), cloned out of the flat buffer."""
+        self._need_ema("ema_state_dict()")
+        src = self.flat.flat_p if self._ema_swapped else self.flat.shadow
+        return {"shadow": {name: src[o:o + p.numel()].view(p.shape).clone() for name, p, o in self._named_slots()},
+                "updates": int(self.ema_updates), "mu": float(self.ema), "warmup": bool(self.ema_warmup)}
+
+    def load_ema_state_dict(self, sd: Dict) -> None:
+        """Inverse of ``ema_state_dict``; ``{"shadow": EMAHelper.state_dict()}`` alone loads too (``updates`` then restarts at 0,
+        rate and warm-up stay this trainer's).  Every name and shape is checked before anything is written; the shadow is written
+        in place, so a live capture goes on from it."""
+        self._need_ema("load_ema_state_dict()")
+        self._not_in_ema_weights("load_ema_state_dict()")
+        if not isinstance(sd, dict) or "shadow" not in sd:
+            raise ValueError("load_ema_state_dict expects {'shadow': {parameter name: tensor}, 'updates', 'mu', 'warmup'}")
+        shadow, slots = sd["shadow"], self._named_slots()
+        missing = [name for name, _, _ in slots if name not in shadow]
+        extra = sorted(set(shadow) - {name for name, _, _ in slots})
+        if missing or extra:
+            raise ValueError(f"load_ema_state_dict: missing {missing}, unexpected {extra}")
+        for name, p, _ in slots:
+            if tuple(shadow[name].shape) != tuple(p.shape):
+                raise ValueError(f"load_ema_state_dict: shadow of {name!r} has shape {tuple(shadow[name].shape)}, the parameter "
+                                 f"{tuple(p.shape)}")
+        mu = float(sd.get("mu", self.ema))
+        if not 0.0 <= mu <= 1.0:
+            raise ValueError(f"load_ema_state_dict: mu={mu!r} must be in [0, 1]")
+        for name, p, o in slots:
+            self.flat.shadow[o:o + p.numel()].view(p.shape).copy_(shadow[name])
+        self.ema, self.ema_warmup = mu, bool(sd.get("warmup", self.ema_warmup))
+        self.ema_updates = int(sd.get("updates", 0))
+
+    def reset_ema(self) -> None:
+        """The shadow restarts as a copy of the current parameters with no update done: ``EMAHelper.register`` after a load."""
+        self._need_ema("reset_ema()")
+        self._not_in_ema_weights("reset_ema()")
+        self.flat.shadow.copy_(self.flat.flat_p)
+        self.ema_updates = 0
 
     # ---- checkpoint surface of torch.optim.Adam (R/diffusion_trainer.py:187-193, 263-268: "optim_dict") ----
     def _indexed_params(self):

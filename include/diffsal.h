@@ -1324,6 +1324,14 @@ int diffsal_train_key_advance(unsigned long long* key, diffsal_stream_t stream);
  *   of an adam_args block made in stream order before the launch) -- nothing of the step number, the learning rate or
  *   the clip bound is a launch argument, so a captured graph replays it for any step (R/diffusion_trainer.py:228-235
  *   once per replay).  Same grid, vector width, tail and arithmetic as adam_step: bit-identical results.
+ * adam_ema_step / adam_ema_args / adam_ema_step_args: the three above with a shadow buffer `s` (an exponential moving average
+ *   of p, R/models/diffusion_decoder/ema.py:4-48) updated in the same pass, from the NEW p:
+ *   s = fmaf(mu, s, omm * p) with omm = (float)(1 - ema_mu) and mu = (float)ema_mu formed on the host -- the rounding
+ *   sequence of axpbypcz(p, 1 - ema_mu, s, ema_mu), so the shadow is bit-equal to adam_step followed by that call, and p, g,
+ *   m, v are bit-equal to adam_step's.  0 <= ema_mu <= 1.  The block of adam_ema_args_size() bytes is adam_args' block
+ *   followed by the two floats omm, mu; adam_args_size() and its block are unchanged.
+ * ema_swap: exchanges p and s in place, bit for bit (NaN payloads and -0 survive), one launch, no third buffer; the
+ *   buffers must not overlap.  Its own inverse.
  * scale_by: out = x * s[0] with s a device scalar (the incoming d(loss) of the MSE backward); any n > 0.
  * multi_copy: dst[dst_offsets[i] .. +sizes[i]) = srcs[i][0 .. sizes[i]) for i < count, a few launches for any count
  *   (gathers the per-parameter gradients autograd produced into the flat gradient buffer; the three tables are HOST
@@ -1344,6 +1352,15 @@ int diffsal_adam_args(double lr, double beta1, double beta2, double eps, double 
                       float max_norm, void* out /*host*/);
 int diffsal_adam_step_args(float* p, float* g, float* m, float* v, long n, const void* args_dev, const float* norm,
                            int store_clipped_grad, diffsal_stream_t stream);
+int diffsal_adam_ema_step(float* p, float* g, float* m, float* v, float* s, long n, double lr, double beta1, double beta2,
+                          double eps, double weight_decay, int step, float gscale, const float* norm, float max_norm,
+                          int store_clipped_grad, double ema_mu, diffsal_stream_t stream);
+size_t diffsal_adam_ema_args_size(void);
+int diffsal_adam_ema_args(double lr, double beta1, double beta2, double eps, double weight_decay, int step, float gscale,
+                          float max_norm, double ema_mu, void* out /*host*/);
+int diffsal_adam_ema_step_args(float* p, float* g, float* m, float* v, float* s, long n, const void* args_dev,
+                               const float* norm, int store_clipped_grad, diffsal_stream_t stream);
+int diffsal_ema_swap(float* p, float* s, long n, diffsal_stream_t stream);
 
 #ifdef __cplusplus
 }
