@@ -27,8 +27,13 @@ def lib():
     return ops, autograd_ops, _lib
 
 
-def dev32(t):
-    return t.float().contiguous().to(DEV)
+def to_dev(t):
+    """The upload of every case body here; tests/test_gpu_guard_bands.py passes tests/_guard.py's ``put`` in its place."""
+    return t.to(DEV)
+
+
+def dev32(t, up=to_dev):
+    return up(t.float().contiguous())
 
 
 def record(family, ratio):
@@ -58,13 +63,12 @@ def raw_resize_bwd(lib, dy, h, w, route):
     return dx
 
 
-@pytest.mark.parametrize("case", R.RESIZE_EXACT, ids=R.case_id)
-def test_resize_adjoint_is_exact_on_every_route(lib, case):
+def case_resize_adjoint_is_exact_on_every_route(lib, case, up=to_dev):
     ops, ag, _ = lib
     (h, w), (H, W), Cc = case
     dy = R.resize_operands(case)
     ref = R.resize_bwd64(dy, h, w)
-    dyd = dev32(dy)
+    dyd = dev32(dy, up)
     outs = {r: raw_resize_bwd(lib, dyd, h, w, r) for r in R.resize_routes(case)}
     for r, got in outs.items():
         R.check_exact(got, ref, f"route {r}")
@@ -75,19 +79,28 @@ def test_resize_adjoint_is_exact_on_every_route(lib, case):
     record("resize (exact)", 0.0)
 
 
-@pytest.mark.parametrize("case", R.RESIZE_BOUNDED, ids=R.case_id)
-def test_resize_adjoint_at_other_ratios_within_the_counted_bound(lib, case):
+@pytest.mark.parametrize("case", R.RESIZE_EXACT, ids=R.case_id)
+def test_resize_adjoint_is_exact_on_every_route(lib, case):
+    case_resize_adjoint_is_exact_on_every_route(lib, case)
+
+
+def case_resize_adjoint_at_other_ratios_within_the_counted_bound(lib, case, up=to_dev):
     ops, _, _ = lib
     (h, w), (H, W), Cc = case
     dy = R.resize_operands(case, exact=False)
     ref = R.resize_bwd64(dy, h, w)
-    dyd = dev32(dy)
+    dyd = dev32(dy, up)
     worst = 0.0
     for r in R.resize_routes(case):
         worst = max(worst, R.check_bound(raw_resize_bwd(lib, dyd, h, w, r), ref, R.resize_bound(dy, case, r), f"route {r}"))
     worst = max(worst, R.check_bound(ops.resize_bilinear_bwd(dyd, h, w), ref, R.resize_bound(dy, case, "joint4"), "ops"))
     print("routes:", case, R.resize_routes(case))
     record("resize (bounded)", worst)
+
+
+@pytest.mark.parametrize("case", R.RESIZE_BOUNDED, ids=R.case_id)
+def test_resize_adjoint_at_other_ratios_within_the_counted_bound(lib, case):
+    case_resize_adjoint_at_other_ratios_within_the_counted_bound(lib, case)
 
 
 def test_resize_autograd_node_is_the_exact_adjoint(lib):
@@ -101,13 +114,17 @@ def test_resize_autograd_node_is_the_exact_adjoint(lib):
 
 
 # ---- tapsum_bwd ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", R.TAPSUM_CASES, ids=R.case_id)
-def test_tapsum_bwd_is_exact(lib, case):
+def case_tapsum_bwd_is_exact(lib, case, up=to_dev):
     ops, _, _ = lib
     (H, W), (h, w), Cc, dil = case
     du = R.tapsum_operands(case)
-    R.check_exact(ops.tapsum_bwd(dev32(du), h, w, dil), R.tapsum_bwd64(du, h, w, dil), "tapsum_bwd")
+    R.check_exact(ops.tapsum_bwd(dev32(du, up), h, w, dil), R.tapsum_bwd64(du, h, w, dil), "tapsum_bwd")
     record("tapsum_bwd", 0.0)
+
+
+@pytest.mark.parametrize("case", R.TAPSUM_CASES, ids=R.case_id)
+def test_tapsum_bwd_is_exact(lib, case):
+    case_tapsum_bwd_is_exact(lib, case)
 
 
 def test_tapsum_bwd_writes_its_slice_of_a_larger_buffer_and_nothing_else(lib):
@@ -137,19 +154,23 @@ def test_tapsum_autograd_node_fills_every_source_block(lib):
 
 
 # ---- col2im ----------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("kind,case", [("disjoint", c) for c in R.COL2IM_DISJOINT] + [("gather", c) for c in R.COL2IM_GATHER],
-                         ids=lambda v: v if isinstance(v, str) else R.case_id(v))
-def test_col2im_is_exact(lib, kind, case):
+def case_col2im_is_exact(lib, kind, case, up=to_dev):
     ops, _, _ = lib
     kh, kw, stride, pad, extra, H, W, Cc = case
     cols = R.col2im_operands(case)
     ref = R.col2im64(cols, case)
     fn = ops.col2im_disjoint if kind == "disjoint" else ops.col2im_gather
-    got = fn(dev32(cols), (2, H, W, Cc), R.col2im_out_hw(case), kh, kw, stride, pad)
+    got = fn(dev32(cols, up), (2, H, W, Cc), R.col2im_out_hw(case), kh, kw, stride, pad)
     R.check_exact(got, ref, "col2im_" + kind)
     if kind == "disjoint":                                                   # the gather kernel handles disjoint taps too
-        R.check_exact(ops.col2im_gather(dev32(cols), (2, H, W, Cc), R.col2im_out_hw(case), kh, kw, stride, pad), ref, "gather on disjoint taps")
+        R.check_exact(ops.col2im_gather(dev32(cols, up), (2, H, W, Cc), R.col2im_out_hw(case), kh, kw, stride, pad), ref, "gather on disjoint taps")
     record("col2im", 0.0)
+
+
+@pytest.mark.parametrize("kind,case", [("disjoint", c) for c in R.COL2IM_DISJOINT] + [("gather", c) for c in R.COL2IM_GATHER],
+                         ids=lambda v: v if isinstance(v, str) else R.case_id(v))
+def test_col2im_is_exact(lib, kind, case):
+    case_col2im_is_exact(lib, kind, case)
 
 
 @pytest.mark.parametrize("kind", ["gather", "disjoint"])
@@ -182,13 +203,12 @@ def test_strided_convolution_node_reaches_col2im_and_stays_exact(lib, kind):
 
 
 # ---- depthwise convolution -------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", R.DWCONV_CASES, ids=R.case_id)
-def test_dwconv_forward_and_both_gradients_are_exact(lib, case):
+def case_dwconv_forward_and_both_gradients_are_exact(lib, case, up=to_dev):
     ops, ag, _ = lib
     Cc, H, W, k, stride, pad = case
     x, w, du = R.dwconv_operands(case)
     out, dx, dw = R.dwconv64(x, w, du, case)
-    xd, wd, dud = dev32(x), dev32(w), dev32(du)
+    xd, wd, dud = dev32(x, up), dev32(w, up), dev32(du, up)
     R.check_exact(ops.dwconv(xd, wd, k, stride, pad), out, "dwconv")
     gdx, gdw = ops.dwconv_bwd(xd, wd, dud, k, stride, pad)
     R.check_exact(gdx, dx, "dwconv_bwd_data")
@@ -201,15 +221,24 @@ def test_dwconv_forward_and_both_gradients_are_exact(lib, case):
     record("dwconv", 0.0)
 
 
+@pytest.mark.parametrize("case", R.DWCONV_CASES, ids=R.case_id)
+def test_dwconv_forward_and_both_gradients_are_exact(lib, case):
+    case_dwconv_forward_and_both_gradients_are_exact(lib, case)
+
+
 # ---- head ------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", R.HEAD_CASES, ids=R.case_id)
-def test_head_bwd_is_exact(lib, case):
+def case_head_bwd_is_exact(lib, case, up=to_dev):
     ops, _, _ = lib
     y, w, s, ds = R.head_operands(case)
-    dy, dw, db = ops.head_bwd(dev32(y), dev32(w), dev32(s), dev32(ds))
+    dy, dw, db = ops.head_bwd(dev32(y, up), dev32(w, up), dev32(s, up), dev32(ds, up))
     for n, a, b in zip(("dy", "dw", "db"), (dy, dw, db), R.head_bwd64(y, w, s, ds)):
         R.check_exact(a, b, n)
     record("head_bwd", 0.0)
+
+
+@pytest.mark.parametrize("case", R.HEAD_CASES, ids=R.case_id)
+def test_head_bwd_is_exact(lib, case):
+    case_head_bwd_is_exact(lib, case)
 
 
 @pytest.mark.parametrize("case", R.HEAD_E2E_CASES, ids=R.case_id)
@@ -226,44 +255,51 @@ def test_head_sigmoid_end_to_end_within_the_measured_bound(lib, case):
 
 
 # ---- conv_in ---------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", R.CONV_IN_CASES, ids=R.case_id)
-def test_conv_in_bwd_is_exact(lib, case):
+def case_conv_in_bwd_is_exact(lib, case, up=to_dev):
     ops, ag, _ = lib
     x, dy = R.conv_in_operands(case)
     dw, db = R.conv_in_bwd64(x, dy)
-    gdw, gdb = ops.conv_in_bwd(dev32(x), dev32(dy))
+    gdw, gdb = ops.conv_in_bwd(dev32(x, up), dev32(dy, up))
     R.check_exact(gdw, dw, "dw")
     R.check_exact(gdb, db, "db")
     if case == R.CONV_IN_CASES[2]:                                           # the autograd node, once
         Cc = case[3]
         wl, bl = torch.zeros(Cc, 9, device=DEV, requires_grad=True), torch.zeros(Cc, device=DEV, requires_grad=True)
-        ag.conv_in(dev32(x), wl, bl, 0).backward(dev32(dy))
+        ag.conv_in(dev32(x, up), wl, bl, 0).backward(dev32(dy, up))
         R.check_exact(wl.grad, dw, "ConvInFn dw")
         R.check_exact(bl.grad, db, "ConvInFn db")
     record("conv_in_bwd", 0.0)
 
 
+@pytest.mark.parametrize("case", R.CONV_IN_CASES, ids=R.case_id)
+def test_conv_in_bwd_is_exact(lib, case):
+    case_conv_in_bwd_is_exact(lib, case)
+
+
 # ---- dense_small -----------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", R.DENSE_CASES, ids=R.case_id)
-def test_dense_small_bwd_without_swish_is_exact(lib, case):
+def case_dense_small_bwd_without_swish_is_exact(lib, case, up=to_dev):
     ops, ag, _ = lib
     x, w, dout = R.dense_operands(case, False)
     refs = R.dense_bwd(x, w, dout, False)
-    for n, a, b in zip(("dx", "dw", "db"), ops.dense_small_bwd(dev32(x), dev32(w), dev32(dout), False), refs):
+    for n, a, b in zip(("dx", "dw", "db"), ops.dense_small_bwd(dev32(x, up), dev32(w, up), dev32(dout, up), False), refs):
         R.check_exact(a, b, n)
     if case == R.DENSE_CASES[5]:                                             # the autograd node, once (the time embedding's shape)
-        xl, wl, bl = dev32(x).requires_grad_(True), dev32(w).requires_grad_(True), torch.zeros(case[2], device=DEV, requires_grad=True)
-        ag.dense_small(xl, wl, bl, False).backward(dev32(dout))
+        xl, wl, bl = dev32(x, up).requires_grad_(True), dev32(w, up).requires_grad_(True), torch.zeros(case[2], device=DEV, requires_grad=True)
+        ag.dense_small(xl, wl, bl, False).backward(dev32(dout, up))
         for n, a, b in zip(("dx", "dw", "db"), (xl.grad, wl.grad, bl.grad), refs):
             R.check_exact(a, b, n + " (DenseSmallFn)")
     record("dense_small_bwd (exact)", 0.0)
 
 
 @pytest.mark.parametrize("case", R.DENSE_CASES, ids=R.case_id)
-def test_dense_small_bwd_with_swish_within_the_measured_bound(lib, case):
+def test_dense_small_bwd_without_swish_is_exact(lib, case):
+    case_dense_small_bwd_without_swish_is_exact(lib, case)
+
+
+def case_dense_small_bwd_with_swish_within_the_measured_bound(lib, case, up=to_dev):
     ops, _, _ = lib
     x, w, dout = R.dense_operands(case, True)
-    got = dict(zip(("dx", "dw", "db"), ops.dense_small_bwd(dev32(x), dev32(w), dev32(dout), True)))
+    got = dict(zip(("dx", "dw", "db"), ops.dense_small_bwd(dev32(x, up), dev32(w, up), dev32(dout, up), True)))
     tols = {n: (tol, ref) for n, tol, ref in R.measured_tols("dense", case)}
     worst = max(R.check_bound(got[n], tols[n][1], tols[n][0], n) for n in ("dx", "dw"))
     db_tol = max(case[0] - 1, 0) * R.U * R.dense_mag(x, w, dout, True)[2]                       # COUNTED: no swish on its path, B - 1 additions
@@ -271,13 +307,17 @@ def test_dense_small_bwd_with_swish_within_the_measured_bound(lib, case):
     record("dense_small_bwd (swish)", worst)
 
 
+@pytest.mark.parametrize("case", R.DENSE_CASES, ids=R.case_id)
+def test_dense_small_bwd_with_swish_within_the_measured_bound(lib, case):
+    case_dense_small_bwd_with_swish_within_the_measured_bound(lib, case)
+
+
 # ---- audio_fuse ------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", R.AUDIO_CASES, ids=R.case_id)
-def test_audio_fuse_and_its_backward_within_the_measured_bound(lib, case):
+def case_audio_fuse_and_its_backward_within_the_measured_bound(lib, case, up=to_dev):
     ops, ag, _ = lib
-    B, T, Cc, h, w, up = case
+    B, T, Cc, h, w, _ = case
     a, x, dout = R.audio_operands(case)
-    ad, xd, gd = dev32(a), dev32(x), dev32(dout)
+    ad, xd, gd = dev32(a, up), dev32(x, up), dev32(dout, up)
     out = ops.audio_fuse(ad, xd, h, w)
     dx, da = ops.audio_fuse_bwd(ad, xd, gd, h, w)
     got = dict(out=out, dx=dx, da=da)
@@ -288,6 +328,11 @@ def test_audio_fuse_and_its_backward_within_the_measured_bound(lib, case):
         o2.backward(gd)
         assert torch.equal(o2.detach(), out) and torch.equal(xl.grad, dx) and torch.equal(al.grad, da)
     record("audio_fuse", worst)
+
+
+@pytest.mark.parametrize("case", R.AUDIO_CASES, ids=R.case_id)
+def test_audio_fuse_and_its_backward_within_the_measured_bound(lib, case):
+    case_audio_fuse_and_its_backward_within_the_measured_bound(lib, case)
 
 
 def test_audio_fuse_bwd_refuses_an_up_factor_above_eight(lib):
@@ -343,20 +388,24 @@ def test_dropout_mask_is_the_hash_and_its_own_backward(lib, n, p):
 
 
 # ---- mse_loss --------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", R.MSE_NS)
-@pytest.mark.parametrize("want_grad", [True, False])
-def test_mse_loss_value_within_the_counted_bound_and_gradient_exact(lib, n, want_grad):
+def case_mse_loss_value_within_the_counted_bound_and_gradient_exact(lib, n, want_grad, up=to_dev):
     ops, _, _ = lib
     pred, tgt = R.mse_operands(n)
     scale = 0.7 / 3
     loss64, dp32, mag = R.mse64(pred, tgt, scale)
-    loss, dpred = ops.mse_loss(dev32(pred), dev32(tgt), scale, want_grad=want_grad)
+    loss, dpred = ops.mse_loss(dev32(pred, up), dev32(tgt, up), scale, want_grad=want_grad)
     worst = R.check_bound(loss.reshape(()), loss64, R.MSE_K * R.U * mag, "loss")
     if want_grad:
         assert torch.equal(dpred.cpu(), dp32), f"{int((dpred.cpu() != dp32).sum())} of {n} gradient elements differ"
     else:
         assert dpred is None
     record("mse_loss", worst)
+
+
+@pytest.mark.parametrize("n", R.MSE_NS)
+@pytest.mark.parametrize("want_grad", [True, False])
+def test_mse_loss_value_within_the_counted_bound_and_gradient_exact(lib, n, want_grad):
+    case_mse_loss_value_within_the_counted_bound_and_gradient_exact(lib, n, want_grad)
 
 
 def test_mse_loss_node_runs_a_map_whose_size_is_no_multiple_of_four(lib):
@@ -373,15 +422,19 @@ def test_mse_loss_node_runs_a_map_whose_size_is_no_multiple_of_four(lib):
 
 
 # ---- grad_norm -------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("n", R.NORM_NS)
-@pytest.mark.parametrize("spread", [False, True])
-def test_grad_norm_within_one_rounding(lib, n, spread):
+def case_grad_norm_within_one_rounding(lib, n, spread, up=to_dev):
     ops, _, _ = lib
     g = R.norm_operands(n, spread)
     for gscale in (1.0, 0.25):
         ref = gscale * g.double().norm()
-        worst = R.check_bound(ops.grad_norm(dev32(g), gscale).reshape(()), ref, R.NORM_REL * ref, f"gscale {gscale}")
+        worst = R.check_bound(ops.grad_norm(dev32(g, up), gscale).reshape(()), ref, R.NORM_REL * ref, f"gscale {gscale}")
     record("grad_norm", worst)
+
+
+@pytest.mark.parametrize("n", R.NORM_NS)
+@pytest.mark.parametrize("spread", [False, True])
+def test_grad_norm_within_one_rounding(lib, n, spread):
+    case_grad_norm_within_one_rounding(lib, n, spread)
 
 
 # ---- adam_step -------------------------------------------------------------------------------------------------------------------------

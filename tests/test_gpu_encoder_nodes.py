@@ -18,17 +18,21 @@ def lib():
     return ops, encoder_autograd
 
 
-def dev32(t):
-    return t.float().to(DEV)
+def to_dev(t):
+    """The upload of every case body here; tests/test_gpu_guard_bands.py passes tests/_guard.py's ``put`` in its place."""
+    return t.to(DEV)
+
+
+def dev32(t, up=to_dev):
+    return up(t.float())
 
 
 # ---- relative-position projection ------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", R.RELPOS_CASES, ids=R.case_id)
-def test_relpos_project_forward_and_backward_are_exact(lib, case):
+def case_relpos_project_forward_and_backward_are_exact(lib, case, up=to_dev):
     ops, eg = lib
     q_size, k_size, E, BH, D = case
     q, Rs, dE, acc = R.relpos_operands(case)
-    qd, Rd, dEd = dev32(q), [dev32(r) for r in Rs], dev32(dE)
+    qd, Rd, dEd = dev32(q, up), [dev32(r, up) for r in Rs], dev32(dE, up)
     ref = R.relpos_extra64(q, Rs, q_size, k_size, E)
     ex = ops.relpos_project(qd, *Rd, q_size, k_size, E)
     R.check_exact(ex, ref, "extra")
@@ -44,7 +48,7 @@ def test_relpos_project_forward_and_backward_are_exact(lib, case):
         R.check_exact(a, b, n)
     assert int(got[0][:, :, 0].count_nonzero()) == 0
     # accumulate: the tensor passed in is the one returned, and it holds its old value plus the projection's gradient
-    accd = dev32(acc)
+    accd = dev32(acc, up)
     refs_acc = R.relpos_bwd64(q, Rs, dE, q_size, k_size, E, dq_accum=acc)
     got_acc = ops.relpos_project_bwd(dEd, qd, *Rd, q_size, k_size, dq_accum=accd)
     assert got_acc[0] is accd
@@ -58,6 +62,11 @@ def test_relpos_project_forward_and_backward_are_exact(lib, case):
     (out * dEd).sum().backward()
     for n, a, b in zip(names, [ql.grad] + [r.grad for r in Rl], refs):
         R.check_exact(a, b, n + " (RelposProjectFn)")
+
+
+@pytest.mark.parametrize("case", R.RELPOS_CASES, ids=R.case_id)
+def test_relpos_project_forward_and_backward_are_exact(lib, case):
+    case_relpos_project_forward_and_backward_are_exact(lib, case)
 
 
 @pytest.mark.parametrize("case", R.ATTENTION_CASES, ids=R.case_id)
@@ -110,29 +119,27 @@ def test_relpos_attention_node_against_the_two_nodes_and_fp64(lib, case, monkeyp
 
 
 # ---- relative-position tables ----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("D", R.REL_DS)
-@pytest.mark.parametrize("block", R.REL_BLOCKS, ids=R.case_id)
-def test_rel_tables_forward_backward_and_an_unused_table(lib, block, D):
+def case_rel_tables_forward_backward_and_an_unused_table(lib, block, D, up=to_dev):
     ops, eg = lib
-    plans = tuple(R.rel_plan(*geom, DEV) for geom in block)
+    plans = tuple({k: up(v) if torch.is_tensor(v) else v for k, v in R.rel_plan(*geom, DEV).items()} for geom in block)
     g = R.generator(77 + D)
     rels = [torch.randn(geom[0], D, generator=g) for geom in block]
     douts = [R.ints(g, (geom[1], geom[2], D)).float() for geom in block]
-    outs = ops.rel_tables([r.to(DEV) for r in rels], plans)
+    outs = ops.rel_tables([up(r) for r in rels], plans)
     worst_f = worst_b = 0.0
     for rel, pl, out in zip(rels, plans, outs):
         ref, tol = R.rel_table64(rel, pl)
         worst_f = max(worst_f, R.check_bound(out, ref, tol, "rel_tables"))
-    grads = ops.rel_tables_bwd([d.to(DEV) for d in douts], plans)
+    grads = ops.rel_tables_bwd([up(d) for d in douts], plans)
     for dout, pl, got in zip(douts, plans, grads):
         ref, tol = R.rel_table_bwd64(dout, pl)
         worst_b = max(worst_b, R.check_bound(got, ref, tol, "rel_tables_bwd"))
     print(f"{R.case_id(block)} D={D}: worst ratio to the bound: forward {worst_f:.3f}, backward {worst_b:.3f}")
     # the autograd node; a table whose gathered form nobody uses gets an exactly zero gradient
     for unused in (None, 0, 1, 2):
-        leaves = [r.to(DEV).requires_grad_(True) for r in rels]
+        leaves = [up(r).requires_grad_(True) for r in rels]
         tabs = eg.rel_tables(*leaves, plans)
-        sum((t * d.to(DEV)).sum() for i, (t, d) in enumerate(zip(tabs, douts)) if i != unused).backward()
+        sum((t * up(d)).sum() for i, (t, d) in enumerate(zip(tabs, douts)) if i != unused).backward()
         for i, (leaf, dout, pl) in enumerate(zip(leaves, douts, plans)):
             assert leaf.grad is not None and leaf.grad.shape == leaf.shape
             if i == unused:
@@ -141,17 +148,19 @@ def test_rel_tables_forward_backward_and_an_unused_table(lib, block, D):
                 R.check_bound(leaf.grad, *R.rel_table_bwd64(dout, pl), "RelTablesFn")
 
 
+@pytest.mark.parametrize("D", R.REL_DS)
+@pytest.mark.parametrize("block", R.REL_BLOCKS, ids=R.case_id)
+def test_rel_tables_forward_backward_and_an_unused_table(lib, block, D):
+    case_rel_tables_forward_backward_and_an_unused_table(lib, block, D)
+
+
 # ---- max-pool with arg-max -------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C", R.MAXPOOL_CS)
-@pytest.mark.parametrize("case", R.MAXPOOL_CASES, ids=R.case_id)
-def test_maxpool_ties_go_to_the_first_window_position(lib, case, C):
-    """Inputs from {0, 1, 2}: more than half of the windows tie.  Output, recorded index and input gradient against F.max_pool3d on
-    the CPU (first position in (t, y, x) order wins); an all-negative input tells the -3e38 start value from a zero start."""
+def case_maxpool_ties_go_to_the_first_window_position(lib, case, C, up=to_dev):
     ops, eg = lib
     for negative in (False, True):
         x, dy = R.maxpool_operands(case, C, negative)
         t_out, t_idx, t_dx = R.maxpool_torch(x, case, dy)
-        xd, dyd = x.to(DEV), dy.to(DEV)
+        xd, dyd = up(x), up(dy)
         out, idx = ops.maxpool_tokens_idx(xd, *case)
         R.check_exact(out, t_out, "out")
         R.check_exact(idx, t_idx, "idx")
@@ -162,6 +171,14 @@ def test_maxpool_ties_go_to_the_first_window_position(lib, case, C):
         o.backward(dyd)
         R.check_exact(o, t_out, "MaxPoolTokensFn forward")
         R.check_exact(xl.grad, t_dx, "MaxPoolTokensFn backward")
+
+
+@pytest.mark.parametrize("C", R.MAXPOOL_CS)
+@pytest.mark.parametrize("case", R.MAXPOOL_CASES, ids=R.case_id)
+def test_maxpool_ties_go_to_the_first_window_position(lib, case, C):
+    """Inputs from {0, 1, 2}: more than half of the windows tie.  Output, recorded index and input gradient against F.max_pool3d on
+    the CPU (first position in (t, y, x) order wins); an all-negative input tells the -3e38 start value from a zero start."""
+    case_maxpool_ties_go_to_the_first_window_position(lib, case, C)
 
 
 # ---- token transposes ------------------------------------------------------------------------------------------------------------------
@@ -192,10 +209,7 @@ def test_token_transposes_at_ragged_tiles(lib, off):
 
 
 # ---- pooling convolutions outside the fused path ---------------------------------------------------------------------------------------
-@pytest.mark.parametrize("param_layout", (False, True), ids=("tap-major", "parameter-layout"))
-def test_qkv_pool_per_tensor_route(lib, param_layout):
-    """D = 64: QKVPoolFn takes the per-tensor pool3d kernels (the one-launch form is D = 96 only); filters tap-major [27, D] or in
-    the parameter's own [D, 27] layout.  Against fp64 conv3d autograd, with the figures test_pool_maxpool_relpos_backward uses."""
+def case_qkv_pool_per_tensor_route(lib, param_layout, up=to_dev):
     ops, eg = lib
     c = R.QKVPOOL_CASE
     B, heads, D, size = c["B"], c["heads"], c["D"], c["size"]
@@ -213,13 +227,20 @@ def test_qkv_pool_per_tensor_route(lib, param_layout):
         ref = ref.detach().double().cpu()
         return float((got.detach().double().cpu() - ref).abs().max() / ref.abs().max())
 
-    qd = qkv.to(DEV).requires_grad_(True)
-    wd = [(w.reshape(D, 27) if param_layout else w.reshape(D, 27).t().contiguous()).to(DEV).requires_grad_(True) for w in ws]
+    qd = up(qkv).requires_grad_(True)
+    wd = [up(w.reshape(D, 27) if param_layout else w.reshape(D, 27).t().contiguous()).requires_grad_(True) for w in ws]
     outs = eg.qkv_pool(qd, *wd, size, strides[0], strides[1])
-    sum((o * G.to(DEV)).sum() for o, G in zip(outs, Gs)).backward()
+    sum((o * up(G)).sum() for o, G in zip(outs, Gs)).backward()
     for o, r in zip(outs, refs):
         assert o.shape == r.shape and rel(o, r) < 2e-5
     assert rel(qd.grad, q64.grad) < 5e-5
     for i in range(3):
         ref_dw = w64[i].grad.reshape(D, 27)
         assert rel(wd[i].grad, ref_dw if param_layout else ref_dw.t()) < 5e-5, i
+
+
+@pytest.mark.parametrize("param_layout", (False, True), ids=("tap-major", "parameter-layout"))
+def test_qkv_pool_per_tensor_route(lib, param_layout):
+    """D = 64: QKVPoolFn takes the per-tensor pool3d kernels (the one-launch form is D = 96 only); filters tap-major [27, D] or in
+    the parameter's own [D, 27] layout.  Against fp64 conv3d autograd, with the figures test_pool_maxpool_relpos_backward uses."""
+    case_qkv_pool_per_tensor_route(lib, param_layout)

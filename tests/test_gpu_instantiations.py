@@ -17,6 +17,11 @@ from tests.test_gpu_lowp import DTYPES, OP_RTOL, q as q16
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
+
+def to_dev(t):
+    """The upload of every case body here; tests/test_gpu_guard_bands.py passes tests/_guard.py's ``put`` in its place."""
+    return t.to(DEV)
+
 FWD_TOL = 2e-5          # fp32 forward (test_gpu_ops.py)
 ATTN_BWD_TOL = 5e-5     # attention backward (test_gpu_train_ops.py)
 LN_BWD_TOL = 2e-5       # LayerNorm-family backward (test_gpu_train_ops.py)
@@ -99,11 +104,11 @@ def attention_inputs(C, heads, Lk, dname):
     return qkv, attention_ref(*(t.double() for t in qkv), heads, C ** -0.5)
 
 
-def run_attention_forward(ops, case, dname, family):
+def run_attention_forward(ops, case, dname, family, up=to_dev):
     C, heads, Lk, _ = case
     (qq, k, v), ref = attention_inputs(C, heads, Lk, dname)
     dt = torch.float32 if dname == "fp32" else DTYPES[dname]
-    qd, kd, vd = (t.to(dt).to(DEV) for t in (qq, k, v))
+    qd, kd, vd = (up(t.to(dt)) for t in (qq, k, v))
     poison(qd)
     got = ops.attention(qd, kd, vd, heads, C ** -0.5)
     check(got, ref, FWD_TOL if dname == "fp32" else OP_RTOL[dname], family, ic.attention_id(case), heads=heads)
@@ -137,17 +142,21 @@ def attention_bwd_reference(C, heads, Lk):
     return tuple(t.detach().float() for t in (qq, k, v)) + (go,), (qq.grad, k.grad, v.grad)
 
 
-@pytest.mark.parametrize("case", ic.ATTN_BWD_CASES, ids=ic.attention_id)
-def test_attention_backward(ops, case):
+def case_attention_backward(ops, case, up=to_dev):
     C, heads, Lk, _ = case
     (qq, k, v, go), grads = attention_bwd_reference(C, heads, Lk)
-    qd, kd, vd, god = (t.to(DEV) for t in (qq, k, v, go))
+    qd, kd, vd, god = (up(t) for t in (qq, k, v, go))
     ld = (heads * Lk + 3) // 4 * 4
     poison(qd, (qd.shape[0] * qd.shape[1] * ld, torch.float32), (qd.shape[0] * qd.shape[1] * ld, torch.float32),
            (2 * ld * C, torch.float32), (2 * ld * C, torch.float32))
     got = ops.attention_bwd(qd, kd, vd, god, heads, C ** -0.5)
     for name, g_, r_ in zip(("dq", "dk", "dv"), got, grads):
         check(g_, r_, ATTN_BWD_TOL, f"attention bwd {name}", ic.attention_id(case), heads=heads)
+
+
+@pytest.mark.parametrize("case", ic.ATTN_BWD_CASES, ids=ic.attention_id)
+def test_attention_backward(ops, case):
+    case_attention_backward(ops, case)
 
 
 @pytest.mark.parametrize("C,heads,Lk", ic.ATTN_AUTOGRAD)
@@ -193,13 +202,13 @@ def ln_inputs(C, M, dname):
     return x, g, b, ln_ref(x, g, b)
 
 
-def run_layernorm(ops, C, dname, family):
+def run_layernorm(ops, C, dname, family, up=to_dev):
     dt = torch.float32 if dname == "fp32" else DTYPES[dname]
     for M in ic.row_counts(C):
         x, g, b, ref = ln_inputs(C, M, dname)
-        xd = x.to(dt).to(DEV)
+        xd = up(x.to(dt))
         poison(xd)
-        got = ops.layernorm(xd, g.to(DEV), b.to(DEV), 1e-5)
+        got = ops.layernorm(xd, up(g), up(b), 1e-5)
         check(got, ref, FWD_TOL if dname == "fp32" else OP_RTOL[dname], family, f"C={C} M={M}", tail=min(4, C))
 
 
@@ -222,20 +231,24 @@ def multi_rows(C, n):
     return ([many], [many, 1], [7, many, 1])[n - 1]
 
 
-@pytest.mark.parametrize("C", ic.ROW_WIDTHS)
-def test_layernorm_multi(ops, C):
-    """Up to three tensors of one width in one launch: bit-equal to a launch per tensor, and within the bound of float64."""
+def case_layernorm_multi(ops, C, up=to_dev):
     for n in (1, 2, 3):
         xs = [rnd(f"imx{C}_{t}", M, C) * 1.5 + 0.3 for t, M in enumerate(multi_rows(C, n))]
         gb = [ln_params(C, str(t)) for t in range(n)]
         eps = [1e-5, 1e-6, 1e-5][:n]
-        xd = [x.to(DEV) for x in xs]
-        gd, bd = [g.to(DEV) for g, _ in gb], [b.to(DEV) for _, b in gb]
+        xd = [up(x) for x in xs]
+        gd, bd = [up(g) for g, _ in gb], [up(b) for _, b in gb]
         poison(*xd)
         got = ops.layernorm_multi(xd, gd, bd, eps)
         for t in range(n):
             check(got[t], ln_ref(xs[t], *gb[t], eps[t]), FWD_TOL, "layernorm_multi", f"C={C} n={n} tensor {t}", tail=min(4, C))
             assert torch.equal(got[t], ops.layernorm(xd[t], gd[t], bd[t], eps[t])), (C, n, t)
+
+
+@pytest.mark.parametrize("C", ic.ROW_WIDTHS)
+def test_layernorm_multi(ops, C):
+    """Up to three tensors of one width in one launch: bit-equal to a launch per tensor, and within the bound of float64."""
+    case_layernorm_multi(ops, C)
 
 
 @functools.lru_cache(maxsize=None)
@@ -248,11 +261,11 @@ def ln_bwd_reference(C, M, tag=""):
     return (x, g, dy, add), (xr.grad, gr.grad, br.grad)
 
 
-def run_layernorm_bwd(ops, C, M):
+def run_layernorm_bwd(ops, C, M, up=to_dev):
     from diff_sal_amd import _lib
 
     (x, g, dy, add), (dx, dg, db) = ln_bwd_reference(C, M)
-    xd, gd, dyd, addd = (t.to(DEV) for t in (x, g, dy, add))
+    xd, gd, dyd, addd = (up(t) for t in (x, g, dy, add))
     part = (_lib.load().diffsal_layernorm_bwd_blocks(M, C) * 2 * C, torch.float64)
     for with_add in (False, True):
         poison(xd, part, (2 * C, torch.float32))
@@ -269,11 +282,10 @@ def test_layernorm_backward(ops, C):
         run_layernorm_bwd(ops, C, M)
 
 
-@pytest.mark.parametrize("C", ic.ROW_WIDTHS)
-def test_layernorm_backward_multi(ops, C):
+def case_layernorm_backward_multi(ops, C, up=to_dev):
     for n in (1, 2, 3):
         refs = [ln_bwd_reference(C, M, str(t)) for t, M in enumerate(multi_rows(C, n))]
-        xd, dyd, gd = ([r[0][i].to(DEV) for r in refs] for i in (0, 2, 1))
+        xd, dyd, gd = ([up(r[0][i]) for r in refs] for i in (0, 2, 1))
         poison(*xd)
         dxs, dgs, dbs = ops.layernorm_bwd_multi(xd, dyd, gd, [1e-5] * n)
         for t in range(n):
@@ -281,6 +293,11 @@ def test_layernorm_backward_multi(ops, C):
             check(dxs[t], refs[t][1][0], LN_BWD_TOL, "layernorm_bwd_multi dx", case, tail=min(4, C))
             check(dgs[t], refs[t][1][1], LN_BWD_TOL, "layernorm_bwd_multi dgamma", case, tail=min(4, C))
             check(dbs[t], refs[t][1][2], LN_BWD_TOL, "layernorm_bwd_multi dbeta", case, tail=min(4, C))
+
+
+@pytest.mark.parametrize("C", ic.ROW_WIDTHS)
+def test_layernorm_backward_multi(ops, C):
+    case_layernorm_backward_multi(ops, C)
 
 
 def dwconv3_ref(x, w9, g, b):
@@ -296,21 +313,24 @@ def dwpool_ref(x, wkk, g, b, k):
     return ln_ref(y.flatten(2).transpose(1, 2), g, b)
 
 
+def case_dwconv3_ln(ops, C, W, up=to_dev):
+    N, H = ic.DWCONV_NH
+    x, w9 = rnd(f"idx{C}", N, H, W, C), rnd("idw9", 9, C, scale=0.3)
+    g, b = ln_params(C, "q")
+    xd = up(x)
+    poison(xd)
+    got = ops.dwconv3_ln(xd, up(w9), up(g), up(b))
+    check(got, dwconv3_ref(x, w9, g, b), FWD_TOL, "dwconv3_ln", f"C={C} W={W}", tail=min(4, C))
+
+
 @pytest.mark.parametrize("W", ic.DWCONV_WS)
 @pytest.mark.parametrize("C", ic.ROW_WIDTHS)
 def test_dwconv3_ln(ops, C, W):
     """W = 19: the strip kernel for C <= 256 (ragged last strip of 3 pixels); W = 15: the generic kernel."""
-    N, H = ic.DWCONV_NH
-    x, w9 = rnd(f"idx{C}", N, H, W, C), rnd("idw9", 9, C, scale=0.3)
-    g, b = ln_params(C, "q")
-    xd = x.to(DEV)
-    poison(xd)
-    got = ops.dwconv3_ln(xd, w9.to(DEV), g.to(DEV), b.to(DEV))
-    check(got, dwconv3_ref(x, w9, g, b), FWD_TOL, "dwconv3_ln", f"C={C} W={W}", tail=min(4, C))
+    case_dwconv3_ln(ops, C, W)
 
 
-@pytest.mark.parametrize("C", ic.ROW_WIDTHS)
-def test_dwpool_ln_kv(ops, C):
+def case_dwpool_ln_kv(ops, C, up=to_dev):
     H, W = ic.DWPOOL_HW
     xk, xv = rnd(f"ipk{C}", 2, H, W, C), rnd(f"ipv{C}", 2, H, W, C)
     (gk, bk), (gv, bv) = ln_params(C, "k"), ln_params(C, "v")
@@ -318,18 +338,19 @@ def test_dwpool_ln_kv(ops, C):
         wk, wv = rnd("ipwk", k * k, C, scale=1.0 / k), rnd("ipwv", k * k, C, scale=1.0 / k)
         n_out = 2 * (H // k) * (W // k) * C
         poison((n_out, torch.float32), (n_out, torch.float32))
-        got_k, got_v = ops.dwpool_ln_kv(*(t.to(DEV) for t in (xk, xv, wk, wv, gk, bk, gv, bv)), k)
+        got_k, got_v = ops.dwpool_ln_kv(*(up(t) for t in (xk, xv, wk, wv, gk, bk, gv, bv)), k)
         check(got_k, dwpool_ref(xk, wk, gk, bk, k), FWD_TOL, "dwpool_ln_kv k", f"C={C} k={k}", tail=min(4, C))
         check(got_v, dwpool_ref(xv, wv, gv, bv, k), FWD_TOL, "dwpool_ln_kv v", f"C={C} k={k}", tail=min(4, C))
 
 
-@pytest.mark.parametrize("W", ic.DWCONV_WS)
 @pytest.mark.parametrize("C", ic.ROW_WIDTHS)
-def test_qkv_prep_equals_the_two_entries(ops, C, W):
-    """The merged launch == dwconv3_ln + dwpool_ln_kv bit for bit, and the block's first LayerNorm folded into the loads ==
-    a layernorm launch in front (key input normalised or not): the property of test_depthwise_projections on every width."""
+def test_dwpool_ln_kv(ops, C):
+    case_dwpool_ln_kv(ops, C)
+
+
+def case_qkv_prep_equals_the_two_entries(ops, C, W, up=to_dev):
     N, H = ic.DWCONV_NH
-    dv = lambda t: t.to(DEV)      # noqa: E731
+    dv = up
     xn, xa = dv(rnd(f"iqn{C}", N, H, W, C)), dv(rnd(f"iqa{C}", N, H, W, C))
     w9 = dv(rnd("iqw9", 9, C, scale=0.3))
     norms = [tuple(dv(t) for t in ln_params(C, f"q{i}")) for i in range(4)]
@@ -351,6 +372,14 @@ def test_qkv_prep_equals_the_two_entries(ops, C, W):
             assert all(torch.equal(r_, g_) for r_, g_ in zip(ref3, got3)), (C, W, k, ln_k)
 
 
+@pytest.mark.parametrize("W", ic.DWCONV_WS)
+@pytest.mark.parametrize("C", ic.ROW_WIDTHS)
+def test_qkv_prep_equals_the_two_entries(ops, C, W):
+    """The merged launch == dwconv3_ln + dwpool_ln_kv bit for bit, and the block's first LayerNorm folded into the loads ==
+    a layernorm launch in front (key input normalised or not): the property of test_depthwise_projections on every width."""
+    case_qkv_prep_equals_the_two_entries(ops, C, W)
+
+
 def test_row_entries_refuse_more_than_1024_channels(ops):
     """Argument checks before any launch (DIFFSAL_E_SHAPE = -1), as in test_conv_igemm_rejects_bad_channels."""
     C = ic.ROW_REJECTED_WIDTH
@@ -363,13 +392,17 @@ def test_row_entries_refuse_more_than_1024_channels(ops):
         ops.layernorm_bwd(x, x, v)
 
 
+def case_layernorm_past_the_grid_cap(ops, C, M, up=to_dev):
+    x, g, b, ref = ln_inputs(C, M, "fp32")
+    xd = up(x)
+    poison(xd)
+    check(ops.layernorm(xd, up(g), up(b), 1e-5), ref, FWD_TOL, "layernorm past the grid cap", f"C={C} M={M}")
+
+
 @pytest.mark.parametrize("C,M", ic.LN_PAST_CAP)
 def test_layernorm_past_the_grid_cap(ops, C, M):
     """More rows than 8192 workgroups hold: the grid-stride loop."""
-    x, g, b, ref = ln_inputs(C, M, "fp32")
-    xd = x.to(DEV)
-    poison(xd)
-    check(ops.layernorm(xd, g.to(DEV), b.to(DEV), 1e-5), ref, FWD_TOL, "layernorm past the grid cap", f"C={C} M={M}")
+    case_layernorm_past_the_grid_cap(ops, C, M)
 
 
 @pytest.mark.parametrize("C,M", ic.LN_BWD_PAST_CAP)
@@ -378,19 +411,23 @@ def test_layernorm_backward_past_the_grid_cap(ops, C, M):
     run_layernorm_bwd(ops, C, M)
 
 
-def test_dwconv3_ln_strip_kernel_past_the_grid_cap(ops):
-    """The first batch whose strips exceed 8192 workgroups x 4 lane groups (G = 64): the whole batch against its two halves (each
-    under the cap) bit for bit, and the last image -- where the second trip of the grid-stride loop lands -- against float64."""
+def case_dwconv3_ln_strip_kernel_past_the_grid_cap(ops, up=to_dev):
     N, H, W, C = ic.DWCONV_STRIP_PAST_CAP
     x, w9 = rnd("isx", N, H, W, C), rnd("isw9", 9, C, scale=0.3)
     g, b = ln_params(C, "s")
-    xd, w9d, gd, bd = (t.to(DEV) for t in (x, w9, g, b))
+    xd, w9d, gd, bd = (up(t) for t in (x, w9, g, b))
     poison(xd)
     whole = ops.dwconv3_ln(xd, w9d, gd, bd)
     assert not torch.isnan(whole).any()
     halves = torch.cat([ops.dwconv3_ln(xd[:N // 2], w9d, gd, bd), ops.dwconv3_ln(xd[N // 2:], w9d, gd, bd)])
     assert torch.equal(whole, halves)
     check(whole[-1:], dwconv3_ref(x[-1:], w9, g, b), FWD_TOL, "dwconv3_ln strip past the grid cap", f"N={N} H={H} W={W} C={C}")
+
+
+def test_dwconv3_ln_strip_kernel_past_the_grid_cap(ops):
+    """The first batch whose strips exceed 8192 workgroups x 4 lane groups (G = 64): the whole batch against its two halves (each
+    under the cap) bit for bit, and the last image -- where the second trip of the grid-stride loop lands -- against float64."""
+    case_dwconv3_ln_strip_kernel_past_the_grid_cap(ops)
 
 
 # ---- d. MViT pooling -------------------------------------------------------------------------------------------------------------
@@ -406,23 +443,23 @@ def pool_inputs(D):
             rnd("iPg", D, scale=0.1) + 1, rnd("iPb", D, scale=0.1))
 
 
-@pytest.mark.parametrize("stride", ic.POOL_STRIDES, ids=pool_id)
-@pytest.mark.parametrize("D", ic.POOL_DS, ids=pool_id)
-def test_pool3d_ln(ops, D, stride):
+def case_pool3d_ln(ops, D, stride, up=to_dev):
     qkv, w, g, b = pool_inputs(D)
     ref, ref_size = mo.attention_pool(qkv[:, :, 1].permute(0, 2, 1, 3).double(), w.double(), stride, ic.POOL_SIZE, g.double(), b.double())
     To, Ho, Wo = ((s - 1) // st + 1 for s, st in zip(ic.POOL_SIZE, stride))
     poison((ic.POOL_B * ic.POOL_HEADS * (1 + To * Ho * Wo) * D, torch.float32))
-    got, out_size = ops.pool3d_ln(qkv.to(DEV)[:, :, 1], w.reshape(D, 27).t().contiguous().to(DEV), g.to(DEV), b.to(DEV), ic.POOL_SIZE, stride)
+    got, out_size = ops.pool3d_ln(up(qkv)[:, :, 1], up(w.reshape(D, 27).t().contiguous()), up(g), up(b), ic.POOL_SIZE, stride)
     assert tuple(out_size) == tuple(ref_size) == (To, Ho, Wo)
     check(got, ref, FWD_TOL, "pool3d_ln", f"D={D} stride={stride}")
 
 
 @pytest.mark.parametrize("stride", ic.POOL_STRIDES, ids=pool_id)
 @pytest.mark.parametrize("D", ic.POOL_DS, ids=pool_id)
-def test_pool3d_backward(ops, D, stride):
-    """dx (written through the strides of the q / k / v slice of the fused-qkv gradient) and the filter gradient against float64
-    autograd of the depthwise conv3d with the class token passed through."""
+def test_pool3d_ln(ops, D, stride):
+    case_pool3d_ln(ops, D, stride)
+
+
+def case_pool3d_backward(ops, D, stride, up=to_dev):
     qkv, w, _, _ = pool_inputs(D)
     B, heads, (T, H, W) = ic.POOL_B, ic.POOL_HEADS, ic.POOL_SIZE
     x = qkv[:, :, 1].double().requires_grad_(True)                       # [B, N, heads, D]
@@ -432,11 +469,19 @@ def test_pool3d_backward(ops, D, stride):
     out = torch.cat([x[:, :1].permute(0, 2, 1, 3), y.reshape(B, heads, D, -1).transpose(2, 3)], dim=2)      # [B, heads, 1 + Lo, D]
     dy = rnd(f"iPdy{D}", *out.shape)
     out.backward(dy.double())
-    qd = qkv.to(DEV)
-    dqkv = torch.full_like(qd, float("nan"))
+    qd = up(qkv)
+    dqkv = up(torch.full_like(qkv, float("nan")))
     poison((27 * D, torch.float32))
-    dw = ops.pool3d_bwd(qd[:, :, 1], w.reshape(D, 27).t().contiguous().to(DEV), dy.to(DEV), dqkv[:, :, 1], ic.POOL_SIZE, stride)
+    dw = ops.pool3d_bwd(qd[:, :, 1], up(w.reshape(D, 27).t().contiguous()), up(dy), dqkv[:, :, 1], ic.POOL_SIZE, stride)
     assert torch.isnan(dqkv[:, :, 0]).all() and torch.isnan(dqkv[:, :, 2]).all(), "the neighbouring slices were written"
     case = f"D={D} stride={stride}"
     check(dqkv[:, :, 1], x.grad, POOL_BWD_TOL, "pool3d_bwd dx", case)
     check(dw, wr.grad.reshape(D, 27).t(), POOL_BWD_TOL, "pool3d_bwd dw", case)
+
+
+@pytest.mark.parametrize("stride", ic.POOL_STRIDES, ids=pool_id)
+@pytest.mark.parametrize("D", ic.POOL_DS, ids=pool_id)
+def test_pool3d_backward(ops, D, stride):
+    """dx (written through the strides of the q / k / v slice of the fused-qkv gradient) and the filter gradient against float64
+    autograd of the depthwise conv3d with the class token passed through."""
+    case_pool3d_backward(ops, D, stride)

@@ -19,8 +19,13 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
 
-def dv(t, dname="fp32"):
-    return t.detach().to(DEV).to(vr.DTYPES[dname])
+def to_dev(t):
+    """The upload of the shared case bodies; tests/test_gpu_guard_bands.py passes tests/_guard.py's ``put`` in its place."""
+    return t.to(DEV)
+
+
+def dv(t, dname="fp32", up=to_dev):
+    return up(t.detach().to(DEV).to(vr.DTYPES[dname]))
 
 
 def ids(cases):
@@ -99,20 +104,23 @@ def test_gn_affine_rows(ops, case):
 GN_TRAIN = vr.gn_train_cases()
 
 
+def case_groupnorm_swish_training(agops, case, up=to_dev):
+    t, _, _ = vr.evaluate(case)
+    x, g, b = (dv(t[k], up=up).requires_grad_(True) for k in ("x", "g", "b"))
+    y = agops.groupnorm_swish(x, g, b, 32, vr.GN_EPS)
+    y.backward(dv(t["dy"], up=up))
+    vr.check(case, dict(y=y, dx=x.grad, dgamma=g.grad, dbeta=b.grad), "autograd groupnorm_swish")
+
+
 @pytest.mark.parametrize("case", GN_TRAIN, ids=ids(GN_TRAIN))
 def test_groupnorm_swish_training(agops, case):
-    t, _, _ = vr.evaluate(case)
-    x, g, b = (dv(t[k]).requires_grad_(True) for k in ("x", "g", "b"))
-    y = agops.groupnorm_swish(x, g, b, 32, vr.GN_EPS)
-    y.backward(dv(t["dy"]))
-    vr.check(case, dict(y=y, dx=x.grad, dgamma=g.grad, dbeta=b.grad), "autograd groupnorm_swish")
+    case_groupnorm_swish_training(agops, case)
 
 
 BN = vr.bn_cases()
 
 
-@pytest.mark.parametrize("case", BN, ids=ids(BN))
-def test_batchnorm_training(agops, case):
+def case_batchnorm_training(agops, case, up=to_dev):
     t, _, _ = vr.evaluate(case)
     bn = torch.nn.BatchNorm2d(vr.BN_C, eps=vr.BN_EPS, momentum=0.1).to(DEV)
     with torch.no_grad():
@@ -120,11 +128,18 @@ def test_batchnorm_training(agops, case):
         bn.bias.copy_(t["b"])
         bn.running_mean.copy_(t["rm"])
         bn.running_var.copy_(t["rv"])
-    x = dv(t["x"]).requires_grad_(True)
+    for t_ in (bn.weight, bn.bias, bn.running_mean, bn.running_var):
+        t_.data = up(t_.data)
+    x = dv(t["x"], up=up).requires_grad_(True)
     y = agops.batchnorm_relu_train(x, bn, relu=case.p["relu"])
-    y.backward(dv(t["dy"]))
+    y.backward(dv(t["dy"], up=up))
     vr.check(case, dict(y=y, running_mean=bn.running_mean, running_var=bn.running_var, dx=x.grad, dgamma=bn.weight.grad,
                         dbeta=bn.bias.grad), "autograd batchnorm_relu_train")
+
+
+@pytest.mark.parametrize("case", BN, ids=ids(BN))
+def test_batchnorm_training(agops, case):
+    case_batchnorm_training(agops, case)
 
 
 # ------------------------------------------------------------------------------------------------------------------------
